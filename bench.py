@@ -3,6 +3,13 @@
 
     python bench.py [--gpus N --steps K --warmup W] [--variant noblank|binary|blank]
                     [--scaling weak|strong --global-batch B] [--batch B_per_gpu]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times exactly K steps in one bracketed region and reports them
+(`value` samples/s, `ms_per_step`); `--dump-outputs DIR` then writes what the last timed step
+computed.  `--full` adds everything else the benchmark measures and checks: per-launch kernel
+times and the HBM roofline on them, the secondary collective figures, the co-residence table of
+`--occupant`, the eager Python step, parity against the float64 oracle and the CPU baselines.
 
 A "step" is one pass of the hot path over one batch of synthetic, HBM-resident input:
 loss AND the full input gradient (what `loss = ctc_loss(...); loss.backward()` costs in
@@ -21,7 +28,7 @@ BASELINE north_star; `--loss-bucket 1`, the default), captured into the hipGraph
 and enqueued on the launch stream itself behind `scale_grad` (`--collective-stream same`: no
 cross-stream edge in the graph, no collective kernel resident beside the next loss launch;
 `side` = asynchronous on RCCL's own stream).  `--loss-bucket M` sends the losses of M steps
-through one all-reduce instead; the default run reports that form (M = one graph replay) as the
+through one all-reduce instead; a `--full` run reports that form (M = one graph replay) as the
 secondary figure `bucketed`.  A capture that fails falls back to eager issue and says so.
 
 Prints ONE JSON line on rank 0.
@@ -90,15 +97,25 @@ def parse():
                          "workgroup.  Off by default: inside a captured graph the cross-stream dependencies cost more than the gate saves")
     ap.add_argument("--occupant", type=int, default=None,
                     help="--rehearse-collective: a stand-in for the collective's kernel (a 1-rank all-reduce launches none) -- "
-                         "K workgroups with rcclGenericKernel's footprint resident for --occupant-us on a side stream, and the "
-                         "co-residence measurements of DESIGN.md section 5 (`coresident` in the output)")
+                         "K workgroups with rcclGenericKernel's footprint resident for --occupant-us on a side stream, and with "
+                         "--full the co-residence measurements of DESIGN.md section 5 (`coresident` in the output)")
     ap.add_argument("--occupant-us", type=float, default=15.0)
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="N>1 collective backend: nccl = RCCL over xGMI; gloo only to rehearse the multi-rank "
                          "path on a box with fewer GPUs than ranks (ranks then share devices)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="CPU budget of the oracle baseline leg")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary figures: per-launch kernel times and the roofline on them, the bucketed / "
+                         "per-step collective forms, the co-residence table of --occupant, the eager Python step (unless "
+                         "--no-eager-python), parity against the float64 oracle and the CPU baselines (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, nll, grad) as DIR/<name>.npy "
+                         "(rank 0; see dump_outputs for the size cap)")
+    a = ap.parse_args()
+    if a.steps is not None and a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 class Workload:
@@ -164,6 +181,35 @@ class Workload:
 
 def cur_stream(dev):
     return torch.cuda.current_stream(dev).cuda_stream
+
+
+DUMP_CAP_BYTES = 64_000_000          # --dump-outputs: array data written in all, at most
+DUMP_SAMPLE = 1 << 22                # draws of the seeded sample that stands for an array beyond the cap
+DUMP_SEED = 0
+
+
+def dump_outputs(dirname, arrays, cap_bytes=DUMP_CAP_BYTES, sample=DUMP_SAMPLE, seed=DUMP_SEED):
+    """arrays: name -> tensor, written in order as dirname/<name>.npy (float64 stays float64, anything else becomes
+    float32).  An array that would take the total beyond cap_bytes is written as dirname/<name>_sample.npy instead: its
+    flattened elements at np.unique(np.random.default_rng(seed).integers(0, numel, sample)), the same positions for
+    the same shape in every run.  Returns name -> shape of what was written."""
+    os.makedirs(dirname, exist_ok=True)
+    used, written = 0, {}
+    for name, t in arrays.items():
+        t = t.detach()
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        size = 8 if dt == torch.float64 else 4
+        if used + t.numel() * size > cap_bytes:
+            idx = np.unique(np.random.default_rng(seed).integers(0, t.numel(), min(sample, t.numel())))
+            if used + idx.size * size > cap_bytes:
+                raise RuntimeError("dump_outputs: no room for a sample of %s within %d bytes" % (name, cap_bytes))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            name += "_sample"
+        a = t.to(dt).cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        used += a.nbytes
+        written[name] = list(a.shape)
+    return written
 
 
 def oracle_step(wl, threads, want_grad=True, dtype=np.float32):
@@ -413,7 +459,8 @@ def main():
         graphs = try_capture("the step with its all-reduce", M, collective=True, gate=use_gate, occupant=n_occ)
         if graphs is not None:
             try:
-                graphs[0].replay()
+                for g in graphs:                            # (each graph's first replay uploads it: set-up, not a timed step)
+                    g.replay()
                 torch.cuda.synchronize()
             except Exception as e:                          # noqa: BLE001
                 print("bench: replay of the captured collective failed (%s)" % str(e).splitlines()[0][:200], file=sys.stderr)
@@ -428,6 +475,10 @@ def main():
             capture_note = "graph capture failed: steps issued eagerly"
             launch, M, graphs = "eager", 1, []
             bucket = bucket or 1
+        else:
+            for g in graphs:                                # (each graph's first replay uploads it: set-up, not a timed step)
+                g.replay()
+            torch.cuda.synchronize()
     # Every other graph of this run is captured NOW, before the measurement phase issues its first eager all-reduce:
     # ProcessGroupNCCL's watchdog thread polls the events of eager works, and an event query from another thread while a
     # capture is in progress aborts the process on this stack even in the thread-local capture mode (seen once in round 3
@@ -435,8 +486,8 @@ def main():
     # not handed to the watchdog, so captured collectives are safe; drain() additionally waits out the watchdog's period.
     gp = gb = None
     Mb = max(1, min(a.graph_steps, K))
-    want_per_step = coll and not per_step_collective and a.launch == "graph" and a.backend == "nccl" and launch == "graph"
-    want_bucketed = per_step_collective and a.launch == "graph"
+    want_per_step = a.full and coll and not per_step_collective and a.launch == "graph" and a.backend == "nccl" and launch == "graph"
+    want_bucketed = a.full and per_step_collective and a.launch == "graph"
     if want_per_step:
         gp = try_capture("the per-step all-reduce (secondary figure)", M, collective=True, gate=use_gate, occupant=0)
     if want_bucketed:
@@ -447,7 +498,7 @@ def main():
                 ("allreduce_only_us_per_step", dict(collective=True, gate=False, occupant=0, placement="side")),
                 ("allreduce_same_stream_us_per_step", dict(collective=True, gate=False, occupant=0, placement="same")),
                 ("no_collective_us_per_step", dict(collective=False)))
-    if in_graph and n_occ and world == 1:
+    if a.full and in_graph and n_occ and world == 1:
         for label, kw in co_specs:
             co_graphs[label] = try_capture(label, M, **kw)
 
@@ -472,6 +523,7 @@ def main():
             if coll and not (replayed and graph_collective):
                 pending[k] = dist.all_reduce(rings[k][:max(m, 1)], op=dist.ReduceOp.SUM, async_op=True)
                 state["eager_works"] = True
+            state["last_loss"] = (k, m - 1)                 # where the latest step's loss lands
             state["i"] += 1
             done += m
         for k in (0, 1):
@@ -499,12 +551,13 @@ def main():
         return el
 
     run_steps(W)
-    # K steps are timed in one bracketed region.  A short K (the driver uses 20) is one or two graph
-    # replays, i.e. mostly launch latency of the replay itself: the region is then repeated and the
-    # median taken (>= 50 timed iterations), every repeat timing exactly K steps.
-    repeats = 1 if K >= 100 else min(15, max(3, -(-150 // max(K, 1))))
-    els = sorted(timed(K) for _ in range(repeats))
-    el = els[len(els) // 2]
+    # exactly K steps, timed in one bracketed region (the captured graphs were replayed once during set-up)
+    el = timed(K)
+
+    outputs = None
+    if a.dump_outputs and rank == 0:                        # what the last timed step handed its caller
+        k, j = state["last_loss"]
+        outputs = dump_outputs(a.dump_outputs, {"loss": rings[k][j], "nll": wl.nll, "grad": wl.grad})
 
     # secondary figures for N>1: the same steps with the loss all-reduce amortised over a graph replay (`bucketed`, when
     # the primary run has one all-reduce per step), or with one all-reduce per step captured into the graph
@@ -547,24 +600,25 @@ def main():
             elx = sorted(timed(nb, launch="graph", graphs=gx, M=M, bucket=M, graph_collective=True) for _ in range(3))[1]
             coresident[label] = round(elx / nb * 1e6, 3)
 
-    # ---- dominant kernel: per-launch duration from HIP events on the launch stream
-    n_ev = 200 if variant != "blank" else 20
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_ev)]
-    s = cur_stream(dev)
-    for e0, e1 in ev:
+    # ---- dominant kernel (--full): per-launch duration from HIP events on the launch stream
+    if a.full:
+        n_ev = 200 if variant != "blank" else 20
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_ev)]
+        s = cur_stream(dev)
+        for e0, e1 in ev:
+            e0.record()
+            wl.fused(rings[0].data_ptr(), ws, s)
+            e1.record()
+        torch.cuda.synchronize()
+        per = sorted(e0.elapsed_time(e1) * 1e3 for e0, e1 in ev)          # us
+        kern_us = float(np.mean(per))
+        e0, e1 = ev[0]
         e0.record()
-        wl.fused(rings[0].data_ptr(), ws, s)
+        for _ in range(n_ev):
+            wl.fused(rings[0].data_ptr(), ws, s)
         e1.record()
-    torch.cuda.synchronize()
-    per = sorted(e0.elapsed_time(e1) * 1e3 for e0, e1 in ev)          # us
-    kern_us = float(np.mean(per))
-    e0, e1 = ev[0]
-    e0.record()
-    for _ in range(n_ev):
-        wl.fused(rings[0].data_ptr(), ws, s)
-    e1.record()
-    torch.cuda.synchronize()
-    b2b_us = e0.elapsed_time(e1) * 1e3 / n_ev
+        torch.cuda.synchronize()
+        b2b_us = e0.elapsed_time(e1) * 1e3 / n_ev
 
     out = None
     if rank == 0:
@@ -574,10 +628,6 @@ def main():
             traffic = json.load(open(tpath)).get("%s_B%d" % (variant, B), {}).get("hbm_bytes_per_launch")
             if traffic is not None:
                 traffic_source = "profiles/traffic.json (rocprofv3 --pmc passes of tools/profile.sh, not this run)"
-        # average launch duration: n_ev launches between two HIP events on the launch stream (this
-        # includes the inter-launch gap and is what rocprofv3 --stats reports, profiles/*.md); the
-        # per-launch bracketed figure carries ~2 us of event overhead and is kept for reference
-        achieved = wl.alg_bytes / (b2b_us * 1e-6) / 1e9
         sps = Bg * K / el
         # BASELINE.md section 4's own definition: algorithmic bytes of this rank's batch / the whole timed step
         # (fused launch + the scale_grad boundary of backward [+ the collective]) / peak
@@ -595,21 +645,27 @@ def main():
                                               "one all-reduce per %d steps" % bucket) if coll else None),
                        "launch": launch, "graph_steps": M if launch == "graph" else None,
                        "loss_allreduce_bucket": bucket if coll else None,
-                       "timed_repeats_median_of": repeats,
                        "step": "fused loss+grad launch + scale_grad launch (loss.backward(), grad_out=1)"},
             "lattice_cells_per_sec": round(wl.cells * (Bg / B) * K / el, 1),
             "lattice_cells_per_sec_2Sp1": round(Bg * wl.T * (2 * wl.S + 1) * K / el, 1),
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4),
+            "roofline": {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "achieved_step": round(achieved_step, 1), "frac_step": round(achieved_step / HBM_PEAK_GBS, 4),
                          "frac_step_what": "algorithmic bytes / ms_per_step / peak: the fused launch AND the scale_grad "
                                            "launch of backward (a kernel boundary that moves no data when grad_out == 1)",
                          "traffic": traffic, "traffic_source": traffic_source,
-                         "kernel": "%s fused loss+grad" % variant, "kernel_us_avg": round(b2b_us, 3),
-                         "kernel_us_event_bracketed_avg": round(kern_us, 3),
-                         "kernel_us_event_bracketed_median": round(per[len(per) // 2], 3),
+                         "kernel": "%s fused loss+grad" % variant,
                          "algorithmic_bytes_per_launch": wl.alg_bytes},
         }
+        if a.full:
+            # average launch duration: n_ev launches between two HIP events on the launch stream (this
+            # includes the inter-launch gap and is what rocprofv3 --stats reports, profiles/*.md); the
+            # per-launch bracketed figure carries ~2 us of event overhead and is kept for reference
+            achieved = wl.alg_bytes / (b2b_us * 1e-6) / 1e9
+            out["roofline"].update({"achieved": round(achieved, 1), "frac": round(achieved / HBM_PEAK_GBS, 4),
+                                    "kernel_us_avg": round(b2b_us, 3), "kernel_us_event_bracketed_avg": round(kern_us, 3),
+                                    "kernel_us_event_bracketed_median": round(per[len(per) // 2], 3)})
+        if outputs is not None:
+            out["outputs"] = {"dir": a.dump_outputs, "arrays": outputs, "what": "the last timed step: loss, nll, grad"}
         if bucketed is not None:
             out["bucketed"] = bucketed
         if per_step is not None:
@@ -621,34 +677,35 @@ def main():
             out["config"]["workload"] += "; loss all-reduce every %s" % ("step" if bucket == 1 else "%d steps" % bucket)
         if capture_note:
             out["config"]["note"] = capture_note
-        # (before anything multi-threaded runs on the host: the checker's OpenMP workers keep spinning for a while after
-        # their last parallel region and the autograd engine's thread wake-ups then take 2-3x as long)
-        eager = eager_python_step(wl, 300 if variant != "blank" else 20) if (world == 1 and not a.no_eager_python) else None
-        # parity of THIS batch against the float64 oracle (untimed)
-        ref = oracle_step(wl, threads=min(16, os.cpu_count() or 1), dtype=np.float64)
-        torch.cuda.synchronize()
-        nll_dev = wl.nll.cpu().numpy().astype(np.float64)
-        out["parity"] = {"checker": "oracle/ctc_oracle.c float64",
-                         "max_rel_err_nll": float((np.abs(nll_dev - ref["nll"]) / np.maximum(1.0, np.abs(ref["nll"]))).max()),
-                         "max_abs_err_nll": float(np.abs(nll_dev - ref["nll"]).max()),
-                         "max_abs_err_grad": float(np.abs(wl.grad.cpu().numpy() - ref["grad"] * (B / Bg)).max())}
-        del ref
-        if world == 1 and not a.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(wl, a.cpu_seconds)
-            if variant == "blank":
-                out["cpu_baseline_torch"] = torch_cpu_ctc_baseline(wl, a.cpu_seconds)
-        else:
-            out["cpu_baseline"] = None
-        if eager is not None:
-            step_us, floor_us, fwd_us = eager
-            out["eager_python"] = {"us_per_step": round(step_us, 2),
-                                   "launch": "eager-python",
-                                   "what": "CTCLoss.apply(...) + loss.backward() issued eagerly (train.py:427,444), host-inclusive",
-                                   "torch_floor_us": round(floor_us, 2),
-                                   "torch_floor_what": "x.sum().backward() on the same tensor, same loop: the autograd engine's own cost per eager step",
-                                   "forward_only_us": round(fwd_us, 2),
-                                   "autograd_node": "C++ (ctc_amd/csrc/autograd_ext.cpp)" if (variant != "blank" and _host_ext_loaded())
-                                   else "python (ctc_amd/functional.py)"}
+        if a.full:
+            # (before anything multi-threaded runs on the host: the checker's OpenMP workers keep spinning for a while after
+            # their last parallel region and the autograd engine's thread wake-ups then take 2-3x as long)
+            eager = eager_python_step(wl, 300 if variant != "blank" else 20) if (world == 1 and not a.no_eager_python) else None
+            # parity of THIS batch against the float64 oracle (untimed)
+            ref = oracle_step(wl, threads=min(16, os.cpu_count() or 1), dtype=np.float64)
+            torch.cuda.synchronize()
+            nll_dev = wl.nll.cpu().numpy().astype(np.float64)
+            out["parity"] = {"checker": "oracle/ctc_oracle.c float64",
+                             "max_rel_err_nll": float((np.abs(nll_dev - ref["nll"]) / np.maximum(1.0, np.abs(ref["nll"]))).max()),
+                             "max_abs_err_nll": float(np.abs(nll_dev - ref["nll"]).max()),
+                             "max_abs_err_grad": float(np.abs(wl.grad.cpu().numpy() - ref["grad"] * (B / Bg)).max())}
+            del ref
+            if world == 1 and not a.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(wl, a.cpu_seconds)
+                if variant == "blank":
+                    out["cpu_baseline_torch"] = torch_cpu_ctc_baseline(wl, a.cpu_seconds)
+            else:
+                out["cpu_baseline"] = None
+            if eager is not None:
+                step_us, floor_us, fwd_us = eager
+                out["eager_python"] = {"us_per_step": round(step_us, 2),
+                                       "launch": "eager-python",
+                                       "what": "CTCLoss.apply(...) + loss.backward() issued eagerly (train.py:427,444), host-inclusive",
+                                       "torch_floor_us": round(floor_us, 2),
+                                       "torch_floor_what": "x.sum().backward() on the same tensor, same loop: the autograd engine's own cost per eager step",
+                                       "forward_only_us": round(fwd_us, 2),
+                                       "autograd_node": "C++ (ctc_amd/csrc/autograd_ext.cpp)" if (variant != "blank" and _host_ext_loaded())
+                                       else "python (ctc_amd/functional.py)"}
     if coll:
         if world > 1:
             dist.barrier()

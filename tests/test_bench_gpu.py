@@ -12,10 +12,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
 
-def _bench(*args):
+def _bench(*args, full=True):
+    """full: the secondary figures these tests read (kernel times, roofline, parity, collective forms); the CPU baseline
+    and the eager Python step stay off"""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29547")
+    extra = ("--full", "--no-cpu-baseline", "--no-eager-python") if full else ()
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5",
-                          "--no-cpu-baseline", "--no-eager-python", *args],
+                          *extra, *args],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -33,6 +36,30 @@ def test_bench_line_n1():
     assert r["bound"] == "hbm" and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3 and 0.2 < r["frac"] < 1.0
     assert d["parity"]["max_abs_err_grad"] < 1e-6
     assert d["config"]["collective"] is None
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) reports the headline only, over exactly --steps timed steps; --dump-outputs writes what
+    the last timed step computed, checked here against the float64 oracle on the same seeded batch."""
+    import numpy as np
+    from oracle import ctc_c
+    from tests.helpers import np_, synth_noblank
+    d = _bench("--gpus", "1", "--dump-outputs", str(tmp_path), full=False)
+    assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 5 and d["higher_is_better"] is True
+    assert d["metric"] == "ctc_samples_per_sec" and d["unit"] == "samples/s" and d["dtype"] == "f32"
+    assert math.isfinite(d["value"]) and d["value"] > 1e6
+    assert abs(d["value"] - d["config"]["global_batch"] / (d["ms_per_step"] * 1e-3)) <= 1e-3 * d["value"]
+    for k in ("parity", "cpu_baseline", "eager_python", "bucketed", "coresident"):
+        assert k not in d, k
+    assert "frac" not in d["roofline"] and "kernel_us_avg" not in d["roofline"]
+    assert d["outputs"]["arrays"] == {"loss": [], "nll": [256], "grad": [150, 256, 158]}
+    loss, nll, grad = (np.load(tmp_path / (n + ".npy")) for n in ("loss", "nll", "grad"))
+    assert loss.dtype == nll.dtype == grad.dtype == np.float32
+    x, lab, Tb, L = synth_noblank(0, 150, 256, 158, 20)
+    ref = ctc_c.noblank_ctc(np_(x), np_(lab), np_(Tb), np_(L), np.float64, threads=16)
+    assert np.abs((nll - ref["nll"]) / np.maximum(1.0, np.abs(ref["nll"]))).max() < 1e-5
+    assert abs(float(loss) - float(ref["loss"])) <= 1e-5 * abs(float(ref["loss"]))
+    assert np.abs(grad - ref["grad"]).max() < 1e-6
 
 
 def test_bench_collective_path_rehearsal():

@@ -6,7 +6,7 @@ export CTC_AMD_LIB=ctc_amd/lib/libctc_amd_diag.so
 for B in "$@"; do
   for on in 0 1; do
     if [ $on = 1 ]; then export $SW=1; else unset $SW; fi
-    timeout -k 10 120 python bench.py --variant $V --batch $B --no-cpu-baseline --no-eager-python --steps 200 --warmup 20 2>/dev/null | python -c "
+    timeout -k 10 120 python bench.py --full --variant $V --batch $B --no-cpu-baseline --no-eager-python --steps 200 --warmup 20 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); r = d['roofline']
 print('B=%5d $SW=$on kernel_us %.2f frac %.3f' % ($B, r['kernel_us_avg'], r['frac']))"
