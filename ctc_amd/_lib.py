@@ -9,6 +9,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("CTC_AMD_LIB") or os.path.join(_HERE, "lib", "libctc_amd.so")   # override: kernel experiments
 
 NOBLANK, BINARY, BLANK = 0, 1, 2
+F32, BF16, F16 = 0, 1, 2            # CTC_AMD_F32 / CTC_AMD_BF16 / CTC_AMD_F16: element types of the typed entry points
+ERR_BAD_ARGUMENT = -1
 ABI_VERSION = 2                     # CTC_AMD_ABI_VERSION of include/ctc_amd.h this binding was written for
 ERR_UNSUPPORTED_SHAPE = -2
 ERR_CODE_OVERFLOW = -3
@@ -24,11 +26,14 @@ PROTOTYPES = {
                                          _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "ctc_amd_noblank_smoothed_loss_grad": (_int, [_vp, _i64, _i64, _vp, _int, _vp, _vp, _int, _int, _int, _int, _f32,
                                                   _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "ctc_amd_noblank_loss_grad_typed": (_int, [_vp, _int, _i64, _i64, _vp, _int, _vp, _vp, _int, _int, _int, _int, _f32,
+                                               _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "ctc_amd_binary_loss_grad": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _int, _int, _int, _int,
                                         _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "ctc_amd_blank_loss_grad": (_int, [_vp, _i64, _i64, _vp, _int, _vp, _vp, _int, _int, _int, _int, _int,
                                        _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "ctc_amd_scale_grad": (_int, [_vp, _vp, _sz, _vp]),
+    "ctc_amd_scale_grad_typed": (_int, [_vp, _int, _vp, _sz, _vp]),
     "ctc_amd_collective_gate": (_int, [_vp, _int, _int, _vp]),
     "ctc_amd_binary_posteriors": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _int, _int, _int, _int, _vp, _vp, _vp, _vp]),
     "ctc_amd_lstm_cell_step": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _vp, _vp, _vp,

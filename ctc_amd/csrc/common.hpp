@@ -61,14 +61,24 @@ __device__ __forceinline__ void through_store(wt_f4 *p, wt_f4 v)
 {
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
+// (2-byte gradients: four packed elements are 8 bytes, two are one dword)
+typedef unsigned wt_u2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void through_store(wt_u2 *p, wt_u2 v)
+{
+    asm volatile("global_store_dwordx2 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
+}
+__device__ __forceinline__ void through_store(unsigned *p, unsigned v)
+{
+    asm volatile("global_store_dword %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
+}
 // gradient store of a launch: write-through while logits + gradient fit the memory-side cache, non-temporal
 // beyond it (r16 kernel, T = 150, C = 158, us per launch, write-through / non-temporal: B = 512 25.9 / 30.6,
-// 1024 49.7 / 54.6, 1536 83.9 / 78.2, 2048 133.5 / 101.3)
-template <bool NT, typename V>
+// 1024 49.7 / 54.6, 1536 83.9 / 78.2, 2048 133.5 / 101.3).  `A`: the alignment the address is known to have.
+template <bool NT, typename V, int A = 8>
 __device__ __forceinline__ void grad_store(V *p, V v)
 {
     if (NT) {
-        typedef V __attribute__((aligned(8))) VA;
+        typedef V __attribute__((aligned(A))) VA;
         __builtin_nontemporal_store(v, reinterpret_cast<VA *>(p));
     } else {
         through_store(p, v);

@@ -420,6 +420,63 @@ __global__ __launch_bounds__(256) void scale_grad_kernel(float *g, const float *
     }
 }
 
+// the four-rows-per-wave kernel (noblank_r16.hpp) for a row chunking n4 / n2 (r16_shape): the persistent form when `ps`
+// and two row sets fit the 128 VGPRs of a 16-wave workgroup (4 n4 + 2 n2 <= 12, C <= 192), else one sample per workgroup
+template <typename E>
+static int launch_r16(int n4, int n2, bool nt, bool ps, int cus, size_t rsmem, hipStream_t s, const NoblankParams &p)
+{
+    const dim3 grid(p.B), block(kThreads);
+    if (ps) {
+        const dim3 pgrid(cus);
+#define CTC_R16_CASE(K, A, Bq)                                                                          \
+        case K: return nt ? launch<noblank_r16_kernel<A, Bq, true, true, E>>(pgrid, block, rsmem, s, p)   \
+                          : launch<noblank_r16_kernel<A, Bq, false, true, E>>(pgrid, block, rsmem, s, p);
+        switch (4 * n4 + n2) {
+            CTC_R16_CASE(1, 0, 1) CTC_R16_CASE(2, 0, 2) CTC_R16_CASE(4, 1, 0) CTC_R16_CASE(5, 1, 1)
+            CTC_R16_CASE(6, 1, 2) CTC_R16_CASE(8, 2, 0) CTC_R16_CASE(9, 2, 1) CTC_R16_CASE(10, 2, 2)
+            CTC_R16_CASE(12, 3, 0)
+            default: break;
+        }
+#undef CTC_R16_CASE
+    }
+#define CTC_R16_CASE(K, A, Bq)                                                                          \
+    case K: return nt ? launch<noblank_r16_kernel<A, Bq, true, false, E>>(grid, block, rsmem, s, p)   \
+                      : launch<noblank_r16_kernel<A, Bq, false, false, E>>(grid, block, rsmem, s, p);
+    switch (4 * n4 + n2) {
+        CTC_R16_CASE(1, 0, 1) CTC_R16_CASE(2, 0, 2) CTC_R16_CASE(4, 1, 0) CTC_R16_CASE(5, 1, 1)
+        CTC_R16_CASE(6, 1, 2) CTC_R16_CASE(8, 2, 0) CTC_R16_CASE(9, 2, 1) CTC_R16_CASE(10, 2, 2)
+        CTC_R16_CASE(12, 3, 0) CTC_R16_CASE(13, 3, 1) CTC_R16_CASE(14, 3, 2)
+        default: return nt ? launch<noblank_r16_kernel<4, 0, true, false, E>>(grid, block, rsmem, s, p)
+                           : launch<noblank_r16_kernel<4, 0, false, false, E>>(grid, block, rsmem, s, p);
+    }
+#undef CTC_R16_CASE
+}
+
+// the same for a 2-byte gradient (ctc_amd_scale_grad_typed): round(float(g) * s), 8 bytes per access where the array is
+// 8-byte aligned
+template <typename E>
+__global__ __launch_bounds__(256) void scale_grad_lowp_kernel(E *g, const float *go, size_t n)
+{
+    const float s = *go;
+    if (s == 1.0f) return;                                   // loss.backward(): nothing to do
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    size_t done = 0;
+    if ((reinterpret_cast<uintptr_t>(g) & 7) == 0) {
+        wt_u2 *g4 = reinterpret_cast<wt_u2 *>(g);
+        const size_t n4 = n / 4;
+        const f2_t s2 = {s, s};
+        for (size_t k = i; k < n4; k += stride) {
+            wt_u2 v = g4[k];
+            v.x = r16_narrow2<E>(r16_widen2<E>(v.x) * s2);
+            v.y = r16_narrow2<E>(r16_widen2<E>(v.y) * s2);
+            g4[k] = v;
+        }
+        done = n4 * 4;
+    }
+    for (size_t k = done + i; k < n; k += stride) g[k] = (E)((float)g[k] * s);
+}
+
 template <int K>
 static int launch_noblank(int ch, size_t smem, hipStream_t s, const NoblankParams &p)
 {
@@ -438,15 +495,24 @@ static int launch_noblank(int ch, size_t smem, hipStream_t s, const NoblankParam
 
 using namespace ctc;
 
-// label_smoothing < 0: the plain loss (every kernel); in [0, 1]: the smoothed emission, r16 kernel only
-static int noblank_run(const float *x, int64_t stride_t, int64_t stride_b,
+static bool r16_no_ps()
+{
+    static const bool no_ps = diag_env("CTC_AMD_NOPS") != 0;
+    return no_ps;
+}
+
+// label_smoothing < 0: the plain loss (every kernel); in [0, 1]: the smoothed emission, r16 kernel only.
+// x_dtype CTC_AMD_BF16 / CTC_AMD_F16: 2-byte x and grad, the r16 kernel's shape domain only (include/ctc_amd.h).
+static int noblank_run(const void *xv, int64_t stride_t, int64_t stride_b,
                        const void *labels, int labels_i64,
                        const int64_t *in_len, const int64_t *tgt_len,
                        int T, int B, int C, int S,
                        float loss_scale, float grad_scale,
-                       float *nll, float *loss, float *grad,
-                       void *workspace, void *stream, float label_smoothing)
+                       float *nll, float *loss, void *gradv,
+                       void *workspace, void *stream, float label_smoothing, int x_dtype = CTC_AMD_F32)
 {
+    const float *x = static_cast<const float *>(xv);
+    float *grad = static_cast<float *>(gradv);
     if (!x || !labels || !in_len || !tgt_len || !nll || !loss || !workspace) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (T < 1 || B < 1 || C < 1 || S < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
     int K = 1;
@@ -469,6 +535,23 @@ static int noblank_run(const float *x, int64_t stride_t, int64_t stride_b,
     const bool smooth = label_smoothing >= 0.f;
     p.ls_b = smooth ? (1.f - label_smoothing) / (float)C : 0.f;
     p.ls_a = smooth ? label_smoothing - p.ls_b : 1.f;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (x_dtype != CTC_AMD_F32) {
+        // 2-byte logits: the four-rows-per-wave kernel or nothing (no silent detour through another kernel or an fp32
+        // copy).  Its fp32 conditions with 4-byte instead of 8-byte aligned rows: the kernel moves 8-byte pieces.
+        int n4 = 0, n2 = 0;
+        const bool aligned = C % 2 == 0 && stride_t % 2 == 0 && stride_b % 2 == 0 &&
+                             reinterpret_cast<uintptr_t>(x) % 4 == 0 && reinterpret_cast<uintptr_t>(grad) % 4 == 0;
+        const size_t rsmem = r16_smem_bytes(T, p.SP, C);
+        if (K != 1 || T > kPipeMaxT || !aligned || !r16_shape(C, n4, n2) || p.SP > 31 || rsmem > kMaxLds)
+            return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
+        const int cus = device_cus();
+        const bool nt = (size_t)4 * T * B * C > ((size_t)230 << 20);     // 2 bytes of logits + 2 of gradient per element
+        p.next_round = (B > cus && (size_t)T * ((C * 2 + 127) / 128) <= (size_t)kPipeWorkers * kWave) ? cus : 0;
+        const bool ps = B > 2 * cus && cus > 0 && !r16_no_ps() && p.grad;
+        return x_dtype == CTC_AMD_BF16 ? launch_r16<__bf16>(n4, n2, nt, ps, cus, rsmem, s, p)
+                                       : launch_r16<_Float16>(n4, n2, nt, ps, cus, rsmem, s, p);
+    }
     size_t smem = noblank_smem_bytes(T, p.SP, C);
     if (smem > kMaxLds) {                                    // long sequence: lattice in the workspace
         if (smooth) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
@@ -477,7 +560,6 @@ static int noblank_run(const float *x, int64_t stride_t, int64_t stride_b,
         p.lattice = reinterpret_cast<float *>(static_cast<char *>(workspace) + 256 + acc_list_bytes(B));
         p.slab = (int64_t)noblank_lattice_floats(T, p.SP);
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
     const int ch = C <= 256 ? (C + kWave - 1) / kWave : 0;
     // common case (S <= 64, C <= 256, T <= 168): the pipelined schedule
     static const bool no_pipe = diag_env("CTC_AMD_NOPIPE") != 0;
@@ -528,31 +610,7 @@ static int noblank_run(const float *x, int64_t stride_t, int64_t stride_b,
             // second set of registers (noblank_r16.hpp), wherever two sets fit the 128 VGPRs of a 16-wave workgroup
             // (C <= 192) and a gradient is wanted.  T = 150, C = 158, us per launch persistent / one sample per
             // workgroup: B = 2048 82.7 / 98.0, 1024 41.7 / 45.1, 512 24.3 / 24.1.
-            static const bool no_ps = diag_env("CTC_AMD_NOPS") != 0;
-            if (B > 2 * cus && cus > 0 && !no_ps && p.grad && 4 * n4 + 2 * n2 <= 12) {
-                const dim3 pgrid(cus);
-#define CTC_R16_CASE(K, A, Bq)                                                                          \
-                case K: return nt ? launch<noblank_r16_kernel<A, Bq, true, true>>(pgrid, block, rsmem, s, p)   \
-                                  : launch<noblank_r16_kernel<A, Bq, false, true>>(pgrid, block, rsmem, s, p);
-                switch (4 * n4 + n2) {
-                    CTC_R16_CASE(1, 0, 1) CTC_R16_CASE(2, 0, 2) CTC_R16_CASE(4, 1, 0) CTC_R16_CASE(5, 1, 1)
-                    CTC_R16_CASE(6, 1, 2) CTC_R16_CASE(8, 2, 0) CTC_R16_CASE(9, 2, 1) CTC_R16_CASE(10, 2, 2)
-                    CTC_R16_CASE(12, 3, 0)
-                    default: break;
-                }
-#undef CTC_R16_CASE
-            }
-#define CTC_R16_CASE(K, A, Bq)                                                                          \
-            case K: return nt ? launch<noblank_r16_kernel<A, Bq, true>>(grid, block, rsmem, s, p)         \
-                              : launch<noblank_r16_kernel<A, Bq, false>>(grid, block, rsmem, s, p);
-            switch (4 * n4 + n2) {
-                CTC_R16_CASE(1, 0, 1) CTC_R16_CASE(2, 0, 2) CTC_R16_CASE(4, 1, 0) CTC_R16_CASE(5, 1, 1)
-                CTC_R16_CASE(6, 1, 2) CTC_R16_CASE(8, 2, 0) CTC_R16_CASE(9, 2, 1) CTC_R16_CASE(10, 2, 2)
-                CTC_R16_CASE(12, 3, 0) CTC_R16_CASE(13, 3, 1) CTC_R16_CASE(14, 3, 2)
-                default: return nt ? launch<noblank_r16_kernel<4, 0, true>>(grid, block, rsmem, s, p)
-                                   : launch<noblank_r16_kernel<4, 0, false>>(grid, block, rsmem, s, p);
-            }
-#undef CTC_R16_CASE
+            return launch_r16<float>(n4, n2, nt, B > 2 * cus && cus > 0 && !r16_no_ps() && p.grad, cus, rsmem, s, p);
         }
         if (smooth) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;    // the smoothed emission lives in the kernel above only
         if (!no_xr && xsmem <= kMaxLds && (!dual || 2 * xsmem <= kMaxLds)) {
@@ -633,6 +691,38 @@ extern "C" int ctc_amd_scale_grad(float *grad, const float *grad_out, size_t n, 
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(scale_grad_kernel, dim3((unsigned)blocks), dim3(256), 0,
                        static_cast<hipStream_t>(stream), grad, grad_out, n);
+    return (int)hipGetLastError();
+}
+
+extern "C" int ctc_amd_noblank_loss_grad_typed(const void *x, int x_dtype, int64_t stride_t, int64_t stride_b,
+                                               const void *labels, int labels_i64,
+                                               const int64_t *in_len, const int64_t *tgt_len,
+                                               int T, int B, int C, int S, float label_smoothing,
+                                               float loss_scale, float grad_scale,
+                                               float *nll, float *loss, void *grad,
+                                               void *workspace, void *stream)
+{
+    if (x_dtype != CTC_AMD_F32 && x_dtype != CTC_AMD_BF16 && x_dtype != CTC_AMD_F16) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (label_smoothing != label_smoothing || label_smoothing > 1.f) return CTC_AMD_ERR_BAD_ARGUMENT;
+    return noblank_run(x, stride_t, stride_b, labels, labels_i64, in_len, tgt_len, T, B, C, S, loss_scale, grad_scale,
+                       nll, loss, grad, workspace, stream, label_smoothing < 0.f ? -1.f : label_smoothing, x_dtype);
+}
+
+extern "C" int ctc_amd_scale_grad_typed(void *grad, int dtype, const float *grad_out, size_t n, void *stream)
+{
+    if (dtype == CTC_AMD_F32) return ctc_amd_scale_grad(static_cast<float *>(grad), grad_out, n, stream);
+    if ((dtype != CTC_AMD_BF16 && dtype != CTC_AMD_F16) || !grad || !grad_out) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (n == 0) return 0;
+    size_t blocks = (n / 4 + 255) / 256;                     // (the grid of ctc_amd_scale_grad)
+    static const int cap = diag_env("CTC_AMD_SCALE_BLOCKS", 1024);
+    if (blocks > (size_t)cap) blocks = cap;
+    if (blocks < 1) blocks = 1;
+    if (dtype == CTC_AMD_BF16)
+        hipLaunchKernelGGL(scale_grad_lowp_kernel<__bf16>, dim3((unsigned)blocks), dim3(256), 0,
+                           static_cast<hipStream_t>(stream), static_cast<__bf16 *>(grad), grad_out, n);
+    else
+        hipLaunchKernelGGL(scale_grad_lowp_kernel<_Float16>, dim3((unsigned)blocks), dim3(256), 0,
+                           static_cast<hipStream_t>(stream), static_cast<_Float16 *>(grad), grad_out, n);
     return (int)hipGetLastError();
 }
 

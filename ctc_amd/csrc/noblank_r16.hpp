@@ -346,8 +346,43 @@ typedef float f4u_t __attribute__((ext_vector_type(4), aligned(8)));   // rows i
 // (tools/micro/rw_phase.hip: the launch's whole read-then-write traffic takes 7.6 us in 8-byte and
 // 5.8 us in 16-byte pieces), and the same goes for the LDS tile.  Only the LAST chunk can stick out
 // of the row (C even; a float4 last chunk only when C % 4 == 0, see r16_shape).
+//
+// E: the element type of x and grad in global memory -- float, or the 2-byte __bf16 / _Float16.  A 2-byte row keeps
+// the same lane-to-column layout: a 4-element chunk is ONE 8-byte load / store, a 2-element chunk one 4-byte access
+// (4-byte aligned rows).  The row waits in registers as loaded (`ra`, `rc`: half the registers of the fp32 form, which
+// is what the next sample's rows of the PS form cost) until widen() makes the fp32 elements `a`, `c` that everything
+// downstream works on; bf16 widens by a 16-bit shift, fp16 by v_cvt_f32_f16, both exact.  The gradient is the fp32
+// value of the fp32 kernel, rounded once to nearest even (v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32).
+typedef unsigned u2a4_t __attribute__((ext_vector_type(2), aligned(4)));   // 8 bytes of a 2-byte row: 4-byte aligned only
+template <typename E>
+__device__ __forceinline__ f2_t r16_widen2(unsigned u)     // two 2-byte elements, the lower address in the low half
+{
+    if constexpr (__is_same(E, __bf16)) {
+        const f2_t f = {__builtin_bit_cast(float, u << 16), __builtin_bit_cast(float, u & 0xffff0000u)};
+        return f;
+    } else {
+        typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
+        return __builtin_convertvector(__builtin_bit_cast(h2_t, u), f2_t);
+    }
+}
+template <typename E>
+__device__ __forceinline__ unsigned r16_narrow2(f2_t v)    // round to nearest even (NaN stays NaN)
+{
+    typedef E e2_t __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, e2_t));
+}
+
+template <bool kRaw, int N4, int N2>
+struct R16RawRegs {};                                        // fp32 rows: nothing (the fp32 kernel's code stays as it was)
 template <int N4, int N2>
-struct R16Row {
+struct R16RawRegs<true, N4, N2> {                            // 2-byte rows: as loaded, until widen()
+    wt_u2 ra[N4 > 0 ? N4 : 1];
+    unsigned rc[N2 > 0 ? N2 : 1];
+};
+
+template <int N4, int N2, typename E = float>
+struct R16Row : R16RawRegs<sizeof(E) == 2, N4, N2> {
+    static constexpr bool kLowp = sizeof(E) == 2;
     f4_t a[N4 > 0 ? N4 : 1];
     f2_t c[N2 > 0 ? N2 : 1];
     static constexpr int kCols = 64 * N4 + 32 * N2;
@@ -356,14 +391,37 @@ struct R16Row {
     __device__ static __forceinline__ int off2(int k, int i16) { return 64 * N4 + 32 * k + 2 * i16; }
     __device__ static __forceinline__ int off_last(int i16) { return kLast4 ? off4(N4 - 1, i16) : off2(N2 - 1, i16); }
 
-    __device__ __forceinline__ void load(const float *row, int i16, int c_last)
+    __device__ __forceinline__ void load(const E *row, int i16, int c_last)
     {
+        if constexpr (kLowp) {
 #pragma unroll
-        for (int j = 0; j < N4; ++j)
-            a[j] = *reinterpret_cast<const f4u_t *>(row + ((kLast4 && j == N4 - 1) ? c_last : off4(j, i16)));
+            for (int j = 0; j < N4; ++j)
+                this->ra[j] = *reinterpret_cast<const u2a4_t *>(row + ((kLast4 && j == N4 - 1) ? c_last : off4(j, i16)));
 #pragma unroll
-        for (int k = 0; k < N2; ++k)
-            c[k] = *reinterpret_cast<const f2_t *>(row + (k == N2 - 1 ? c_last : off2(k, i16)));
+            for (int k = 0; k < N2; ++k)
+                this->rc[k] = *reinterpret_cast<const unsigned *>(row + (k == N2 - 1 ? c_last : off2(k, i16)));
+        } else {
+#pragma unroll
+            for (int j = 0; j < N4; ++j)
+                a[j] = *reinterpret_cast<const f4u_t *>(row + ((kLast4 && j == N4 - 1) ? c_last : off4(j, i16)));
+#pragma unroll
+            for (int k = 0; k < N2; ++k)
+                c[k] = *reinterpret_cast<const f2_t *>(row + (k == N2 - 1 ? c_last : off2(k, i16)));
+        }
+    }
+    // 2-byte rows: the loaded elements -> fp32 registers (fp32 rows: nothing to do).  Where the row is first used: a
+    // conversion right behind the load would make the compiler wait for the load there.
+    __device__ __forceinline__ void widen()
+    {
+        if constexpr (kLowp) {
+#pragma unroll
+            for (int j = 0; j < N4; ++j) {
+                const f2_t lo = r16_widen2<E>(this->ra[j].x), hi = r16_widen2<E>(this->ra[j].y);
+                a[j] = f4_t{lo.x, lo.y, hi.x, hi.y};
+            }
+#pragma unroll
+            for (int k = 0; k < N2; ++k) c[k] = r16_widen2<E>(this->rc[k]);
+        }
     }
     // largest element.  No mask: a lane whose last chunk would stick out of the row was given the row's LAST chunk
     // instead (`c_last`), and duplicates do not change a maximum.  Plain v_max3 / v_max (the values are loaded
@@ -448,7 +506,7 @@ struct R16Row {
     // grad row = x * rs + tile, the tile holding MINUS the class occupancy (nothing to negate here), written through;
     // `g` = start of the row in grad (`cb`: a constant added to every element -- the label-smoothing term, 0 otherwise)
     template <bool NT, bool LS>
-    __device__ __forceinline__ void store_grad(float *g, const float *trow, int i16, float rs, bool col_ok, float cb) const
+    __device__ __forceinline__ void store_grad(E *g, const float *trow, int i16, float rs, bool col_ok, float cb) const
     {
         const f2_t r2 = {rs, rs}, cb2 = {cb, cb};
         // every tile read first, then the arithmetic and the stores: a gradient store is inline asm with a memory clobber,
@@ -467,28 +525,55 @@ struct R16Row {
             if (LS) { olo += cb2; ohi += cb2; }
             const f2_t xlo = {a[j].x, a[j].y}, xhi = {a[j].z, a[j].w};
             const f2_t vlo = __builtin_elementwise_fma(xlo, r2, olo), vhi = __builtin_elementwise_fma(xhi, r2, ohi);
-            const f4_t v = {vlo.x, vlo.y, vhi.x, vhi.y};
-            if (!(kLast4 && j == N4 - 1) || col_ok) grad_store<NT>(reinterpret_cast<f4_t *>(g + off4(j, i16)), v);
+            if (!(kLast4 && j == N4 - 1) || col_ok) {
+                if constexpr (kLowp) {
+                    const wt_u2 n = {r16_narrow2<E>(vlo), r16_narrow2<E>(vhi)};
+                    grad_store<NT, wt_u2, 4>(reinterpret_cast<wt_u2 *>(g + off4(j, i16)), n);
+                } else {
+                    const f4_t v = {vlo.x, vlo.y, vhi.x, vhi.y};
+                    grad_store<NT>(reinterpret_cast<f4_t *>(g + off4(j, i16)), v);
+                }
+            }
         }
 #pragma unroll
         for (int k = 0; k < N2; ++k) {
             f2_t o = o2[k];
             if (LS) o += cb2;
             const f2_t v = __builtin_elementwise_fma(c[k], r2, o);
-            if (k < N2 - 1 || col_ok) grad_store<NT>(reinterpret_cast<f2_t *>(g + off2(k, i16)), v);
+            if (k < N2 - 1 || col_ok) {
+                if constexpr (kLowp) grad_store<NT, unsigned, 4>(reinterpret_cast<unsigned *>(g + off2(k, i16)), r16_narrow2<E>(v));
+                else grad_store<NT>(reinterpret_cast<f2_t *>(g + off2(k, i16)), v);
+            }
         }
     }
     // a "use" of every register of the row: where the compiler waits for the row's loads
     __device__ __forceinline__ void touch() const
     {
+        if constexpr (kLowp) {
 #pragma unroll
-        for (int j = 0; j < N4; ++j) asm volatile("" ::"v"(a[j]));
+            for (int j = 0; j < N4; ++j) asm volatile("" ::"v"(this->ra[j]));
 #pragma unroll
-        for (int k = 0; k < N2; ++k) asm volatile("" ::"v"(c[k]));
+            for (int k = 0; k < N2; ++k) asm volatile("" ::"v"(this->rc[k]));
+        } else {
+#pragma unroll
+            for (int j = 0; j < N4; ++j) asm volatile("" ::"v"(a[j]));
+#pragma unroll
+            for (int k = 0; k < N2; ++k) asm volatile("" ::"v"(c[k]));
+        }
     }
     template <bool NT>
-    __device__ static __forceinline__ void store_zero(float *g, int i16, bool col_ok)
+    __device__ static __forceinline__ void store_zero(E *g, int i16, bool col_ok)
     {
+        if constexpr (kLowp) {
+            const wt_u2 z4 = {0u, 0u};
+#pragma unroll
+            for (int j = 0; j < N4; ++j)
+                if (!(kLast4 && j == N4 - 1) || col_ok) grad_store<NT, wt_u2, 4>(reinterpret_cast<wt_u2 *>(g + off4(j, i16)), z4);
+#pragma unroll
+            for (int k = 0; k < N2; ++k)
+                if (k < N2 - 1 || col_ok) grad_store<NT, unsigned, 4>(reinterpret_cast<unsigned *>(g + off2(k, i16)), 0u);
+            return;
+        }
         const f4_t z4 = {0.f, 0.f, 0.f, 0.f};
         const f2_t z2 = {0.f, 0.f};
 #pragma unroll
@@ -519,11 +604,18 @@ static bool r16_shape(int C, int &n4, int &n2)
 // while this sample's chains run (instead of the 4-byte-per-line L2 prefetch of the one-sample form), so the next
 // sample starts with its rows, lengths and labels already there.  Two workgroup barriers per sample (everyone is done
 // with the lattice / the lattice is initialised); N4 / N2 whose two row sets do not fit 128 VGPRs keep the other form.
-template <int N4, int N2, bool NT, bool PS = false>
+// E: element type of x and grad (R16Row); p.x / p.grad then hold the addresses of 2-byte arrays, p.st / p.sb count
+// elements of E.
+template <typename E>
+__device__ __forceinline__ const E *r16_xrow(const NoblankParams &p, int t, int b)
+{
+    return reinterpret_cast<const E *>(p.x) + (int64_t)t * p.st + (int64_t)b * p.sb;
+}
+template <int N4, int N2, bool NT, bool PS = false, typename E = float>
 __global__ __launch_bounds__(kThreads, 4) void noblank_r16_kernel(NoblankParams p)
 {
     extern __shared__ float4 smem_raw[];
-    typedef R16Row<N4, N2> Row;
+    typedef R16Row<N4, N2, E> Row;
     constexpr int RP = Row::kCols;                           // floats per staged row
     constexpr int G = kPipeRows / 4;                         // groups of four rows per worker
     const R16Smem sm(reinterpret_cast<float *>(smem_raw), p.T, p.SP, RP);
@@ -581,8 +673,8 @@ __global__ __launch_bounds__(kThreads, 4) void noblank_r16_kernel(NoblankParams 
 #pragma unroll
         for (int g = 0; g < G; ++g) {
             tv0[g] = r16_row(p.T, u, g, rho);
-            if (g >= NX) v[g].load(row_ptr(p, tv0[g] >= 0 ? tv0[g] : 0, b), i16, c_last);
-            else nx[g].load(row_ptr(p, tv0[g] >= 0 ? tv0[g] : 0, b), i16, c_last);
+            if (g >= NX) v[g].load(r16_xrow<E>(p, tv0[g] >= 0 ? tv0[g] : 0, b), i16, c_last);
+            else nx[g].load(r16_xrow<E>(p, tv0[g] >= 0 ? tv0[g] : 0, b), i16, c_last);
         }
         stamp_setup(p, 1);                                   // loads issued
         if (PS) {
@@ -728,7 +820,7 @@ __global__ __launch_bounds__(kThreads, 4) void noblank_r16_kernel(NoblankParams 
     // is published, every scale is 0, the gradient rows come out as zeros): ONE path through the loop.  The compiler
     // places its waits for the next sample's row loads by control-flow paths; with a side path that loads and leaves,
     // the main path waited for its own last gradient stores at the end of every sample.
-    const bool has_grad = PS || p.grad != nullptr, has_gamma = !PS && p.gamma != nullptr;
+    const bool has_grad = PS || p.grad != nullptr, has_gamma = !PS && !Row::kLowp && p.gamma != nullptr;
     // PS: the next sample's rows into the spare register set (all of this sample's rows are in `v` by then)
     // (unconditional, like every load of a next sample's rows: behind the workgroup's last sample they fetch that
     // sample's rows once more, and nobody waits for them -- a load under a condition leaves the compiler with two
@@ -736,20 +828,20 @@ __global__ __launch_bounds__(kThreads, 4) void noblank_r16_kernel(NoblankParams 
     auto load_next = [&]() {
         if (!PS) return;
 #pragma unroll
-        for (int g = 0; g < NX; ++g) nx[g].load(row_ptr(p, tv[g] >= 0 ? tv[g] : 0, bn), i16, c_last);
+        for (int g = 0; g < NX; ++g) nx[g].load(r16_xrow<E>(p, tv[g] >= 0 ? tv[g] : 0, bn), i16, c_last);
     };
     // ... and of the groups that are loaded in place, once this sample no longer needs the registers
 #define CTC_R16_RELOAD(g)                                                                             \
     do {                                                                                              \
-        if (PS && (g) >= NX) v[g].load(row_ptr(p, tv[g] >= 0 ? tv[g] : 0, bn), i16, c_last); \
+        if (PS && (g) >= NX) v[g].load(r16_xrow<E>(p, tv[g] >= 0 ? tv[g] : 0, bn), i16, c_last); \
     } while (0)
     if (!PS && Tb == 0) {                                    // no alignment exists: zero gradient
         if (p.grad) {
 #pragma unroll
             for (int g = 0; g < G; ++g)
-                if (tv[g] >= 0) Row::template store_zero<NT>(p.grad + ((int64_t)tv[g] * p.B + b) * p.C, i16, col_ok);
+                if (tv[g] >= 0) Row::template store_zero<NT>(reinterpret_cast<E *>(p.grad) + ((int64_t)tv[g] * p.B + b) * p.C, i16, col_ok);
         }
-        if (p.gamma) {                                       // posteriors of a sample without alignment: zeros
+        if (!Row::kLowp && p.gamma) {                                       // posteriors of a sample without alignment: zeros
 #pragma unroll
             for (int g = 0; g < G; ++g)
                 for (int l = i16; l < p.S && tv[g] >= 0; l += 16) p.gamma[((int64_t)b * p.T + tv[g]) * p.S + l] = 0.f;
@@ -783,6 +875,7 @@ __global__ __launch_bounds__(kThreads, 4) void noblank_r16_kernel(NoblankParams 
         if (g < NX) v[g] = nx[g];
         if (grp[g]) {
             Row &x = v[g];
+            x.widen();
             const int t = tv[g];
             const bool live = t >= 0 && t < Tb;
             float m = x.max();
@@ -868,18 +961,18 @@ __global__ __launch_bounds__(kThreads, 4) void noblank_r16_kernel(NoblankParams 
     }
     // More samples than CUs: the workgroup that follows this one on the CU (dispatch order: block + one full
     // round of CUs, the same XCD under round-robin placement -- speed only) will want the rows of ITS sample.
-    // One 4-byte load per lane, one 128-byte line each, pulls that sample into this XCD's L2 while the chains
-    // of this one run: 14 workers x 64 lanes cover its T rows of C floats.  The value is never used.
+    // One element load per lane, one 128-byte line each, pulls that sample into this XCD's L2 while the chains
+    // of this one run: 14 workers x 64 lanes cover its T rows of C elements.  The value is never used.
     float prefetched = 0.f;
     if (!PS && p.next_round > 0 && (int)blockIdx.x + p.next_round < p.B) {
         const int nb = xcd_sample(blockIdx.x + p.next_round, p.B);
         const int line = u * kWave + lane;                   // 0 .. 895
-        const int lines_per_row = (p.C * 4 + 127) / 128;
-        const int t = line / lines_per_row, c = (line - t * lines_per_row) * 32;
+        const int lines_per_row = (p.C * (int)sizeof(E) + 127) / 128;
+        const int t = line / lines_per_row, c = (line - t * lines_per_row) * (128 / (int)sizeof(E));
         // (plain load through the compiler: it keeps the destination register reserved until the value is
         // there; the add below is the "use", placed where the load has long returned)
-        typedef const float __attribute__((address_space(1))) gfloat;
-        if (t < p.T) prefetched = *(gfloat *)(row_ptr(p, t, nb) + (c < p.C ? c : p.C - 1));
+        typedef const E __attribute__((address_space(1))) gelem;
+        if (t < p.T) prefetched = (float)*(gelem *)(r16_xrow<E>(p, t, nb) + (c < p.C ? c : p.C - 1));
     }
     if (!has_grad && !has_gamma) return;
 
@@ -916,10 +1009,10 @@ __global__ __launch_bounds__(kThreads, 4) void noblank_r16_kernel(NoblankParams 
     int crow[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) crow[s] = opaque_v((lst[s] < p.SP ? lst[s] : p.SP) * sm.TP);
-    float *grow[G];
+    E *grow[G];
 #pragma unroll
     for (int g = 0; g < G; ++g) {
-        grow[g] = p.grad + ((int64_t)(tv[g] > 0 ? tv[g] : 0) * p.B + b) * p.C;
+        grow[g] = reinterpret_cast<E *>(p.grad) + ((int64_t)(tv[g] > 0 ? tv[g] : 0) * p.B + b) * p.C;
         asm volatile("" : "+v"(grow[g]));
     }
     bool starved = false;
@@ -1018,7 +1111,7 @@ __global__ __launch_bounds__(kThreads, 4) void noblank_r16_kernel(NoblankParams 
         lds_order();
         // dense rows: grad = softmax(x) * scale - occupancy   (dead rows: scale = occupancy = 0)
         if (t >= 0) {
-            float *gp = grow[g];
+            E *gp = grow[g];
             if (smooth) x.template store_grad<NT, true>(gp, trow, i16, rs[g] * (1.f - p.ls_b), col_ok, live ? -p.ls_b * gsc : 0.f);
             else x.template store_grad<NT, false>(gp, trow, i16, rs[g], col_ok, 0.f);
         }

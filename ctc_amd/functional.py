@@ -27,6 +27,9 @@ from . import _lib
 _workspaces = {}           # (device index, raw stream, variant) -> [tensor, ...]; the LAST one is current
 _ws_need = {}              # (variant, T, B, C, S) -> bytes
 _VALIDATE = os.environ.get("CTC_AMD_VALIDATE", "0") == "1"
+# 2-byte logits the no-blank loss reads natively (include/ctc_amd.h, ctc_amd_noblank_loss_grad_typed)
+_LOWP_CODE = {torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
+_LOWP_DOMAIN = ("C even <= 256, S <= 31, T <= 168, even strides and 4-byte aligned rows")
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
@@ -194,8 +197,10 @@ def _launch(variant, x, targets, in_len, tgt_len, want_grad, batch_total, blank=
         _require_hip(x, "log_probs")
     if x.dim() != 3:
         raise ValueError("ctc_amd: log_probs must be [T,B,C], got %s" % (tuple(x.shape),))
-    if x.dtype is not torch.float32:
-        raise ValueError("ctc_amd: log_probs must be float32 (the engine computes in fp32), got %s" % x.dtype)
+    lowp = _LOWP_CODE.get(x.dtype) if variant == _lib.NOBLANK else None
+    if x.dtype is not torch.float32 and lowp is None:
+        raise ValueError("ctc_amd: log_probs must be float32 (the engine computes in fp32; the no-blank loss also reads "
+                         "bfloat16 / float16), got %s" % x.dtype)
     T, B, C = x.shape
     if T < 1 or B < 1 or C < 1:
         raise ValueError("ctc_amd: empty log_probs %s" % (tuple(x.shape),))
@@ -231,14 +236,27 @@ def _launch(variant, x, targets, in_len, tgt_len, want_grad, batch_total, blank=
     # on a view returned by a custom Function (`loss /= accum_steps`, `loss += aux` in a training loop)
     nll = torch.empty(B, dtype=torch.float32, device=dev)
     loss = torch.empty((), dtype=torch.float32, device=dev)
-    grad = torch.empty((T, B, C), dtype=torch.float32, device=dev) if want_grad else None
+    grad = torch.empty((T, B, C), dtype=x.dtype, device=dev) if want_grad else None
     lib = _lib.load()
     with _on_device(dev):
         stream = _stream_handle(dev)
         ws = _workspace(variant, T, B, C, S, dev, stream)
         gp = grad.data_ptr() if want_grad else None
         op, lp_ = nll.data_ptr(), loss.data_ptr()
-        if variant == _lib.NOBLANK and label_smoothing is not None:
+        if lowp is not None:
+            ls = -1.0 if label_smoothing is None else float(label_smoothing)
+            if label_smoothing is not None and not 0.0 <= ls <= 1.0:   # (< 0 means "plain" to the typed entry)
+                _lib.check(_lib.ERR_BAD_ARGUMENT, "ctc_amd_noblank_loss_grad_typed")
+            rc = lib.ctc_amd_noblank_loss_grad_typed(
+                xs.data_ptr(), lowp, st, sb, tg.data_ptr(), int(tg.dtype is torch.int64),
+                il.data_ptr(), tl.data_ptr(), T, B, C, S, ls, scale, scale, op, lp_, gp, ws.data_ptr(), stream)
+            if rc == _lib.ERR_UNSUPPORTED_SHAPE:
+                raise _lib.CtcAmdError(
+                    "ctc_amd: %s logits [T=%d, B=%d, C=%d] with S=%d are outside the no-blank loss's reduced-precision "
+                    "domain (%s); pass log_probs.float() for other shapes" % (x.dtype, T, B, C, S, _LOWP_DOMAIN))
+            if rc:
+                _lib.check(rc, "ctc_amd_noblank_loss_grad_typed")
+        elif variant == _lib.NOBLANK and label_smoothing is not None:
             rc = lib.ctc_amd_noblank_smoothed_loss_grad(
                 xs.data_ptr(), st, sb, tg.data_ptr(), int(tg.dtype is torch.int64),
                 il.data_ptr(), tl.data_ptr(), T, B, C, S, float(label_smoothing), scale, scale,
@@ -285,7 +303,11 @@ def _scaled_grad(ctx, gout):
         g = g.detach().to(device=grad.device, dtype=torch.float32).contiguous()
     dev = grad.device
     with _on_device(dev):
-        rc = _lib.load().ctc_amd_scale_grad(grad.data_ptr(), g.data_ptr(), grad.numel(), _stream_handle(dev))
+        if grad.dtype is torch.float32:
+            rc = _lib.load().ctc_amd_scale_grad(grad.data_ptr(), g.data_ptr(), grad.numel(), _stream_handle(dev))
+        else:                               # the no-blank loss's bf16 / fp16 gradient
+            rc = _lib.load().ctc_amd_scale_grad_typed(grad.data_ptr(), _LOWP_CODE[grad.dtype], g.data_ptr(),
+                                                      grad.numel(), _stream_handle(dev))
     if rc:
         _lib.check(rc, "ctc_amd_scale_grad")
     return grad

@@ -93,6 +93,28 @@ int ctc_amd_noblank_smoothed_loss_grad(const float *x, int64_t stride_t, int64_t
                                        float *nll, float *loss, float *grad,
                                        void *workspace, void *stream);
 
+/* Element types of the logits and the gradient for the typed entry points below. */
+#define CTC_AMD_F32  0
+#define CTC_AMD_BF16 1
+#define CTC_AMD_F16  2
+
+/* ctc_amd_noblank_loss_grad / ctc_amd_noblank_smoothed_loss_grad with the element type of x and grad as an argument
+ * (mixed-precision training: logits under autocast come out in bf16 / fp16).  label_smoothing < 0: the plain loss;
+ * in [0, 1]: the smoothed emission.  x_dtype CTC_AMD_F32 is exactly the untyped entries, every kernel and shape.
+ * CTC_AMD_BF16 / CTC_AMD_F16: x [T,B,C] and grad [T,B,C] are 2-byte arrays (strides in elements); x is read as it
+ * is and widened to fp32 in registers (exactly), the arithmetic is that of the fp32 launch, and grad is the fp32
+ * value rounded once to nearest even -- on the same values nll, loss and grad are bitwise the fp32 launch's
+ * nll, loss and grad converted to x_dtype.  nll and loss stay fp32.  Shapes: C even <= 256, S <= 31, T <= 168,
+ * even strides, x and grad 4-byte aligned (the four-rows-per-wave kernel); others return
+ * CTC_AMD_ERR_UNSUPPORTED_SHAPE.  Any other x_dtype: CTC_AMD_ERR_BAD_ARGUMENT. */
+int ctc_amd_noblank_loss_grad_typed(const void *x, int x_dtype, int64_t stride_t, int64_t stride_b,
+                                    const void *labels, int labels_i64,
+                                    const int64_t *in_len, const int64_t *tgt_len,
+                                    int T, int B, int C, int S, float label_smoothing,
+                                    float loss_scale, float grad_scale,
+                                    float *nll, float *loss, void *grad,
+                                    void *workspace, void *stream);
+
 /* NoBlankBinaryCTC.forward (NoBlankBinaryCTC.py:139-151) + gradient.  Same as above
  * except   y [B,S,C] fp32 multi-hot / soft targets in [0,1], contiguous;
  * emission = -BCELoss(sigmoid(x[t,b,:]), y[b,l,:]) (:112,:88, logs clamped at -100);
@@ -167,6 +189,11 @@ int ctc_amd_collective_gate(void *workspace, int B, int timeout_us, void *stream
  * at once when it is exactly 1.0f (the loss.backward() case, train.py:444), so the
  * common case moves no data and needs no host synchronisation. */
 int ctc_amd_scale_grad(float *grad, const float *grad_out, size_t n, void *stream);
+
+/* ctc_amd_scale_grad for a gradient of element type `dtype` (CTC_AMD_F32 / _BF16 / _F16, as
+ * ctc_amd_noblank_loss_grad_typed wrote it): the same exit when *grad_out == 1.0f, otherwise
+ * grad[i] = round_to_nearest_even(float(grad[i]) * *grad_out). */
+int ctc_amd_scale_grad_typed(void *grad, int dtype, const float *grad_out, size_t n, void *stream);
 
 /* Best-path (Viterbi) alignment on the no-blank lattice: the max-semiring twin of
  * the alpha recursion (the reference evaluates with per-step argmax and
