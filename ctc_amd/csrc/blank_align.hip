@@ -1,0 +1,477 @@
+// Best-path (Viterbi) forced alignment on the blank-CTC lattice, gfx950.
+//
+// The max-semiring twin of the blank loss recursion (blank.hip): extended labels l'_s, s = 0..2L (even s = blank,
+// odd s = targets[(s-1)/2]), used as given (no normalisation):
+//   v_0(0) = lp[0,blank], v_0(1) = lp[0,l'_1], every other state -inf;
+//   v_t(s) = best(v_{t-1}(s), v_{t-1}(s-1), [v_{t-1}(s-2) if l'_s != blank and l'_s != l'_{s-2}]) + lp[t,l'_s],
+// candidates taken in the order stay, advance, skip, a later one replacing the current one only when strictly
+// greater; one fp32 add per step in natural log, -inf kept as -inf.  The read-out is state 2L when
+// v(2L) > v(2L-1) (strictly), else 2L-1 (state 0 when L = 0); the path is the walk back over the back-pointers.
+// Every step is one select chain and one add, so a float32 restatement run in the same order is bit-identical.
+//
+// Two launches:
+//   blank_align_gather_kernel   (bandwidth, every CU)  em[b,t,:] = lp[t,b,{l_0 .. l_{32K-1}, blank}] (labels j >= L
+//                               -> -inf): the 4 KB rows of log_probs are read once, all CUs at once, into a
+//                               compact [B][T][RW] table in the workspace (RW = 32K + 4 floats).
+//   blank_align_kernel<K>       (latency, one 512-thread workgroup per sample)  wave 0 runs the max-plus scan,
+//                               K states per lane, the two lower neighbours of a lane's first states through ONE DPP
+//                               wave shift; waves 1..7 copy the compact rows into an LDS ring ahead of it.  Back-pointers
+//                               are 2 bits per state and step, packed per lane into one 32-bit word per 16/K steps
+//                               (16 K bytes per step): in LDS while they fit, in the workspace beyond.  Wave 0 then
+//                               walks them back with one readlane per step and writes the path 64 steps per store.
+#include "common.hpp"
+#include "launch.hpp"
+
+namespace ctc {
+
+constexpr int kAlignThreads = 512;
+constexpr int kAlignWaves = kAlignThreads / kWave;
+constexpr int kAlignLoaders = kAlignWaves - 1;   // loader waves (1..7)
+constexpr int kAlignHead = 64;                   // ints of LDS flags in front of the ring
+constexpr int kAlignSpinLimit = 1 << 23;         // polls of an LDS flag (~0.1 us apart: ~1 s) before a wave gives up
+constexpr int kAlignWalkWords = 16;              // back-pointer words per lane fetched ahead of the walk back
+constexpr int kAlignGatherRows = 8;              // rows per wave of the gather launch
+constexpr int kAlignGatherThreads = 256;
+// LDS flag slots (ints): [0, 7) rows written per loader, 8 rows taken by the scan, 9 abort
+constexpr int kSlotTaken = 8, kSlotAbort = 9;
+
+struct AlignParams {
+    const float *lp;
+    int64_t st, sb;
+    const void *tgt;
+    int tgt64;
+    const int64_t *in_len, *tgt_len;
+    int T, B, C, S, blank;
+    int32_t *path;
+    float *score;
+    unsigned *counter;               // the workspace header (status word)
+    float *em;                       // [B][T][RW] emission rows
+    unsigned *spill;                 // [B][NWS][64] back-pointer words that do not fit in LDS
+    int RW, R, WL, NWS;              // row pitch (floats), ring rows (power of two), LDS word rows, spilled word rows
+};
+
+__host__ __device__ constexpr int align_row_pitch(int K) { return 32 * K + 4; }
+__host__ __device__ constexpr int align_steps_per_word(int K) { return 16 / K; }
+
+__device__ __forceinline__ bool align_sample(const AlignParams &p, int b, int &Tb, int &L)
+{
+    const int64_t Tb64 = p.in_len[b], L64 = p.tgt_len[b];
+    const bool ok = L64 >= 0 && L64 <= p.S && Tb64 >= 1 && Tb64 <= p.T;
+    Tb = ok ? (int)Tb64 : 0;
+    L = ok ? (int)L64 : 0;
+    return ok;
+}
+
+__device__ __forceinline__ int align_label(const AlignParams &p, int b, int j)
+{
+    const int c = load_label(p.tgt, p.tgt64, (int64_t)b * p.S + j);
+    return c < 0 ? 0 : (c >= p.C ? p.C - 1 : c);             // memory safety for bad labels
+}
+
+// ---- launch 1: the compact emission rows ---------------------------------------------------------
+// grid (ceil(T / (4 * kAlignGatherRows)), B); every wave takes kAlignGatherRows rows, all loads in flight at once
+template <int K>
+__global__ __launch_bounds__(kAlignGatherThreads) void blank_align_gather_kernel(AlignParams p)
+{
+    constexpr int RW = align_row_pitch(K), M = (RW + kWave - 1) / kWave;
+    const int b = blockIdx.y, lane = lane_id();
+    int Tb, L;
+    if (!align_sample(p, b, Tb, L)) return;
+    const int t0 = (blockIdx.x * (kAlignGatherThreads / kWave) + wave_id()) * kAlignGatherRows;
+    if (t0 >= Tb) return;
+    int col[M];
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+        const int j = lane + kWave * m;
+        col[m] = j < L ? align_label(p, b, j) : (j == 32 * K ? p.blank : -1);
+    }
+    const float *__restrict__ lp = p.lp + (int64_t)b * p.sb;
+    float v[kAlignGatherRows][M];
+#pragma unroll
+    for (int r = 0; r < kAlignGatherRows; ++r) {
+        const int t = min(t0 + r, Tb - 1);
+#pragma unroll
+        for (int m = 0; m < M; ++m) v[r][m] = lp[(int64_t)t * p.st + (col[m] >= 0 ? col[m] : p.blank)];
+    }
+    float *__restrict__ out = p.em + ((int64_t)b * p.T + t0) * RW;
+#pragma unroll
+    for (int r = 0; r < kAlignGatherRows; ++r) {
+        if (t0 + r >= Tb) break;
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            const int j = lane + kWave * m;
+            if (j < RW) out[r * RW + j] = col[m] >= 0 ? v[r][m] : -__builtin_inff();
+        }
+    }
+}
+
+// ---- launch 2: scan + walk back ------------------------------------------------------------------
+__device__ __forceinline__ int align_load(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+__device__ __forceinline__ void align_store(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+
+// loader wave i: rows t = i, i + 7, i + 14, ... of the sample, kAlignLoadRows in flight, each into ring slot t % R once
+// the scan has taken row t - R.  false: a wait ran out (or the scan gave up)
+template <int K>
+__device__ __forceinline__ bool align_loader(const AlignParams &p, int *flags, float *ring, int b, int Tb, int i)
+{
+    constexpr int RW = align_row_pitch(K), M = (RW + kWave - 1) / kWave;
+    // rows a loader wave keeps in flight: the seven loaders hold ~100 rows against the latency of the table (4 rows each
+    // measured the same at config 5, 347 against 346 us: the scan does not wait for its loaders there)
+    constexpr int kAlignLoadRows = K == 8 ? 8 : 16;
+    const int lane = lane_id();
+    const float *src = p.em + (int64_t)b * p.T * RW;
+    int taken = 0;
+    for (int q0 = 0; i + q0 * kAlignLoaders < Tb; q0 += kAlignLoadRows) {
+        float v[kAlignLoadRows][M];
+#pragma unroll
+        for (int d = 0; d < kAlignLoadRows; ++d) {
+            const int t = min(i + (q0 + d) * kAlignLoaders, Tb - 1);
+#pragma unroll
+            for (int m = 0; m < M; ++m) v[d][m] = src[(int64_t)t * RW + min(lane + kWave * m, RW - 1)];
+        }
+#pragma unroll
+        for (int d = 0; d < kAlignLoadRows; ++d) {
+            const int t = i + (q0 + d) * kAlignLoaders;
+            if (t >= Tb) break;
+            if (t - p.R >= taken) {                                  // the slot still holds row t - R: wait for the scan
+                bool ok = false;
+                for (int it = 0; it < kAlignSpinLimit; ++it) {
+                    taken = align_load(flags + kSlotTaken);
+                    if (t - p.R < taken) { ok = true; break; }
+                    if (align_load(flags + kSlotAbort)) break;
+                    __builtin_amdgcn_s_sleep(1);
+                }
+                if (!ok) return false;
+            }
+            float *dst = ring + (t & (p.R - 1)) * RW;
+#pragma unroll
+            for (int m = 0; m < M; ++m)
+                if (lane + kWave * m < RW) dst[lane + kWave * m] = v[d][m];
+            lds_order();                                             // (a wave's LDS operations complete in order)
+            align_store(flags + i, q0 + d + 1);
+        }
+    }
+    return true;
+}
+
+// the emissions of one step in the scan's registers: el[j] = label (lane K/2 + j), eb = blank
+template <int K>
+struct AlignRow {
+    float el[K / 2];
+    float eb;
+};
+
+template <int K>
+__device__ __forceinline__ void align_read_row(const float *ring, int R, int t, AlignRow<K> &r)
+{
+    constexpr int RW = align_row_pitch(K);
+    const float *row = ring + (t & (R - 1)) * RW;
+    const int lane = lane_id();
+    if constexpr (K == 2) {
+        r.el[0] = row[lane];
+    } else if constexpr (K == 4) {
+        const float2 x = reinterpret_cast<const float2 *>(row)[lane];
+        r.el[0] = x.x; r.el[1] = x.y;
+    } else {
+#pragma unroll
+        for (int q = 0; q < K / 2; q += 4) {
+            const float4 x = reinterpret_cast<const float4 *>(row)[lane * (K / 8) + q / 4];
+            r.el[q] = x.x; r.el[q + 1] = x.y; r.el[q + 2] = x.z; r.el[q + 3] = x.w;
+        }
+    }
+    r.eb = row[32 * K];
+}
+
+// value of state s (wave-uniform) from the lane that holds it
+template <int K>
+__device__ __forceinline__ float align_state_value(const float (&a)[K], int s)
+{
+    // every register read out first, the choice among them made on wave-uniform values (a select among the a[k]
+    // by a runtime k becomes an indexed access to a stack copy of a[])
+    const int kk = s & (K - 1);
+    int x = __builtin_amdgcn_readlane(__builtin_bit_cast(int, a[0]), s / K);
+#pragma unroll
+    for (int k = 1; k < K; ++k) {
+        const int y = __builtin_amdgcn_readlane(__builtin_bit_cast(int, a[k]), s / K);
+        x = kk == k ? y : x;
+    }
+    return __builtin_bit_cast(float, x);
+}
+
+template <int K>
+struct AlignScan {
+    static constexpr int P = align_steps_per_word(K);            // steps per back-pointer word
+    static constexpr int G = K == 8 ? 8 : 16;                    // steps per group (a multiple of P)
+    int R, WL;                                                   // (copies: a reference to the kernel argument goes to scratch)
+    int *flags;
+    const float *ring;
+    unsigned *bp;                                                // [WL][64] in LDS
+    unsigned *spill;                                             // [NWS][64] of this sample
+    int Tb, ready;
+    float a[K];
+    bool skip[K];
+
+    __device__ __forceinline__ AlignScan(const AlignParams &p, int *f, const float *r, unsigned *bp_, unsigned *sp, int Tb_)
+        : R(p.R), WL(p.WL), flags(f), ring(r), bp(bp_), spill(sp), Tb(Tb_), ready(0) {}
+
+    // rows < upto (<= Tb) are in the ring; false when the wait ran out
+    __device__ __forceinline__ bool wait_rows(int upto)
+    {
+        for (int it = 0; ready < upto; ++it) {
+            if (it >= kAlignSpinLimit) return false;
+            if (it) __builtin_amdgcn_s_sleep(1);
+            int x = 0x7fffffff;
+#pragma unroll
+            for (int i = 0; i < kAlignLoaders; ++i) x = min(x, align_load(flags + i) * kAlignLoaders + i);
+            ready = x;
+        }
+        lds_order();
+        return true;
+    }
+
+    __device__ __forceinline__ void read_group(AlignRow<K> (&buf)[G], int t0)
+    {
+#pragma unroll
+        for (int j = 0; j < G; ++j) align_read_row<K>(ring, R, t0 + j, buf[j]);
+        lds_order();
+        align_store(flags + kSlotTaken, t0 + G);                 // (in order behind the reads)
+    }
+
+    __device__ __forceinline__ void store_word(int w, unsigned word)
+    {
+        if (w < WL) bp[w * kWave + lane_id()] = word;
+        else spill[(w - WL) * kWave + lane_id()] = word;
+    }
+
+    // one step: the select chain stay -> advance -> skip, one add; 2-bit codes into `word`
+    __device__ __forceinline__ void step(const AlignRow<K> &e, int sub, unsigned &word)
+    {
+        const float nb = wave_shr1(a[K - 1], -__builtin_inff());
+        float n[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const float adv = k == 0 ? nb : a[k - 1];
+            float best = a[k];
+            unsigned c = 0;
+            if (adv > best) { best = adv; c = 1; }
+            if (k & 1) {
+                const float sk = k == 1 ? nb : a[k - 2];
+                if (skip[k] && sk > best) { best = sk; c = 2; }
+            }
+            n[k] = best + ((k & 1) ? e.el[k / 2] : e.eb);
+            word |= c << (2 * K * sub + 2 * k);
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) a[k] = n[k];
+    }
+
+    template <bool GUARD>
+    __device__ __forceinline__ void group(const AlignRow<K> (&buf)[G], int t0)
+    {
+        unsigned word = 0;
+#pragma unroll
+        for (int j = 0; j < G; ++j) {
+            const int t = t0 + j;
+            if (GUARD && t >= Tb) break;
+            if (GUARD && t == 0) {
+                const int s0 = lane_id() * K;
+#pragma unroll
+                for (int k = 0; k < K; ++k)
+                    a[k] = s0 + k == 0 ? buf[j].eb : (s0 + k == 1 ? buf[j].el[0] : -__builtin_inff());
+            } else {
+                step(buf[j], j % P, word);
+            }
+            if (j % P == P - 1 || (GUARD && t == Tb - 1)) {
+                store_word(t / P, word);
+                word = 0;
+            }
+        }
+    }
+
+    __device__ __forceinline__ void run_group(const AlignRow<K> (&buf)[G], int t0)
+    {
+        if (t0 > 0 && t0 + G <= Tb) group<false>(buf, t0);
+        else group<true>(buf, t0);
+    }
+
+    // false: a wait ran out
+    __device__ __forceinline__ bool scan()
+    {
+        AlignRow<K> A[G], B[G];
+        if (!wait_rows(min(G, Tb))) return false;
+        read_group(A, 0);
+        for (int t0 = 0;;) {
+            bool more = t0 + G < Tb;
+            if (more) {
+                if (!wait_rows(min(t0 + 2 * G, Tb))) return false;
+                read_group(B, t0 + G);
+            }
+            run_group(A, t0);
+            t0 += G;
+            if (!more) break;
+            more = t0 + G < Tb;
+            if (more) {
+                if (!wait_rows(min(t0 + 2 * G, Tb))) return false;
+                read_group(A, t0 + G);
+            }
+            run_group(B, t0);
+            t0 += G;
+            if (!more) break;
+        }
+        return true;
+    }
+
+    __device__ __forceinline__ void load_words(unsigned (&w)[kAlignWalkWords], int wtop)
+    {
+#pragma unroll
+        for (int i = 0; i < kAlignWalkWords; ++i) {
+            const int r = wtop - i;
+            w[i] = r < 0 ? 0u : (r < WL ? bp[r * kWave + lane_id()] : spill[(r - WL) * kWave + lane_id()]);
+        }
+    }
+
+    // from state `s` at step Tb-1 down to step 0; path[t] = s_t, stored 64 steps at a time
+    __device__ __forceinline__ void walk(int s, int32_t *out)
+    {
+        const int lane = lane_id();
+        unsigned cur[kAlignWalkWords], nxt[kAlignWalkWords];
+        int outv = -1;
+        const int wtop = (Tb - 1) / P;
+        load_words(nxt, wtop);
+        for (int w0 = wtop; w0 >= 0; w0 -= kAlignWalkWords) {
+#pragma unroll
+            for (int i = 0; i < kAlignWalkWords; ++i) cur[i] = nxt[i];
+            if (w0 >= kAlignWalkWords) load_words(nxt, w0 - kAlignWalkWords);
+#pragma unroll
+            for (int i = 0; i < kAlignWalkWords; ++i) {
+                const int word = (int)cur[i];
+#pragma unroll
+                for (int sub = P - 1; sub >= 0; --sub) {
+                    const int t = (w0 - i) * P + sub;                 // (t < 0 only below the last block: nothing to do)
+                    if (t >= 0 && t < Tb) {
+                        outv = lane == (t & (kWave - 1)) ? s : outv;
+                        if ((t & (kWave - 1)) == 0 && t + lane < Tb) out[t + lane] = outv;
+                        const unsigned x = (unsigned)__builtin_amdgcn_readlane(word, s / K);
+                        if (t >= 1) s -= (int)((x >> (2 * K * sub + 2 * (s & (K - 1)))) & 3u);
+                    }
+                }
+            }
+        }
+    }
+};
+
+template <int K>
+__global__ __launch_bounds__(kAlignThreads) void blank_align_kernel(AlignParams p)
+{
+    constexpr int RW = align_row_pitch(K);
+    extern __shared__ __attribute__((aligned(16))) int align_smem[];
+    int *flags = align_smem;                                      // [kAlignHead]
+    float *ring = reinterpret_cast<float *>(align_smem + kAlignHead);   // [R][RW]
+    unsigned *bp = reinterpret_cast<unsigned *>(ring + p.R * RW);       // [WL][64]
+    const int b = blockIdx.x, tid = threadIdx.x, w = wave_id(), lane = lane_id();
+    int32_t *out = p.path + (int64_t)b * p.T;
+    int Tb, L;
+    const bool ok = align_sample(p, b, Tb, L);
+    if (!ok) {
+        for (int t = tid; t < p.T; t += kAlignThreads) out[t] = -1;
+        if (tid == 0) p.score[b] = -__builtin_inff();
+        return;
+    }
+    if (tid < kAlignHead) flags[tid] = 0;
+    __syncthreads();
+
+    if (w > 0) {
+        for (int t = Tb + tid - kWave; t < p.T; t += kAlignThreads - kWave) out[t] = -1;
+        if (!align_loader<K>(p, flags, ring, b, Tb, w - 1)) {
+            align_store(flags + kSlotAbort, 1);
+            raise_status(p.counter, kStatusAlignStarved);
+        }
+        return;
+    }
+
+    __builtin_amdgcn_s_setprio(3);
+    AlignScan<K> sc(p, flags, ring, bp, p.spill + (int64_t)b * p.NWS * kWave, Tb);
+    {
+        const int s0 = lane * K;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int s = s0 + k;
+            // a label state s >= 3 may come from s - 2 when its class is no blank and differs from that of s - 2
+            bool sk = false;
+            if ((k & 1) && s >= 3 && s <= 2 * L - 1) {
+                const int c = align_label(p, b, (s - 1) >> 1), c2 = align_label(p, b, (s - 3) >> 1);
+                sk = c != p.blank && c != c2;
+            }
+            sc.skip[k] = sk;
+        }
+    }
+    const bool done = sc.scan();
+    if (!done) {                                                  // a wait ran out: NaN score, no path
+        align_store(flags + kSlotAbort, 1);
+        raise_status(p.counter, kStatusAlignStarved);
+        for (int t = lane; t < Tb; t += kWave) out[t] = -1;
+        if (lane == 0) p.score[b] = __builtin_nanf("");
+        return;
+    }
+    int sfin = 0;
+    if (L > 0) sfin = align_state_value<K>(sc.a, 2 * L) > align_state_value<K>(sc.a, 2 * L - 1) ? 2 * L : 2 * L - 1;
+    const float score = align_state_value<K>(sc.a, sfin);
+    if (lane == 0) p.score[b] = score;
+    if (!(score > -__builtin_inff())) {                           // no alignment
+        for (int t = lane; t < Tb; t += kWave) out[t] = -1;
+        return;
+    }
+    __builtin_amdgcn_s_waitcnt(0);                                // the spilled words have landed before they are read back
+    sc.walk(sfin, out);
+}
+
+template <int K>
+static int run_blank_align(AlignParams &p, hipStream_t s)
+{
+    constexpr int RW = align_row_pitch(K), P = align_steps_per_word(K);
+    p.RW = RW;
+    p.R = K == 8 ? 32 : 64;
+    const size_t head = kAlignHead * sizeof(int), ring = (size_t)p.R * RW * sizeof(float);
+    const int nw = (p.T + P - 1) / P;
+    const int cap = (int)((kMaxLds - head - ring) / (kWave * sizeof(unsigned)));
+    p.WL = nw < cap ? nw : cap;
+    p.NWS = nw - p.WL;
+    char *ws = reinterpret_cast<char *>(p.counter) + 256;
+    p.em = reinterpret_cast<float *>(ws);
+    p.spill = reinterpret_cast<unsigned *>(ws + (size_t)p.B * p.T * RW * sizeof(float));
+    const size_t need = 256 + (size_t)p.B * p.T * RW * sizeof(float) + (size_t)p.B * p.NWS * kWave * sizeof(unsigned);
+    if (need > ctc_amd_workspace_bytes(CTC_AMD_BLANK, p.T, p.B, p.C, p.S)) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
+    const int rows_per_block = (kAlignGatherThreads / kWave) * kAlignGatherRows;
+    const dim3 ggrid((p.T + rows_per_block - 1) / rows_per_block, p.B);
+    int rc = launch<blank_align_gather_kernel<K>>(ggrid, dim3(kAlignGatherThreads), 0, s, p);
+    if (rc) return rc;
+    const size_t lds = head + ring + (size_t)p.WL * kWave * sizeof(unsigned);
+    return launch<blank_align_kernel<K>>(dim3(p.B), dim3(kAlignThreads), lds, s, p);
+}
+
+}  // namespace ctc
+
+using namespace ctc;
+
+extern "C" int ctc_amd_blank_best_path(const float *log_probs, int64_t stride_t, int64_t stride_b,
+                                       const void *targets, int targets_i64,
+                                       const int64_t *in_len, const int64_t *tgt_len,
+                                       int T, int B, int C, int S, int blank,
+                                       int32_t *path, float *score, void *workspace, void *stream)
+{
+    if (!log_probs || !targets || !in_len || !tgt_len || !path || !score || !workspace) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (T < 1 || B < 1 || C < 1 || S < 1 || blank < 0 || blank >= C) return CTC_AMD_ERR_BAD_ARGUMENT;
+    const int ns = 2 * S + 1;
+    if (ns > kWave * 8) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;                 // S <= 255
+    AlignParams p;
+    p.lp = log_probs; p.st = stride_t; p.sb = stride_b;
+    p.tgt = targets; p.tgt64 = targets_i64;
+    p.in_len = in_len; p.tgt_len = tgt_len;
+    p.T = T; p.B = B; p.C = C; p.S = S; p.blank = blank;
+    p.path = path; p.score = score;
+    p.counter = static_cast<unsigned *>(workspace);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (ns <= kWave * 2) return run_blank_align<2>(p, s);
+    if (ns <= kWave * 4) return run_blank_align<4>(p, s);
+    return run_blank_align<8>(p, s);
+}

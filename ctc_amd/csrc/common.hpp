@@ -90,6 +90,7 @@ __device__ __forceinline__ void grad_store(V *p, V v)
 // ctc_amd_workspace_status() reads / clears it from the host.  Never observed outside fault-injection
 // builds: the hand-offs cannot break unless a workgroup is starved for ~1 s.
 constexpr unsigned kStatusNoblankStarved = 1u, kStatusBinaryStarved = 2u, kStatusBlankStarved = 4u;
+constexpr unsigned kStatusAlignStarved = 8u;          // blank-CTC best path (blank_align.hip)
 __device__ __forceinline__ void raise_status(unsigned *counter, unsigned bit)
 {
 #ifdef CTC_X_NOSTATUS

@@ -79,7 +79,7 @@ def release_workspaces(device=None):
     return freed
 
 
-STATUS_BITS = {1: "no-blank launch", 2: "binary launch", 4: "blank-CTC launch"}
+STATUS_BITS = {1: "no-blank launch", 2: "binary launch", 4: "blank-CTC launch", 8: "blank-CTC best path"}
 
 
 def workspace_status(device=None, clear=True):
@@ -537,6 +537,72 @@ def binary_best_path(logits, targets, input_lengths, target_lengths):
                                                   _stream_handle(dev))
     _lib.check(rc, "ctc_amd_binary_best_path")
     return path, score
+
+
+def blank_best_path(log_probs, targets, input_lengths, target_lengths, blank=0):
+    """Best (Viterbi) alignment on the blank-CTC lattice -> (path[B,T] int32, score[B] fp32).
+
+    Same inputs as ``blank_ctc_loss``: ``log_probs`` [T,B,C] normalised log-probabilities (used as given),
+    ``targets`` [B,S] int32/int64.  ``path[b,t]`` is the extended-label STATE s_t (even = blank, odd s = label
+    (s-1)//2 of targets[b]) for ``t < T_b``, -1 beyond ``T_b`` and for samples with no alignment; ``score[b]`` the
+    log-probability of that alignment (-inf when none exists).  include/ctc_amd.h: ctc_amd_blank_best_path.
+    """
+    _require_hip(log_probs, "log_probs")
+    if log_probs.dim() != 3 or log_probs.dtype != torch.float32:
+        raise ValueError("ctc_amd: log_probs must be float32 [T,B,C]")
+    T, B, C = log_probs.shape
+    if T < 1 or B < 1 or C < 1:
+        raise ValueError("ctc_amd: empty log_probs %s" % (tuple(log_probs.shape),))
+    dev = log_probs.device
+    xs = log_probs.detach()
+    if xs.stride(2) != 1:
+        xs = xs.contiguous()
+    if not isinstance(targets, torch.Tensor) or targets.dim() != 2 or targets.dtype.is_floating_point \
+            or targets.shape[0] != B:
+        raise ValueError("ctc_amd: targets must be [B,S] integer")
+    if targets.dtype not in (torch.int32, torch.int64):
+        targets = targets.long()
+    tg = targets if (targets.device == dev and targets.is_contiguous()) else \
+        targets.to(device=dev, non_blocking=True).contiguous()
+    S = tg.shape[1]
+    if S < 1:
+        raise ValueError("ctc_amd: targets need at least one label column")
+    il = _lengths(input_lengths, B, "input_lengths", dev, T)
+    tl = _lengths(target_lengths, B, "target_lengths", dev, S, lo=0)
+    path = torch.empty((B, T), dtype=torch.int32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        stream = _stream_handle(dev)
+        ws = _workspace(_lib.BLANK, T, B, C, S, dev, stream)
+        rc = _lib.load().ctc_amd_blank_best_path(
+            xs.data_ptr(), xs.stride(0), xs.stride(1), tg.data_ptr(), int(tg.dtype is torch.int64),
+            il.data_ptr(), tl.data_ptr(), T, B, C, S, int(blank), path.data_ptr(), score.data_ptr(), ws.data_ptr(),
+            stream)
+    _lib.check(rc, "ctc_amd_blank_best_path")
+    if _VALIDATE:
+        check_status(dev)
+    return path, score
+
+
+def blank_forced_align(log_probs, targets, input_lengths, target_lengths, blank=0):
+    """Forced alignment of known targets (the batched form of torchaudio-style ``forced_align``) ->
+    (tokens[B,T] int64, frame_scores[B,T] fp32).
+
+    ``tokens[b,t]`` is the class of the best path's state at frame t (``blank`` or the target label), -1 beyond
+    ``T_b`` / without an alignment; ``frame_scores[b,t] = log_probs[t,b,tokens[b,t]]`` (0 where tokens is -1), so
+    that their sum over t in order is ``blank_best_path``'s score.  Derived on the device from the path."""
+    path, _ = blank_best_path(log_probs, targets, input_lengths, target_lengths, blank)
+    dev = path.device
+    tg = targets.to(device=dev, dtype=torch.int64)
+    valid = path >= 0
+    st = path.long().clamp(min=0)
+    lab = torch.gather(tg, 1, ((st - 1) >> 1).clamp(0, tg.shape[1] - 1))
+    tokens = torch.where((st & 1) == 1, lab, torch.full_like(lab, int(blank)))
+    tokens = torch.where(valid, tokens, torch.full_like(tokens, -1))
+    lp = log_probs.detach().transpose(0, 1)                                   # [B,T,C] view
+    fs = torch.gather(lp, 2, tokens.clamp(min=0).unsqueeze(2)).squeeze(2)
+    frame_scores = torch.where(valid, fs, torch.zeros_like(fs))
+    return tokens, frame_scores
 
 
 def noblank_posteriors(logits, targets, input_lengths, target_lengths):

@@ -164,7 +164,8 @@ int ctc_amd_blank_set_schedule(int mode);
  * yields a plausible number: the outputs that could not be produced are filled with NaN (nll of the
  * sample, the loss, the sample's gradient rows) and a bit is ORed into the workspace's STATUS word, which
  * stays set until cleared here.  Reads the word (synchronising `stream`); clear != 0 resets it.
- * Bits: 1 no-blank, 2 binary, 4 blank-CTC launch starved.  Never observed outside fault-injection builds;
+ * Bits: 1 no-blank, 2 binary, 4 blank-CTC launch starved, 8 blank-CTC best path starved (that sample's score NaN,
+ * its path -1).  Never observed outside fault-injection builds;
  * the persistent blank-CTC launch is the one place where another process's kernels could cause it. */
 int ctc_amd_workspace_status(void *workspace, int clear, void *stream, unsigned *status_host);
 
@@ -216,6 +217,24 @@ int ctc_amd_binary_best_path(const float *x, int64_t stride_t, int64_t stride_b,
                              const int64_t *in_len, const int64_t *tgt_len,
                              int T, int B, int C, int S,
                              int32_t *path, float *score, void *workspace, void *stream);
+
+/* Best-path (Viterbi) forced alignment on the blank-CTC lattice (torch.nn.CTCLoss semantics, as
+ * ctc_amd_blank_loss_grad): which frame belongs to which label of a KNOWN target sequence, and the score of that
+ * alignment.  Inputs: the same layout and contract as ctc_amd_blank_loss_grad (log_probs used as given, no
+ * normalisation; 0 <= L_b <= S, 1 <= T_b <= T).  Extended labels l'_s, s = 0..2L (even s = blank, odd s = label
+ * (s-1)/2):  v_0(0) = lp[0,blank], v_0(1) = lp[0,l'_1], others -inf;  v_t(s) = best(v_{t-1}(s), v_{t-1}(s-1),
+ * [v_{t-1}(s-2) when l'_s != blank and l'_s != l'_{s-2}]) + lp[t,l'_s], candidates in the order stay, advance, skip,
+ * a later one taken only when strictly greater; one fp32 add per step (natural log, -inf kept).
+ *   path  [B,T] int32 out: state s_t of the best alignment for t < T_b (the final state is 2L when
+ *         v(2L) > v(2L-1), else 2L-1; 0 when L = 0), -1 for t >= T_b and for samples with no alignment
+ *   score [B]   out: v of the final state (-inf: no alignment -- too short for L plus its adjacent repeats)
+ * workspace: at least ctc_amd_workspace_bytes(CTC_AMD_BLANK, T, B, C, S) bytes; the 256-byte header is left alone
+ * except for status bit 8.  S <= 255, any T (back-pointers beyond LDS go to the workspace). */
+int ctc_amd_blank_best_path(const float *log_probs, int64_t stride_t, int64_t stride_b,
+                            const void *targets, int targets_i64,
+                            const int64_t *in_len, const int64_t *tgt_len,
+                            int T, int B, int C, int S, int blank,
+                            int32_t *path, float *score, void *workspace, void *stream);
 
 /* Target construction: the dedup step of the reference's dataset preparation,
  * datasets/charades_ctc_next_pred.py:646-651,663-678 (same code at :503-505,523-531) -- out[b] = the rows of
