@@ -449,6 +449,307 @@ static int run_blank_align(AlignParams &p, hipStream_t s)
     return launch<blank_align_kernel<K>>(dim3(p.B), dim3(kAlignThreads), lds, s, p);
 }
 
+// ==== per-frame state posteriors (ctc_amd_blank_posteriors) =======================================
+// gamma_t(s) = exp(alpha_t(s) + beta'_t(s) + nll): the sum-semiring twin of the scan above, in three launches --
+//   blank_align_gather_kernel<K>  (as above) the compact emission table em [B][T][RW];
+//   blank_post_chain_kernel<K>    one 128-thread workgroup per sample: wave 0 runs alpha forward, wave 1 beta' backward
+//                                 (beta' leaves out the emission of its own step), K states per lane, neighbours
+//                                 through DPP, emission rows loaded kPostAhead rows ahead into registers; each wave
+//                                 stores its rows [B][T][NSP] to the workspace, wave 0 writes nll;
+//   blank_post_gamma_kernel<K>    (bandwidth, every CU) gamma rows = softmax_s(alpha' + beta') in coalesced stores,
+//                                 zeros outside the support.
+// The chains are fp32 in log2 units but never hold absolute values: every kPostRescale steps a wave subtracts its
+// row maximum (wave-uniform) from its states, so the values near the maximum -- the ones gamma is made of -- stay
+// small and keep their fp32 resolution over any T (the loss's chains reach -2e4 at T = 2000, one ulp 2e-3).  Each
+// emission row enters relative to its own maximum (c_t, over the blank and the labels, in natural log, before the
+// conversion to log2): a per-frame constant that every path pays once, so it cancels from gamma too, and the
+// roundings of the conversion and of the add scale with lp - c_t instead of lp (peaked inputs, lp ~ -250 at T = 150:
+// max |dgamma| 3.6e-5 without it).  Each row is then normalised on its own, so the offsets cancel from gamma; only
+// alpha's (the maxima and the c_t) are summed, in double, for nll.
+// Unreachable states carry the finite stand-in kPostNeg (-inf inputs included) and come out of the row softmax as 0.
+constexpr int kPostAhead = 16;                  // emission rows in flight ahead of a chain
+constexpr int kPostRescale = 8;                 // chain steps between two subtractions of the row maximum
+constexpr int kPostRows = 4;                    // gamma rows per wave of the combine launch (and emission rows per
+                                                // wave_max4 of a chain)
+constexpr int kPostThreads = 256;
+constexpr float kPostNeg = -1.0e30f;            // unreachable (its sums stay finite: no inf - inf in a step)
+constexpr float kPostLive = -1.0e29f;           // above: a reachable value
+
+struct PostParams {
+    AlignParams a;                              // inputs, shape, em (the gather's table)
+    float *al, *be;                             // [B][T][NSP] rescaled alpha / beta' rows, log2 units
+    float *nll, *gamma;
+    int NSP, NS;                                // lattice row pitch 64 K, gamma row pitch 2S+1
+};
+
+__device__ __forceinline__ float post_lse2(float a, float b)
+{
+    return vmax(a, b) + __builtin_amdgcn_logf(1.0f + __builtin_amdgcn_exp2f(-fabsf(a - b)));
+}
+
+// one emission row in registers: el[j] = label lane*K/2 + j, eb = blank (loaded per lane from one address: a vector
+// load, so that every fetch of the ring is counted by the same counter)
+template <int K, bool FWD>
+__device__ __forceinline__ void post_fetch(const float *em, int Tb, int i, int eoff, AlignRow<K> &r)
+{
+    constexpr int RW = align_row_pitch(K);
+    const int ii = i < Tb ? i : Tb - 1;
+    const float *row = em + (int64_t)(FWD ? ii : Tb - 1 - ii) * RW;
+    const int lane = lane_id();
+    if constexpr (K == 2) {
+        r.el[0] = row[lane];
+    } else if constexpr (K == 4) {
+        const float2 x = reinterpret_cast<const float2 *>(row)[lane];
+        r.el[0] = x.x; r.el[1] = x.y;
+    } else {
+        const float4 x = reinterpret_cast<const float4 *>(row)[lane];
+        r.el[0] = x.x; r.el[1] = x.y; r.el[2] = x.z; r.el[3] = x.w;
+    }
+    r.eb = row[32 * K + eoff];
+}
+
+template <int K, bool FWD>
+struct PostChain {
+    float a[K];                                  // state values (log2, relative to the offsets subtracted so far)
+    bool skip[K];
+    double off;                                  // alpha: the state maxima subtracted so far (log2)
+    double coff;                                 // alpha: the emission maxima c_t subtracted so far (natural log)
+
+    // pre[] = log-sum-exp over the predecessors (alpha) / successors (beta) of each state; a label state's third term is
+    // folded into the neighbouring blank's two-term sum (as in blank.hip), so every state is one two-term LSE
+    __device__ __forceinline__ void pre(float (&q)[K]) const
+    {
+        if (FWD) {
+            const float nb1 = wave_shr1(a[K - 1], kPostNeg);
+#pragma unroll
+            for (int k = 0; k < K; k += 2) q[k] = post_lse2(a[k], k ? a[k - 1] : nb1);
+#pragma unroll
+            for (int k = 1; k < K; k += 2) q[k] = post_lse2(a[k], skip[k] ? q[k - 1] : a[k - 1]);
+        } else {
+            const float n1 = wave_shl1(a[0], kPostNeg);
+#pragma unroll
+            for (int k = 0; k < K; k += 2) q[k] = post_lse2(a[k], a[k + 1]);
+            const float nb = wave_shl1(q[0], kPostNeg);
+#pragma unroll
+            for (int k = 1; k < K; k += 2)
+                q[k] = post_lse2(a[k], skip[k] ? (k + 1 < K ? q[k + 1] : nb) : (k + 1 < K ? a[k + 1] : n1));
+        }
+    }
+
+    // a = pre + (emission - c); the row stored is alpha_t (FWD) or beta'_t = pre (!FWD)
+    __device__ __forceinline__ void add_store(const float (&q)[K], const AlignRow<K> &e, float c, float *dst, bool st)
+    {
+        const float eb = vmax((e.eb - c) * kLog2e, kPostNeg);
+#pragma unroll
+        for (int k = 0; k < K; ++k) a[k] = q[k] + ((k & 1) ? vmax((e.el[k / 2] - c) * kLog2e, kPostNeg) : eb);
+        if (FWD) coff += (double)c;
+        if (!st) return;
+        const float *v = FWD ? a : q;
+        if constexpr (K == 2) {
+            *reinterpret_cast<float2 *>(dst) = make_float2(v[0], v[1]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < K; k += 4) *reinterpret_cast<float4 *>(dst + k) = make_float4(v[k], v[k + 1], v[k + 2], v[k + 3]);
+        }
+    }
+
+    // subtract the row maximum (when anything is reachable); clamp what is not at kPostNeg
+    __device__ __forceinline__ void rescale()
+    {
+        float mx = a[0];
+#pragma unroll
+        for (int k = 1; k < K; ++k) mx = vmax(mx, a[k]);
+        float m = wave_max(mx);
+        m = m > kPostLive ? m : 0.f;
+#pragma unroll
+        for (int k = 0; k < K; ++k) a[k] = vmax(a[k] - m, kPostNeg);
+        if (FWD) off += (double)m;
+    }
+
+    __device__ __forceinline__ void step(const AlignRow<K> &e, float c, float *dst, bool st)
+    {
+        float q[K];
+        pre(q);
+        add_store(q, e, c, dst, st);
+    }
+};
+
+// the emission maxima c_t of four rows (0 for a row without a finite emission: everything on it stays unreachable)
+template <int K>
+__device__ __forceinline__ void post_row_max4(const AlignRow<K> *r, float (&c)[kPostRows])
+{
+#pragma unroll
+    for (int i = 0; i < kPostRows; ++i) {
+        c[i] = r[i].eb;
+#pragma unroll
+        for (int j = 0; j < K / 2; ++j) c[i] = fmaxf(c[i], r[i].el[j]);
+    }
+    wave_max4(c[0], c[1], c[2], c[3]);
+#pragma unroll
+    for (int i = 0; i < kPostRows; ++i) c[i] = c[i] > -__builtin_inff() ? c[i] : 0.f;
+}
+
+template <int K, bool FWD>
+__device__ __forceinline__ void post_chain(const PostParams &p, int b, int Tb, int L)
+{
+    constexpr int RW = align_row_pitch(K), D = kPostAhead, G = kPostRescale;
+    static_assert(D % G == 0 && D % kPostRows == 0, "rescale / row-maximum points are compile-time positions in the unrolled body");
+    const int lane = lane_id(), s0 = lane * K, n = 2 * L + 1;
+    const int T = p.a.T;
+    const float *em = p.a.em + (int64_t)b * T * RW;
+    float *out = (FWD ? p.al : p.be) + (int64_t)b * T * p.NSP + s0;
+    const int64_t dir = FWD ? p.NSP : -(int64_t)p.NSP;
+    const bool st = s0 < n;                                       // lanes wholly beyond the lattice store nothing
+    const int eoff = opaque_v(0);
+    PostChain<K, FWD> c;
+    c.off = 0.0;
+    c.coff = 0.0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int s = s0 + k;
+        bool sk = false;
+        // alpha: s from s-2 when l'_s is no blank and differs from l'_{s-2}; beta: s from s+2 under the same rule for s+2
+        if ((k & 1) && (FWD ? (s >= 3 && s <= 2 * L - 1) : (s + 2 <= 2 * L - 1))) {
+            const int c1 = align_label(p.a, b, (s - 1) >> 1), c2 = align_label(p.a, b, FWD ? (s - 3) >> 1 : (s + 1) >> 1);
+            sk = FWD ? (c1 != p.a.blank && c1 != c2) : (c2 != p.a.blank && c2 != c1);
+        }
+        c.skip[k] = sk;
+    }
+    float *dst = out + (int64_t)(FWD ? 0 : Tb - 1) * p.NSP;
+    {
+        AlignRow<K> e0[kPostRows];
+        post_fetch<K, FWD>(em, Tb, 0, eoff, e0[0]);
+        e0[1] = e0[2] = e0[3] = e0[0];
+        float c0[kPostRows];
+        post_row_max4<K>(e0, c0);
+        float q[K];
+        const int sa = FWD ? 0 : 2 * L, sb = FWD ? 1 : 2 * L - 1;       // entry states
+#pragma unroll
+        for (int k = 0; k < K; ++k) q[k] = (s0 + k == sa || s0 + k == sb) ? 0.f : kPostNeg;
+        c.add_store(q, e0[0], c0[0], dst, st);
+        dst += dir;
+    }
+    AlignRow<K> ring[D];
+    float cm[kPostRows];
+#pragma unroll
+    for (int j = 0; j < D; ++j) post_fetch<K, FWD>(em, Tb, 1 + j, eoff, ring[j]);
+    int i = 1;
+    for (; i + D <= Tb; i += D) {
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            if (j % kPostRows == 0) post_row_max4<K>(ring + j, cm);
+            const AlignRow<K> e = ring[j];
+            post_fetch<K, FWD>(em, Tb, i + j + D, eoff, ring[j]);
+            c.step(e, cm[j % kPostRows], dst, st);
+            dst += dir;
+            if (j % G == G - 1) c.rescale();
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < D; ++j)
+        if (i + j < Tb) {
+            if (j % kPostRows == 0) post_row_max4<K>(ring + j, cm);
+            c.step(ring[j], cm[j % kPostRows], dst, st);
+            dst += dir;
+            if (j % G == G - 1) c.rescale();
+        }
+    if (FWD) {
+        const float x = align_state_value<K>(c.a, 2 * L);
+        const float y = L > 0 ? align_state_value<K>(c.a, 2 * L - 1) : kPostNeg;
+        const float v = post_lse2(x, y);
+        if (lane == 0)
+            p.nll[b] = v > kPostLive ? (float)(-((double)v + c.off) * (double)kLn2 - c.coff) : __builtin_inff();
+    }
+}
+
+template <int K>
+__global__ __launch_bounds__(2 * kWave) void blank_post_chain_kernel(PostParams p)
+{
+    const int b = blockIdx.x;
+    int Tb, L;
+    if (!align_sample(p.a, b, Tb, L)) {                          // lengths out of contract: NaN, gamma rows 0
+        if (threadIdx.x == 0) p.nll[b] = __builtin_nanf("");
+        return;
+    }
+    if (wave_id() == 0) post_chain<K, true>(p, b, Tb, L);
+    else post_chain<K, false>(p, b, Tb, L);
+}
+
+// grid (ceil(T / (4 * kPostRows)), B): wave w of block x takes rows t0 .. t0 + kPostRows - 1, state s = lane + 64 k
+template <int K>
+__global__ __launch_bounds__(kPostThreads) void blank_post_gamma_kernel(PostParams p)
+{
+    const int b = blockIdx.y, lane = lane_id(), T = p.a.T;
+    const int t0 = (blockIdx.x * (kPostThreads / kWave) + wave_id()) * kPostRows;
+    if (t0 >= T) return;
+    int Tb, L;
+    const bool ok = align_sample(p.a, b, Tb, L);
+    const bool feasible = ok && p.nll[b] < __builtin_inff();     // (+inf: no alignment; NaN: bad lengths)
+    const int n = 2 * L + 1;
+    const int64_t r0 = (int64_t)b * T + t0;
+    const float *al = p.al + r0 * p.NSP, *be = p.be + r0 * p.NSP;
+    float z[kPostRows][K], m[kPostRows];
+#pragma unroll
+    for (int r = 0; r < kPostRows; ++r) {
+        const bool live = feasible && t0 + r < Tb;
+        m[r] = -__builtin_inff();
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int s = lane + kWave * k;
+            z[r][k] = live && s < n ? al[r * p.NSP + s] + be[r * p.NSP + s] : -__builtin_inff();
+            m[r] = fmaxf(m[r], z[r][k]);
+        }
+    }
+    wave_max4(m[0], m[1], m[2], m[3]);
+    float sum[kPostRows];
+#pragma unroll
+    for (int r = 0; r < kPostRows; ++r) {
+        sum[r] = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            z[r][k] = z[r][k] > -__builtin_inff() ? __builtin_amdgcn_exp2f(z[r][k] - m[r]) : 0.f;
+            sum[r] += z[r][k];
+        }
+    }
+    wave_sum4(sum[0], sum[1], sum[2], sum[3]);
+    float *out = p.gamma + r0 * p.NS;
+#pragma unroll
+    for (int r = 0; r < kPostRows; ++r) {
+        if (t0 + r >= T) break;
+        const float inv = sum[r] > 0.f ? 1.0f / sum[r] : 0.f;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int s = lane + kWave * k;
+            if (s < p.NS) stream_store(out + r * p.NS + s, z[r][k] * inv);
+        }
+    }
+}
+
+template <int K>
+static int run_blank_post(PostParams &pp, hipStream_t s)
+{
+    constexpr int RW = align_row_pitch(K);
+    AlignParams &p = pp.a;
+    p.RW = RW;
+    pp.NSP = kWave * K;
+    pp.NS = 2 * p.S + 1;
+    const size_t cells = (size_t)p.B * p.T;
+    char *ws = reinterpret_cast<char *>(p.counter) + 256;
+    p.em = reinterpret_cast<float *>(ws);
+    pp.al = p.em + cells * RW;
+    pp.be = pp.al + cells * pp.NSP;
+    // the three lattice areas of the blank loss ([B][T][NSP] each, NSP = 64 K) hold em + al + be; nothing behind them
+    if ((size_t)RW + 2 * (size_t)pp.NSP > 3 * (size_t)pp.NSP) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
+    const int rows_per_block = (kAlignGatherThreads / kWave) * kAlignGatherRows;
+    int rc = launch<blank_align_gather_kernel<K>>(dim3((p.T + rows_per_block - 1) / rows_per_block, p.B),
+                                                  dim3(kAlignGatherThreads), 0, s, p);
+    if (rc) return rc;
+    rc = launch<blank_post_chain_kernel<K>>(dim3(p.B), dim3(2 * kWave), 0, s, pp);
+    if (rc) return rc;
+    const int rows = (kPostThreads / kWave) * kPostRows;
+    return launch<blank_post_gamma_kernel<K>>(dim3((p.T + rows - 1) / rows, p.B), dim3(kPostThreads), 0, s, pp);
+}
+
 }  // namespace ctc
 
 using namespace ctc;
@@ -474,4 +775,28 @@ extern "C" int ctc_amd_blank_best_path(const float *log_probs, int64_t stride_t,
     if (ns <= kWave * 2) return run_blank_align<2>(p, s);
     if (ns <= kWave * 4) return run_blank_align<4>(p, s);
     return run_blank_align<8>(p, s);
+}
+
+extern "C" int ctc_amd_blank_posteriors(const float *log_probs, int64_t stride_t, int64_t stride_b,
+                                        const void *targets, int targets_i64,
+                                        const int64_t *in_len, const int64_t *tgt_len,
+                                        int T, int B, int C, int S, int blank,
+                                        float *nll, float *gamma, void *workspace, void *stream)
+{
+    if (!log_probs || !targets || !in_len || !tgt_len || !nll || !gamma || !workspace) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (T < 1 || B < 1 || C < 1 || S < 1 || blank < 0 || blank >= C) return CTC_AMD_ERR_BAD_ARGUMENT;
+    const int ns = 2 * S + 1;
+    if (ns > kWave * 8) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;                 // S <= 255
+    PostParams pp = {};
+    AlignParams &p = pp.a;
+    p.lp = log_probs; p.st = stride_t; p.sb = stride_b;
+    p.tgt = targets; p.tgt64 = targets_i64;
+    p.in_len = in_len; p.tgt_len = tgt_len;
+    p.T = T; p.B = B; p.C = C; p.S = S; p.blank = blank;
+    p.counter = static_cast<unsigned *>(workspace);
+    pp.nll = nll; pp.gamma = gamma;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (ns <= kWave * 2) return run_blank_post<2>(pp, s);
+    if (ns <= kWave * 4) return run_blank_post<4>(pp, s);
+    return run_blank_post<8>(pp, s);
 }

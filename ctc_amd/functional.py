@@ -79,7 +79,8 @@ def release_workspaces(device=None):
     return freed
 
 
-STATUS_BITS = {1: "no-blank launch", 2: "binary launch", 4: "blank-CTC launch", 8: "blank-CTC best path"}
+STATUS_BITS = {1: "no-blank launch", 2: "binary launch", 4: "blank-CTC launch", 8: "blank-CTC best path",
+               16: "blank-CTC posteriors"}
 
 
 def workspace_status(device=None, clear=True):
@@ -603,6 +604,52 @@ def blank_forced_align(log_probs, targets, input_lengths, target_lengths, blank=
     fs = torch.gather(lp, 2, tokens.clamp(min=0).unsqueeze(2)).squeeze(2)
     frame_scores = torch.where(valid, fs, torch.zeros_like(fs))
     return tokens, frame_scores
+
+
+def blank_posteriors(log_probs, targets, input_lengths, target_lengths, blank=0):
+    """Per-frame state posteriors of the blank-CTC lattice -> (gamma[B,T,2S+1] fp32, nll[B] fp32).
+
+    Same inputs as ``blank_best_path``.  ``gamma[b,t,s]`` = P(extended-label state s at frame t | log_probs, targets)
+    (even s = blank, odd s = label (s-1)//2 of targets[b]); rows sum to 1 for ``t < T_b``, and are 0 for ``t >= T_b``,
+    for ``s > 2 L_b`` and for samples with no alignment (``nll`` +inf, as ``blank_ctc_loss`` reports it).  Not
+    differentiable.  ``gamma[b, t, path[b, t]]`` with ``blank_best_path``'s path is the confidence of each aligned
+    frame.  include/ctc_amd.h: ctc_amd_blank_posteriors.
+    """
+    _require_hip(log_probs, "log_probs")
+    if log_probs.dim() != 3 or log_probs.dtype != torch.float32:
+        raise ValueError("ctc_amd: log_probs must be float32 [T,B,C]")
+    T, B, C = log_probs.shape
+    if T < 1 or B < 1 or C < 1:
+        raise ValueError("ctc_amd: empty log_probs %s" % (tuple(log_probs.shape),))
+    dev = log_probs.device
+    xs = log_probs.detach()
+    if xs.stride(2) != 1:
+        xs = xs.contiguous()
+    if not isinstance(targets, torch.Tensor) or targets.dim() != 2 or targets.dtype.is_floating_point \
+            or targets.shape[0] != B:
+        raise ValueError("ctc_amd: targets must be [B,S] integer")
+    if targets.dtype not in (torch.int32, torch.int64):
+        targets = targets.long()
+    tg = targets if (targets.device == dev and targets.is_contiguous()) else \
+        targets.to(device=dev, non_blocking=True).contiguous()
+    S = tg.shape[1]
+    if S < 1:
+        raise ValueError("ctc_amd: targets need at least one label column")
+    il = _lengths(input_lengths, B, "input_lengths", dev, T)
+    tl = _lengths(target_lengths, B, "target_lengths", dev, S, lo=0)
+    gamma = torch.empty((B, T, 2 * S + 1), dtype=torch.float32, device=dev)
+    nll = torch.empty(B, dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        stream = _stream_handle(dev)
+        ws = _workspace(_lib.BLANK, T, B, C, S, dev, stream)
+        rc = _lib.load().ctc_amd_blank_posteriors(
+            xs.data_ptr(), xs.stride(0), xs.stride(1), tg.data_ptr(), int(tg.dtype is torch.int64),
+            il.data_ptr(), tl.data_ptr(), T, B, C, S, int(blank), nll.data_ptr(), gamma.data_ptr(), ws.data_ptr(),
+            stream)
+    _lib.check(rc, "ctc_amd_blank_posteriors")
+    if _VALIDATE:
+        check_status(dev)
+    return gamma, nll
 
 
 def noblank_posteriors(logits, targets, input_lengths, target_lengths):

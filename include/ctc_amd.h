@@ -165,7 +165,9 @@ int ctc_amd_blank_set_schedule(int mode);
  * sample, the loss, the sample's gradient rows) and a bit is ORed into the workspace's STATUS word, which
  * stays set until cleared here.  Reads the word (synchronising `stream`); clear != 0 resets it.
  * Bits: 1 no-blank, 2 binary, 4 blank-CTC launch starved, 8 blank-CTC best path starved (that sample's score NaN,
- * its path -1).  Never observed outside fault-injection builds;
+ * its path -1), 16 blank-CTC posteriors (that sample's nll and gamma rows NaN; reserved: its launches hand rows over
+ * at kernel boundaries only and have no in-launch wait, so nothing sets it today).  Never observed outside
+ * fault-injection builds;
  * the persistent blank-CTC launch is the one place where another process's kernels could cause it. */
 int ctc_amd_workspace_status(void *workspace, int clear, void *stream, unsigned *status_host);
 
@@ -235,6 +237,29 @@ int ctc_amd_blank_best_path(const float *log_probs, int64_t stride_t, int64_t st
                             const int64_t *in_len, const int64_t *tgt_len,
                             int T, int B, int C, int S, int blank,
                             int32_t *path, float *score, void *workspace, void *stream);
+
+/* Per-frame state posteriors on the blank-CTC lattice: gamma_t(s) = P(state s at frame t | log_probs, targets), the soft
+ * alignment beside ctc_amd_blank_best_path's hard one.  Inputs: the same layout and contract as ctc_amd_blank_loss_grad
+ * and ctc_amd_blank_best_path (log_probs used as given; stride over classes 1; 0 <= L_b <= S, 1 <= T_b <= T).
+ * Extended labels l'_s, s = 0..2L (even s = blank, odd s = label (s-1)/2).  alpha_0(0) = lp[0,blank],
+ * alpha_0(1) = lp[0,l'_1], others -inf; alpha_t(s) = LSE(alpha_{t-1}(s), alpha_{t-1}(s-1), [alpha_{t-1}(s-2) when
+ * l'_s != blank and l'_s != l'_{s-2}]) + lp[t,l'_s].  beta' leaves out the emission of its own step:
+ * beta'_{T_b-1}(2L) = beta'_{T_b-1}(2L-1) = 0 (state 0 only when L = 0), others -inf, and the mirror recursion over the
+ * successors s, s+1, [s+2 under the same skip rule], each carrying its emission lp[t+1, l'_.].
+ *   nll   [B] out: -LSE(alpha_{T_b-1}(2L), alpha_{T_b-1}(2L-1)), as ctc_amd_blank_loss_grad writes it (+inf: no alignment)
+ *   gamma [B,T,2S+1] fp32 contiguous out: exp(alpha_t(s) + beta'_t(s) + nll) for t < T_b, s <= 2L_b, formed as
+ *         alpha + beta' normalised per row; exactly 0 for t >= T_b, s > 2L_b, at states no path passes through and on
+ *         every row of a sample with no alignment (L_b = 0: gamma[b,t,0] = 1 for t < T_b)
+ * The chains are fp32 but rescaled (the row maximum subtracted every few steps, alpha's offsets summed in double for
+ * nll), so gamma keeps its resolution at long T: within 5e-4 of float64 at T = 2000 (the loss's occupancies: ~1e-2).
+ * workspace: at least ctc_amd_workspace_bytes(CTC_AMD_BLANK, T, B, C, S) bytes; only the lattice areas behind the
+ * 256-byte header are written (not the loss's state tables and hand-off words behind them; the header is left alone
+ * except for status bit 16).  S <= 255 (CTC_AMD_ERR_UNSUPPORTED_SHAPE beyond), any T.  Deterministic. */
+int ctc_amd_blank_posteriors(const float *log_probs, int64_t stride_t, int64_t stride_b,
+                             const void *targets, int targets_i64,
+                             const int64_t *in_len, const int64_t *tgt_len,
+                             int T, int B, int C, int S, int blank,
+                             float *nll, float *gamma, void *workspace, void *stream);
 
 /* Target construction: the dedup step of the reference's dataset preparation,
  * datasets/charades_ctc_next_pred.py:646-651,663-678 (same code at :503-505,523-531) -- out[b] = the rows of
