@@ -69,17 +69,22 @@ def build(force=False, verbose=False, extra_flags=(), name=None):
     return so
 
 
+def _build_variant(name, flag, verbose):
+    """lib/libctc_amd_<name>.so, rebuilt only when it is older than the (current) product library"""
+    so = os.path.join(LIBDIR, "libctc_amd_%s.so" % name)
+    if os.path.exists(so) and os.path.getmtime(so) >= os.path.getmtime(build()):
+        return so
+    return build(force=True, verbose=verbose, extra_flags=(flag,), name=name)
+
+
 def build_diag(verbose=False):
-    return build(force=True, verbose=verbose, extra_flags=("-DCTC_AMD_DIAGNOSTICS",), name="diag")
+    return _build_variant("diag", "-DCTC_AMD_DIAGNOSTICS", verbose)
 
 
 def build_fault(verbose=False):
     """The fault-injection variant tests/test_status.py drives (-DCTC_AMD_FAULT_INJECT -> lib/libctc_amd_fault.so):
     built here, with the product library, so that the GPU run compiles nothing."""
-    so = os.path.join(LIBDIR, "libctc_amd_fault.so")
-    if os.path.exists(so) and os.path.getmtime(so) >= os.path.getmtime(build()):
-        return so
-    return build(force=True, verbose=verbose, extra_flags=("-DCTC_AMD_FAULT_INJECT",), name="fault")
+    return _build_variant("fault", "-DCTC_AMD_FAULT_INJECT", verbose)
 
 
 def build_occupant():

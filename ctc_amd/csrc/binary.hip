@@ -1084,15 +1084,24 @@ __global__ __launch_bounds__(kBinThreads) void binary_pipe_kernel(BinaryParams p
     stamp(p, 7);
 }
 
-template <bool WT>
+// pitch of the label-row images the MFMA kernels read: >= C (+K padding), PD = 2 (mod 32): conflict-free MFMA
+// fragment reads
+static int binary_image_pitch(int C)
+{
+    int PD = (C + 3) / 4 * 4 + 2;
+    while (PD % 32 != 2) PD += 2;
+    return PD;
+}
+
+template <bool WT, bool GAMMA = false>
 static int launch_binary_pipe_wt(int ch, size_t smem, hipStream_t s, const BinaryParams &p, int PD)
 {
     const dim3 grid(p.B), block(kBinThreads);
     switch (ch) {
-        case 1: return launch<binary_pipe_kernel<1, WT>>(grid, block, smem, s, p, PD);
-        case 2: return launch<binary_pipe_kernel<2, WT>>(grid, block, smem, s, p, PD);
-        case 3: return launch<binary_pipe_kernel<3, WT>>(grid, block, smem, s, p, PD);
-        default: return launch<binary_pipe_kernel<4, WT>>(grid, block, smem, s, p, PD);
+        case 1: return launch<binary_pipe_kernel<1, WT, GAMMA>>(grid, block, smem, s, p, PD);
+        case 2: return launch<binary_pipe_kernel<2, WT, GAMMA>>(grid, block, smem, s, p, PD);
+        case 3: return launch<binary_pipe_kernel<3, WT, GAMMA>>(grid, block, smem, s, p, PD);
+        default: return launch<binary_pipe_kernel<4, WT, GAMMA>>(grid, block, smem, s, p, PD);
     }
 }
 
@@ -1134,14 +1143,13 @@ extern "C" int ctc_amd_binary_loss_grad(const float *x, int64_t stride_t, int64_
 {
     if (!x || !y || !in_len || !tgt_len || !nll || !loss || !workspace) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (T < 1 || B < 1 || C < 1 || S < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
-    int K = 1;
-    while (K <= 4 && S > kWave * K) K *= 2;
+    const auto [K, SP] = lane_states(S);
     if (K > 4) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
     BinaryParams p;
     p.x = x; p.st = stride_t; p.sb = stride_b; p.y = y;
     p.in_len = in_len; p.tgt_len = tgt_len;
     p.T = T; p.B = B; p.C = C; p.S = S;
-    p.SP = (S + K - 1) / K * K;
+    p.SP = SP;
     p.CP = C | 1;                                            // odd pitch: conflict-free column walks
     p.loss_scale = loss_scale; p.grad_scale = grad_scale;
     p.nll = nll; p.loss = loss; p.grad = grad; p.gamma = nullptr;
@@ -1156,8 +1164,7 @@ extern "C" int ctc_amd_binary_loss_grad(const float *x, int64_t stride_t, int64_
         q.SP = (p.SP + 3) / 4 * 4;                           // K padding of the gamma . Y product
         if (q.SP % K) q.SP = (q.SP + 4 * K - 1) / (4 * K) * (4 * K);
         const int Tpad = (T + 15) / 16 * 16;
-        int PD = (C + 3) / 4 * 4 + 2;                        // >= C (+K padding), PD = 2 (mod 32):
-        while (PD % 32 != 2) PD += 2;                        // conflict-free MFMA fragment reads
+        const int PD = binary_image_pitch(C);
         const size_t need = binary_mfma_smem_bytes(T, Tpad, q.SP, PD);
         const int ch = (C + kWave - 1) / kWave;
         static const bool no_pipe = diag_env("CTC_AMD_BINARY_NOPIPE") != 0;
@@ -1216,15 +1223,8 @@ extern "C" int ctc_amd_binary_posteriors(const float *x, int64_t stride_t, int64
         const size_t fb = binary_flow_smem_bytes(T, q.SP, PF, C);
         if (fb <= kMaxLds) return launch_binary_flow_wt<true, true>(ch, fb, s, q, PF);
     }
-    int PD = (C + 3) / 4 * 4 + 2;
-    while (PD % 32 != 2) PD += 2;
+    const int PD = binary_image_pitch(C);
     const size_t smem = binary_pipe_smem_bytes(T, q.SP, PD);
     if (smem > kMaxLds) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
-    const dim3 grid(B), block(kBinThreads);
-    switch (ch) {
-        case 1: return launch<binary_pipe_kernel<1, true, true>>(grid, block, smem, s, q, PD);
-        case 2: return launch<binary_pipe_kernel<2, true, true>>(grid, block, smem, s, q, PD);
-        case 3: return launch<binary_pipe_kernel<3, true, true>>(grid, block, smem, s, q, PD);
-        default: return launch<binary_pipe_kernel<4, true, true>>(grid, block, smem, s, q, PD);
-    }
+    return launch_binary_pipe_wt<true, true>(ch, smem, s, q, PD);
 }

@@ -24,6 +24,16 @@ constexpr int kWave = 64;
 constexpr float kNeg = -10000000000000.0f;
 constexpr float kInfeasible = 1.0e12f;   // nll above this <=> no alignment exists
 
+// S lattice states over the 64 lanes of the chain's wave: K = 1, 2 or 4 per lane, S padded to a multiple of K.
+// K = 8 means S > 256, which no kernel takes.
+struct LaneStates { int K, SP; };
+inline LaneStates lane_states(int S)
+{
+    int K = 1;
+    while (K <= 4 && S > kWave * K) K *= 2;
+    return {K, (S + K - 1) / K * K};
+}
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (kWave - 1); }
 // wave-uniform by construction: keep it in an SGPR so row indices / LDS row addresses are scalar
 __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }

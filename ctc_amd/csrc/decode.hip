@@ -170,15 +170,14 @@ extern "C" int ctc_amd_noblank_best_path(const float *x, int64_t stride_t, int64
     (void)workspace;
     if (!x || !labels || !in_len || !tgt_len || !path || !score) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (T < 1 || B < 1 || C < 1 || S < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
-    int K = 1;
-    while (K <= 4 && S > kWave * K) K *= 2;
+    const auto [K, SP] = lane_states(S);
     if (K > 4) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
     DecodeParams p;
     p.x = x; p.st = stride_t; p.sb = stride_b;
     p.lab = labels; p.lab64 = labels_i64;
     p.in_len = in_len; p.tgt_len = tgt_len;
     p.T = T; p.B = B; p.C = C; p.S = S;
-    p.SP = (S + K - 1) / K * K;
+    p.SP = SP;
     p.path = path; p.score = score;
     const size_t smem = ((size_t)T * p.SP + p.SP) * 4 + (size_t)T * p.SP + 16;
     if (smem > kMaxLds) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
@@ -201,15 +200,14 @@ extern "C" int ctc_amd_binary_best_path(const float *x, int64_t stride_t, int64_
     (void)workspace;
     if (!x || !y || !in_len || !tgt_len || !path || !score) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (T < 1 || B < 1 || C < 1 || S < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
-    int K = 1;
-    while (K <= 4 && S > kWave * K) K *= 2;
+    const auto [K, SP] = lane_states(S);
     if (K > 4) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
     DecodeParams p;
     p.x = x; p.st = stride_t; p.sb = stride_b;
     p.lab = nullptr; p.lab64 = 0;
     p.in_len = in_len; p.tgt_len = tgt_len;
     p.T = T; p.B = B; p.C = C; p.S = S;
-    p.SP = (S + K - 1) / K * K;
+    p.SP = SP;
     p.path = path; p.score = score;
     const size_t smem = ((size_t)T * p.SP + (size_t)kDecWaves * C) * 4 + (size_t)T * p.SP + 16;
     if (smem > kMaxLds) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;

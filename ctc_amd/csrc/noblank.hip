@@ -20,6 +20,8 @@
 // (common.hpp), overlapped with P3.  HBM traffic = read x once, write grad once.
 // Shapes beyond the register-resident tiling (T > 160 rows per pass, C > 256) fall
 // back to re-reading rows from L2 in P3 / to strided row passes.
+#include <type_traits>
+
 #include "lattice.hpp"
 #include "launch.hpp"
 
@@ -97,15 +99,28 @@ static size_t noblank_smem_bytes(int T, int SP, int C)
 {
     return noblank_lattice_floats(T, SP) * 4 + noblank_tables_bytes(SP, C);
 }
+// What a shape needs of the phase-serial kernel (noblank_fused_kernel), which takes every supported shape.  `glb`: a
+// long sequence -- the T x S lattice does not fit in LDS and lives in the workspace, one slab per sample; `smem` then
+// counts the tables alone.  K > 4 or smem > kMaxLds: no kernel takes the shape.
+struct NoblankSizes {
+    int K, SP;
+    bool glb;
+    size_t smem;
+};
+static NoblankSizes noblank_sizes(int T, int C, int S)
+{
+    const auto [K, SP] = lane_states(S);
+    const size_t smem = noblank_smem_bytes(T, SP, C);
+    if (smem <= kMaxLds) return {K, SP, false, smem};
+    return {K, SP, true, noblank_tables_bytes(SP, C)};
+}
 // extra workspace (beyond the first 256 B) of the no-blank entry points: 0 while the lattice
 // fits in LDS, else one slab per sample
 size_t noblank_extra_workspace(int T, int B, int C, int S)
 {
-    int K = 1;
-    while (K <= 4 && S > kWave * K) K *= 2;
-    const int SP = (S + K - 1) / K * K;
-    if (K > 4 || noblank_smem_bytes(T, SP, C) <= kMaxLds) return 0;
-    return (size_t)B * noblank_lattice_floats(T, SP) * 4;
+    const NoblankSizes z = noblank_sizes(T, C, S);
+    if (z.K > 4 || !z.glb) return 0;
+    return (size_t)B * noblank_lattice_floats(T, z.SP) * 4;
 }
 
 __device__ __forceinline__ const float *row_ptr(const NoblankParams &p, int t, int b)
@@ -420,38 +435,6 @@ __global__ __launch_bounds__(256) void scale_grad_kernel(float *g, const float *
     }
 }
 
-// the four-rows-per-wave kernel (noblank_r16.hpp) for a row chunking n4 / n2 (r16_shape): the persistent form when `ps`
-// and two row sets fit the 128 VGPRs of a 16-wave workgroup (4 n4 + 2 n2 <= 12, C <= 192), else one sample per workgroup
-template <typename E>
-static int launch_r16(int n4, int n2, bool nt, bool ps, int cus, size_t rsmem, hipStream_t s, const NoblankParams &p)
-{
-    const dim3 grid(p.B), block(kThreads);
-    if (ps) {
-        const dim3 pgrid(cus);
-#define CTC_R16_CASE(K, A, Bq)                                                                          \
-        case K: return nt ? launch<noblank_r16_kernel<A, Bq, true, true, E>>(pgrid, block, rsmem, s, p)   \
-                          : launch<noblank_r16_kernel<A, Bq, false, true, E>>(pgrid, block, rsmem, s, p);
-        switch (4 * n4 + n2) {
-            CTC_R16_CASE(1, 0, 1) CTC_R16_CASE(2, 0, 2) CTC_R16_CASE(4, 1, 0) CTC_R16_CASE(5, 1, 1)
-            CTC_R16_CASE(6, 1, 2) CTC_R16_CASE(8, 2, 0) CTC_R16_CASE(9, 2, 1) CTC_R16_CASE(10, 2, 2)
-            CTC_R16_CASE(12, 3, 0)
-            default: break;
-        }
-#undef CTC_R16_CASE
-    }
-#define CTC_R16_CASE(K, A, Bq)                                                                          \
-    case K: return nt ? launch<noblank_r16_kernel<A, Bq, true, false, E>>(grid, block, rsmem, s, p)   \
-                      : launch<noblank_r16_kernel<A, Bq, false, false, E>>(grid, block, rsmem, s, p);
-    switch (4 * n4 + n2) {
-        CTC_R16_CASE(1, 0, 1) CTC_R16_CASE(2, 0, 2) CTC_R16_CASE(4, 1, 0) CTC_R16_CASE(5, 1, 1)
-        CTC_R16_CASE(6, 1, 2) CTC_R16_CASE(8, 2, 0) CTC_R16_CASE(9, 2, 1) CTC_R16_CASE(10, 2, 2)
-        CTC_R16_CASE(12, 3, 0) CTC_R16_CASE(13, 3, 1) CTC_R16_CASE(14, 3, 2)
-        default: return nt ? launch<noblank_r16_kernel<4, 0, true, false, E>>(grid, block, rsmem, s, p)
-                           : launch<noblank_r16_kernel<4, 0, false, false, E>>(grid, block, rsmem, s, p);
-    }
-#undef CTC_R16_CASE
-}
-
 // the same for a 2-byte gradient (ctc_amd_scale_grad_typed): round(float(g) * s), 8 bytes per access where the array is
 // 8-byte aligned
 template <typename E>
@@ -477,180 +460,266 @@ __global__ __launch_bounds__(256) void scale_grad_lowp_kernel(E *g, const float 
     for (size_t k = done + i; k < n; k += stride) g[k] = (E)((float)g[k] * s);
 }
 
-template <int K>
-static int launch_noblank(int ch, size_t smem, hipStream_t s, const NoblankParams &p)
+// ---- host side of the entry points: parameters, then a plan, then a launch -------------------------
+
+// Forced kernel choices and debug stops of the diagnostics build (launch.hpp: the product library reads none of them).
+struct NoblankSwitches {
+    bool no_pipe, no_xr, no_r16, no_ps, km;
+    bool nograd;                // forward only
+    int stop;                   // NoblankParams::stop
+};
+static const NoblankSwitches &noblank_switches()
 {
-    const dim3 grid(p.B), block(kThreads);
-    if (p.lattice) return launch<noblank_fused_kernel<K, 0, true>>(grid, block, smem, s, p);
-    switch (ch) {
-        case 1: return launch<noblank_fused_kernel<K, 1>>(grid, block, smem, s, p);
-        case 2: return launch<noblank_fused_kernel<K, 2>>(grid, block, smem, s, p);
-        case 3: return launch<noblank_fused_kernel<K, 3>>(grid, block, smem, s, p);
-        case 4: return launch<noblank_fused_kernel<K, 4>>(grid, block, smem, s, p);
-        default: return launch<noblank_fused_kernel<K, 0>>(grid, block, smem, s, p);
+    static const NoblankSwitches sw = {diag_env("CTC_AMD_NOPIPE") != 0, diag_env("CTC_AMD_NOXR") != 0,
+                                       diag_env("CTC_AMD_NOR16") != 0,  diag_env("CTC_AMD_NOPS") != 0,
+                                       diag_env("CTC_AMD_KM") != 0,     diag_env("CTC_AMD_DEBUG_NOGRAD") != 0,
+                                       diag_env("CTC_AMD_DEBUG_STOP")};
+    return sw;
+}
+
+// Step 1: what the kernels take, from an entry point's arguments.  `gamma` set: the posteriors call, whose batch-mean
+// slot of the in-launch reduction lands in a spare workspace word.  label_smoothing < 0: the plain loss.  next_round
+// and koff belong to the plan (noblank_launch).
+static int noblank_params(NoblankParams &p, const void *x, int64_t stride_t, int64_t stride_b,
+                          const void *labels, int labels_i64, const int64_t *in_len, const int64_t *tgt_len,
+                          int T, int B, int C, int S, float loss_scale, float grad_scale,
+                          float *nll, float *loss, void *grad, float *gamma, void *workspace, float label_smoothing,
+                          const NoblankSwitches &sw)
+{
+    if (!x || !labels || !in_len || !tgt_len || !nll || !(loss || gamma) || !workspace) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (T < 1 || B < 1 || C < 1 || S < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
+    const NoblankSizes z = noblank_sizes(T, C, S);
+    char *ws = static_cast<char *>(workspace);
+    p.x = static_cast<const float *>(x); p.st = stride_t; p.sb = stride_b;
+    p.lab = labels; p.lab64 = labels_i64;
+    p.in_len = in_len; p.tgt_len = tgt_len;
+    p.T = T; p.B = B; p.C = C; p.S = S; p.SP = z.SP;
+    p.stop = sw.stop;
+    p.loss_scale = loss_scale; p.grad_scale = grad_scale;
+    p.nll = nll; p.loss = gamma ? reinterpret_cast<float *>(ws + 32) : loss;
+    p.grad = sw.nograd ? nullptr : static_cast<float *>(grad);
+    p.gamma = gamma;
+    p.counter = static_cast<unsigned *>(workspace);
+    p.lattice = z.glb ? reinterpret_cast<float *>(ws + 256 + acc_list_bytes(B)) : nullptr;   // behind header and list
+    p.slab = z.glb ? (int64_t)noblank_lattice_floats(T, z.SP) : 0;
+    p.next_round = 0; p.koff = 0;
+    const bool smooth = label_smoothing >= 0.f;
+    p.ls_b = smooth ? (1.f - label_smoothing) / (float)C : 0.f;
+    p.ls_a = smooth ? label_smoothing - p.ls_b : 1.f;
+    return 0;
+}
+
+// Step 2: which kernel takes a call.  Everything the choice depends on ...
+struct NoblankQuery {
+    int T, B, C, S;
+    int dtype;                  // CTC_AMD_F32 / _BF16 / _F16: element type of x and grad
+    int64_t st, sb;             // strides of x, in elements
+    unsigned x_low, grad_low;   // low four bits of the two addresses (no gradient: 0)
+    bool want_grad, want_gamma, smooth;
+    int cus;                    // compute units of the device
+    NoblankSwitches sw;
+};
+// ... and the choice: the template selectors of the family's kernel, grid, dynamic LDS, NoblankParams::next_round / koff.
+enum NoblankFamily { kNoblankUnsupported = 0, kNoblankR16, kNoblankKm, kNoblankXr, kNoblankPipelined, kNoblankFused };
+struct NoblankPlan {
+    int family;
+    int n4, n2, nt, ps;         // r16, km: row chunking (r16_shape), non-temporal gradient stores, persistent form
+    int ch, dual;               // xr, pipelined, fused: 64-column chunks of a row (0: generic rows), two workgroups per CU
+    int K, glb;                 // fused: states per lane, lattice in the workspace
+    int grid;
+    size_t lds;
+    int next_round, koff;
+};
+
+// The four-rows-per-wave kernel (noblank_r16.hpp) takes a shape when one wave holds the states (S <= 31 of K = 1), the
+// rows fit its workers (T <= 168, C even <= 256), it can move them in aligned 8-byte pieces -- `align` is what that
+// asks of the two addresses: 8 bytes for fp32, 4 bytes for 2-byte elements -- and its arrays fit in LDS.
+static bool r16_takes(const NoblankQuery &q, const NoblankSizes &z, unsigned align, int &n4, int &n2)
+{
+    return z.K == 1 && q.T <= kPipeMaxT && q.C % 2 == 0 && q.st % 2 == 0 && q.sb % 2 == 0 && q.x_low % align == 0 &&
+           q.grad_low % align == 0 && r16_shape(q.C, n4, n2) && z.SP <= 31 && r16_smem_bytes(q.T, z.SP, q.C) <= kMaxLds;
+}
+
+static NoblankPlan noblank_plan(const NoblankQuery &q)
+{
+    const NoblankSizes z = noblank_sizes(q.T, q.C, q.S);
+    NoblankPlan pl = {};
+    if (z.K > 4) return pl;                                  // S <= 256
+    const bool lowp = q.dtype != CTC_AMD_F32;
+    const int esz = lowp ? 2 : 4, cus = q.cus;
+    pl.grid = q.B;
+    int n4 = 0, n2 = 0;
+    const bool r16 = r16_takes(q, z, lowp ? 4 : 8, n4, n2);
+    // label_smoothing: the smoothed emission lives in the r16 kernel only.  2-byte logits: that kernel or nothing (no
+    // silent detour through another kernel or an fp32 copy), whatever the switches say.
+    const bool r16_only = q.smooth || lowp;
+    const bool fast = z.K == 1 && q.C <= 256 && q.T <= kPipeMaxT && !q.sw.no_pipe && !z.glb && !q.want_gamma;
+    // The r16 kernel wherever it takes the shape (which then always fits in LDS).  The posteriors: same chains, the
+    // gradient phase cut off after the row-normalised posteriors.  The loss: in the common case (S <= 64, C <= 256,
+    // T <= 168: the schedules that overlap rows, chains and gradient), also with more samples than CUs: one workgroup
+    // per CU at a time still beats two of the one-row-per-wave kind
+    // (T = 150, C = 158, us per launch r16 / xr: B = 384 22.5 / 27.7, 512 25.9 / 31.2, 768 37.6 / 45.2,
+    // 1024 49.7 / 56.6, 1536 78.2 / 78.5, 2048 101.3 / 99.7)
+    if (r16 && (q.want_gamma || lowp || (fast && !q.sw.no_r16))) {
+        pl.n4 = n4; pl.n2 = n2;
+        pl.lds = r16_smem_bytes(q.T, z.SP, q.C);
+        if (q.want_gamma) { pl.family = kNoblankR16; return pl; }
+        // logits + gradient beyond the memory-side cache (256 MB): non-temporal gradient stores
+        pl.nt = (size_t)2 * esz * q.T * q.B * q.C > ((size_t)230 << 20);
+#ifdef CTC_AMD_DIAGNOSTICS
+        // the chains split over exponent and mantissa waves (noblank_km.hpp) wherever its arrays fit and the number of
+        // lattice paths leaves two mantissas room in fp32
+        const int koff = km_offset(q.T, q.S);
+        if (q.sw.km && !lowp && km_smem_bytes(q.T, z.SP, q.C) <= kMaxLds && koff >= 0) {
+            pl.family = kNoblankKm;
+            pl.lds = km_smem_bytes(q.T, z.SP, q.C);
+            pl.koff = koff;
+            pl.next_round = (q.B > cus && (size_t)q.T * ((q.C * 4 + 127) / 128) <= (size_t)kKmWorkers * kWave) ? cus : 0;
+            return pl;
+        }
+#endif
+        pl.family = kNoblankR16;
+        // more samples than CUs: a workgroup prefetches the rows of the sample that follows it on its CU
+        pl.next_round = (q.B > cus && (size_t)q.T * ((q.C * esz + 127) / 128) <= (size_t)kPipeWorkers * kWave) ? cus : 0;
+        // More than two rounds of samples: one PERSISTENT workgroup per CU that keeps the next sample's rows in a
+        // second set of registers (noblank_r16.hpp), wherever two sets fit the 128 VGPRs of a 16-wave workgroup
+        // (4 n4 + 2 n2 <= 12, which is C <= 192) and a gradient is wanted.  T = 150, C = 158, us per launch persistent /
+        // one sample per workgroup: B = 2048 82.7 / 98.0, 1024 41.7 / 45.1, 512 24.3 / 24.1.
+        pl.ps = q.B > 2 * cus && cus > 0 && !q.sw.no_ps && q.want_grad && 4 * n4 + 2 * n2 <= 12;
+        if (pl.ps) pl.grid = cus;
+        return pl;
     }
+    if (r16_only || (z.glb && z.smem > kMaxLds)) return NoblankPlan{};
+    if (fast) {
+        pl.ch = (q.C + kWave - 1) / kWave;
+        pl.dual = q.B > cus && 2 * z.smem <= kMaxLds;        // more samples than CUs: two workgroups per CU
+        // extended-range linear lattice (noblank_xr.hpp) wherever its 8-byte cells fit
+        const size_t xsmem = xr_smem_bytes(q.T, z.SP, q.C);
+        const bool xr = !q.sw.no_xr && xsmem <= kMaxLds && (!pl.dual || 2 * xsmem <= kMaxLds);
+        pl.family = xr ? kNoblankXr : kNoblankPipelined;
+        pl.lds = xr ? xsmem : z.smem;
+        return pl;
+    }
+    pl.family = kNoblankFused;
+    pl.K = z.K; pl.glb = z.glb;
+    pl.ch = q.C <= 256 && !z.glb ? (q.C + kWave - 1) / kWave : 0;
+    pl.lds = z.smem;
+    return pl;
+}
+
+// Step 3: the plan's numbers as template arguments.  f(std::integral_constant<int, N>()) for N = n if it is one of
+// Ns..., else for the last of them.
+template <int N, int... Ns, typename F>
+static int with_constant(int n, F f)
+{
+    if constexpr (sizeof...(Ns) == 0) {
+        return f(std::integral_constant<int, N>());
+    } else {
+        return n == N ? f(std::integral_constant<int, N>()) : with_constant<Ns...>(n, f);
+    }
+}
+// f(n4, n2) for the twelve row chunkings that r16_shape gives
+template <typename F>
+static int with_row_chunks(int n4, int n2, F f)
+{
+    return with_constant<1, 2, 4, 5, 6, 8, 9, 10, 12, 13, 14, 16>(4 * n4 + n2, [&](auto k) {
+        return f(std::integral_constant<int, decltype(k)::value / 4>(), std::integral_constant<int, decltype(k)::value % 4>());
+    });
+}
+
+static int noblank_launch(const NoblankPlan &pl, int dtype, NoblankParams &p, hipStream_t s)
+{
+    const dim3 grid(pl.grid), block(kThreads);
+    p.next_round = pl.next_round; p.koff = pl.koff;
+    switch (pl.family) {
+        case kNoblankR16:
+            // the persistent form only for the nine chunkings whose two row sets fit the registers (noblank_plan)
+            return with_row_chunks(pl.n4, pl.n2, [&](auto n4, auto n2) {
+                return with_constant<0, 1>(pl.nt, [&](auto nt) {
+                    return with_constant<CTC_AMD_BF16, CTC_AMD_F16, CTC_AMD_F32>(dtype, [&](auto dt) {
+                        using E = std::conditional_t<decltype(dt)::value == CTC_AMD_BF16, __bf16,
+                                                     std::conditional_t<decltype(dt)::value == CTC_AMD_F16, _Float16, float>>;
+                        constexpr int A = decltype(n4)::value, Bq = decltype(n2)::value;
+                        constexpr bool NT = decltype(nt)::value != 0;
+                        if constexpr (4 * A + 2 * Bq <= 12)
+                            if (pl.ps) return launch<noblank_r16_kernel<A, Bq, NT, true, E>>(grid, block, pl.lds, s, p);
+                        return launch<noblank_r16_kernel<A, Bq, NT, false, E>>(grid, block, pl.lds, s, p);
+                    });
+                });
+            });
+#ifdef CTC_AMD_DIAGNOSTICS
+        case kNoblankKm:
+            return with_row_chunks(pl.n4, pl.n2, [&](auto n4, auto n2) {
+                return with_constant<0, 1>(pl.nt, [&](auto nt) {
+                    return launch<noblank_km_kernel<decltype(n4)::value, decltype(n2)::value, decltype(nt)::value != 0>>(
+                        grid, block, pl.lds, s, p);
+                });
+            });
+#endif
+        case kNoblankXr:
+        case kNoblankPipelined:
+            return with_constant<1, 2, 3, 4>(pl.ch, [&](auto ch) {
+                return with_constant<0, 1>(pl.dual, [&](auto dual) {
+                    constexpr int CH = decltype(ch)::value;
+                    constexpr bool DUAL = decltype(dual)::value != 0;
+                    return pl.family == kNoblankXr ? launch<noblank_xr_kernel<CH, DUAL>>(grid, block, pl.lds, s, p)
+                                                   : launch<noblank_pipelined_kernel<CH, DUAL>>(grid, block, pl.lds, s, p);
+                });
+            });
+        case kNoblankFused:
+            return with_constant<1, 2, 4>(pl.K, [&](auto k) {
+                constexpr int K = decltype(k)::value;
+                if (pl.glb) return launch<noblank_fused_kernel<K, 0, true>>(grid, block, pl.lds, s, p);
+                return with_constant<1, 2, 3, 4, 0>(pl.ch, [&](auto ch) {
+                    return launch<noblank_fused_kernel<K, decltype(ch)::value>>(grid, block, pl.lds, s, p);
+                });
+            });
+        default: return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
+    }
+}
+
+// All no-blank entry points.  label_smoothing < 0: the plain loss (every kernel); in [0, 1]: the smoothed emission, r16
+// kernel only.  x_dtype CTC_AMD_BF16 / CTC_AMD_F16: 2-byte x and grad, the r16 kernel's shape domain only
+// (include/ctc_amd.h).  `gamma`: posteriors instead of loss and gradient; they read no diagnostic switch.
+static int noblank_run(const void *x, int64_t stride_t, int64_t stride_b,
+                       const void *labels, int labels_i64,
+                       const int64_t *in_len, const int64_t *tgt_len,
+                       int T, int B, int C, int S,
+                       float loss_scale, float grad_scale,
+                       float *nll, float *loss, void *grad,
+                       void *workspace, void *stream, float label_smoothing, int x_dtype = CTC_AMD_F32,
+                       float *gamma = nullptr)
+{
+    const NoblankSwitches sw = gamma ? NoblankSwitches{} : noblank_switches();
+    NoblankParams p;
+    if (const int rc = noblank_params(p, x, stride_t, stride_b, labels, labels_i64, in_len, tgt_len, T, B, C, S, loss_scale,
+                                      grad_scale, nll, loss, grad, gamma, workspace, label_smoothing, sw))
+        return rc;
+    const NoblankQuery q = {T, B, C, S, x_dtype, stride_t, stride_b,
+                            (unsigned)(reinterpret_cast<uintptr_t>(x) & 15), (unsigned)(reinterpret_cast<uintptr_t>(grad) & 15),
+                            p.grad != nullptr, gamma != nullptr, label_smoothing >= 0.f,
+                            device_cus(),                    // (per device: a process may drive several)
+                            sw};
+    return noblank_launch(noblank_plan(q), x_dtype, p, static_cast<hipStream_t>(stream));
+}
+
+// the grid of the two scale kernels: in the common case (grad_out == 1) every block only reads one float and leaves: the
+// launch costs one kernel boundary, 1.7 us in a graph, for any grid up to 2048 blocks (tools/scale_grad_time.py: 64
+// blocks 1.68, 1024 blocks 1.72 us).  When the gradient must be scaled -- `(loss / accum_steps).backward()`, a loss
+// scaler -- the grid is what moves the 2 x 24 MB of config 2: 64 blocks 17.7 us, 256 blocks 7.8, 1024 blocks 5.9
+// (round 3; it was 64).
+static dim3 scale_grad_grid(size_t n)
+{
+    size_t blocks = (n / 4 + 255) / 256;
+    static const int cap = diag_env("CTC_AMD_SCALE_BLOCKS", 1024);
+    if (blocks > (size_t)cap) blocks = cap;
+    if (blocks < 1) blocks = 1;
+    return dim3((unsigned)blocks);
 }
 
 }  // namespace ctc
 
 using namespace ctc;
-
-static bool r16_no_ps()
-{
-    static const bool no_ps = diag_env("CTC_AMD_NOPS") != 0;
-    return no_ps;
-}
-
-// label_smoothing < 0: the plain loss (every kernel); in [0, 1]: the smoothed emission, r16 kernel only.
-// x_dtype CTC_AMD_BF16 / CTC_AMD_F16: 2-byte x and grad, the r16 kernel's shape domain only (include/ctc_amd.h).
-static int noblank_run(const void *xv, int64_t stride_t, int64_t stride_b,
-                       const void *labels, int labels_i64,
-                       const int64_t *in_len, const int64_t *tgt_len,
-                       int T, int B, int C, int S,
-                       float loss_scale, float grad_scale,
-                       float *nll, float *loss, void *gradv,
-                       void *workspace, void *stream, float label_smoothing, int x_dtype = CTC_AMD_F32)
-{
-    const float *x = static_cast<const float *>(xv);
-    float *grad = static_cast<float *>(gradv);
-    if (!x || !labels || !in_len || !tgt_len || !nll || !loss || !workspace) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (T < 1 || B < 1 || C < 1 || S < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
-    int K = 1;
-    while (K <= 4 && S > kWave * K) K *= 2;
-    if (K > 4) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;         // S <= 256
-    NoblankParams p;
-    p.x = x; p.st = stride_t; p.sb = stride_b;
-    p.lab = labels; p.lab64 = labels_i64;
-    p.in_len = in_len; p.tgt_len = tgt_len;
-    p.T = T; p.B = B; p.C = C; p.S = S;
-    p.SP = (S + K - 1) / K * K;
-    static const int debug_stop = diag_env("CTC_AMD_DEBUG_STOP");
-    p.stop = debug_stop;
-    p.loss_scale = loss_scale; p.grad_scale = grad_scale;
-    p.nll = nll; p.loss = loss; p.grad = grad; p.gamma = nullptr;
-    static const bool debug_nograd = diag_env("CTC_AMD_DEBUG_NOGRAD") != 0;       // diagnostic: forward only
-    if (debug_nograd) p.grad = nullptr;
-    p.counter = static_cast<unsigned *>(workspace);
-    p.lattice = nullptr; p.slab = 0; p.next_round = 0; p.koff = 0;
-    const bool smooth = label_smoothing >= 0.f;
-    p.ls_b = smooth ? (1.f - label_smoothing) / (float)C : 0.f;
-    p.ls_a = smooth ? label_smoothing - p.ls_b : 1.f;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (x_dtype != CTC_AMD_F32) {
-        // 2-byte logits: the four-rows-per-wave kernel or nothing (no silent detour through another kernel or an fp32
-        // copy).  Its fp32 conditions with 4-byte instead of 8-byte aligned rows: the kernel moves 8-byte pieces.
-        int n4 = 0, n2 = 0;
-        const bool aligned = C % 2 == 0 && stride_t % 2 == 0 && stride_b % 2 == 0 &&
-                             reinterpret_cast<uintptr_t>(x) % 4 == 0 && reinterpret_cast<uintptr_t>(grad) % 4 == 0;
-        const size_t rsmem = r16_smem_bytes(T, p.SP, C);
-        if (K != 1 || T > kPipeMaxT || !aligned || !r16_shape(C, n4, n2) || p.SP > 31 || rsmem > kMaxLds)
-            return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
-        const int cus = device_cus();
-        const bool nt = (size_t)4 * T * B * C > ((size_t)230 << 20);     // 2 bytes of logits + 2 of gradient per element
-        p.next_round = (B > cus && (size_t)T * ((C * 2 + 127) / 128) <= (size_t)kPipeWorkers * kWave) ? cus : 0;
-        const bool ps = B > 2 * cus && cus > 0 && !r16_no_ps() && p.grad;
-        return x_dtype == CTC_AMD_BF16 ? launch_r16<__bf16>(n4, n2, nt, ps, cus, rsmem, s, p)
-                                       : launch_r16<_Float16>(n4, n2, nt, ps, cus, rsmem, s, p);
-    }
-    size_t smem = noblank_smem_bytes(T, p.SP, C);
-    if (smem > kMaxLds) {                                    // long sequence: lattice in the workspace
-        if (smooth) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
-        smem = noblank_tables_bytes(p.SP, C);
-        if (smem > kMaxLds) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
-        p.lattice = reinterpret_cast<float *>(static_cast<char *>(workspace) + 256 + acc_list_bytes(B));
-        p.slab = (int64_t)noblank_lattice_floats(T, p.SP);
-    }
-    const int ch = C <= 256 ? (C + kWave - 1) / kWave : 0;
-    // common case (S <= 64, C <= 256, T <= 168): the pipelined schedule
-    static const bool no_pipe = diag_env("CTC_AMD_NOPIPE") != 0;
-    if (K == 1 && ch >= 1 && T <= kPipeMaxT && !no_pipe && !p.lattice) {
-        const dim3 grid(B), block(kThreads);
-        const int cus = device_cus();                           // (per device: a process may drive several)
-        // extended-range linear lattice (noblank_xr.hpp) wherever its 8-byte cells fit
-        static const bool no_xr = diag_env("CTC_AMD_NOXR") != 0;
-        const size_t xsmem = xr_smem_bytes(T, p.SP, C);
-        const bool dual = B > cus && 2 * smem <= kMaxLds;    // more samples than CUs: two workgroups per CU
-        // lean four-rows-per-wave workers (noblank_r16.hpp): 8-byte aligned rows, S <= 31
-        static const bool no_r16 = diag_env("CTC_AMD_NOR16") != 0;
-        const bool aligned = C % 2 == 0 && stride_t % 2 == 0 && stride_b % 2 == 0 &&
-                             reinterpret_cast<uintptr_t>(x) % 8 == 0 && reinterpret_cast<uintptr_t>(grad) % 8 == 0;
-        const size_t rsmem = r16_smem_bytes(T, p.SP, C);
-        // lean four-rows-per-wave workers (noblank_r16.hpp): 8-byte aligned rows, S <= 31.  Also with more
-        // samples than CUs: one workgroup per CU at a time still beats two of the one-row-per-wave kind
-        // (T = 150, C = 158, us per launch r16 / xr: B = 384 22.5 / 27.7, 512 25.9 / 31.2, 768 37.6 / 45.2,
-        // 1024 49.7 / 56.6, 1536 78.2 / 78.5, 2048 101.3 / 99.7)
-        int n4 = 0, n2 = 0;
-        if (!no_r16 && aligned && r16_shape(C, n4, n2) && p.SP <= 31 && rsmem <= kMaxLds) {
-            // logits + gradient beyond the memory-side cache (256 MB): non-temporal gradient stores
-            const bool nt = (size_t)8 * T * B * C > ((size_t)230 << 20);
-#ifdef CTC_AMD_DIAGNOSTICS
-            // the chains split over exponent and mantissa waves (noblank_km.hpp) wherever its arrays fit and the
-            // number of lattice paths leaves two mantissas room in fp32
-            static const bool use_km = diag_env("CTC_AMD_KM") != 0;
-            const size_t ksmem = km_smem_bytes(T, p.SP, C);
-            const int koff = km_offset(T, S);
-            if (use_km && ksmem <= kMaxLds && koff >= 0) {
-                p.koff = koff;
-                p.next_round = (B > cus && (size_t)T * ((C * 4 + 127) / 128) <= (size_t)kKmWorkers * kWave) ? cus : 0;
-#define CTC_KM_CASE(K, A, Bq)                                                                           \
-                case K: return nt ? launch<noblank_km_kernel<A, Bq, true>>(grid, block, ksmem, s, p)      \
-                                  : launch<noblank_km_kernel<A, Bq, false>>(grid, block, ksmem, s, p);
-                switch (4 * n4 + n2) {
-                    CTC_KM_CASE(1, 0, 1) CTC_KM_CASE(2, 0, 2) CTC_KM_CASE(4, 1, 0) CTC_KM_CASE(5, 1, 1)
-                    CTC_KM_CASE(6, 1, 2) CTC_KM_CASE(8, 2, 0) CTC_KM_CASE(9, 2, 1) CTC_KM_CASE(10, 2, 2)
-                    CTC_KM_CASE(12, 3, 0) CTC_KM_CASE(13, 3, 1) CTC_KM_CASE(14, 3, 2)
-                    default: return nt ? launch<noblank_km_kernel<4, 0, true>>(grid, block, ksmem, s, p)
-                                       : launch<noblank_km_kernel<4, 0, false>>(grid, block, ksmem, s, p);
-                }
-#undef CTC_KM_CASE
-            }
-#endif
-            p.next_round = (B > cus && (size_t)T * ((C * 4 + 127) / 128) <= (size_t)kPipeWorkers * kWave) ? cus : 0;
-            // More than two rounds of samples: one PERSISTENT workgroup per CU that keeps the next sample's rows in a
-            // second set of registers (noblank_r16.hpp), wherever two sets fit the 128 VGPRs of a 16-wave workgroup
-            // (C <= 192) and a gradient is wanted.  T = 150, C = 158, us per launch persistent / one sample per
-            // workgroup: B = 2048 82.7 / 98.0, 1024 41.7 / 45.1, 512 24.3 / 24.1.
-            return launch_r16<float>(n4, n2, nt, B > 2 * cus && cus > 0 && !r16_no_ps() && p.grad, cus, rsmem, s, p);
-        }
-        if (smooth) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;    // the smoothed emission lives in the kernel above only
-        if (!no_xr && xsmem <= kMaxLds && (!dual || 2 * xsmem <= kMaxLds)) {
-            if (dual) {
-                switch (ch) {
-                    case 1: return launch<noblank_xr_kernel<1, true>>(grid, block, xsmem, s, p);
-                    case 2: return launch<noblank_xr_kernel<2, true>>(grid, block, xsmem, s, p);
-                    case 3: return launch<noblank_xr_kernel<3, true>>(grid, block, xsmem, s, p);
-                    default: return launch<noblank_xr_kernel<4, true>>(grid, block, xsmem, s, p);
-                }
-            }
-            switch (ch) {
-                case 1: return launch<noblank_xr_kernel<1, false>>(grid, block, xsmem, s, p);
-                case 2: return launch<noblank_xr_kernel<2, false>>(grid, block, xsmem, s, p);
-                case 3: return launch<noblank_xr_kernel<3, false>>(grid, block, xsmem, s, p);
-                default: return launch<noblank_xr_kernel<4, false>>(grid, block, xsmem, s, p);
-            }
-        }
-        if (dual) {
-            switch (ch) {
-                case 1: return launch<noblank_pipelined_kernel<1, true>>(grid, block, smem, s, p);
-                case 2: return launch<noblank_pipelined_kernel<2, true>>(grid, block, smem, s, p);
-                case 3: return launch<noblank_pipelined_kernel<3, true>>(grid, block, smem, s, p);
-                default: return launch<noblank_pipelined_kernel<4, true>>(grid, block, smem, s, p);
-            }
-        }
-        switch (ch) {
-            case 1: return launch<noblank_pipelined_kernel<1, false>>(grid, block, smem, s, p);
-            case 2: return launch<noblank_pipelined_kernel<2, false>>(grid, block, smem, s, p);
-            case 3: return launch<noblank_pipelined_kernel<3, false>>(grid, block, smem, s, p);
-            default: return launch<noblank_pipelined_kernel<4, false>>(grid, block, smem, s, p);
-        }
-    }
-    if (smooth) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
-    switch (K) {
-        case 1: return launch_noblank<1>(ch, smem, s, p);
-        case 2: return launch_noblank<2>(ch, smem, s, p);
-        default: return launch_noblank<4>(ch, smem, s, p);
-    }
-}
 
 extern "C" int ctc_amd_noblank_loss_grad(const float *x, int64_t stride_t, int64_t stride_b,
                                          const void *labels, int labels_i64,
@@ -681,15 +750,7 @@ extern "C" int ctc_amd_scale_grad(float *grad, const float *grad_out, size_t n, 
 {
     if (!grad || !grad_out) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (n == 0) return 0;
-    // in the common case (grad_out == 1) every block only reads one float and leaves: the launch costs one kernel boundary,
-    // 1.7 us in a graph, for any grid up to 2048 blocks (tools/scale_grad_time.py: 64 blocks 1.68, 1024 blocks 1.72 us).
-    // When the gradient must be scaled -- `(loss / accum_steps).backward()`, a loss scaler -- the grid is what moves the
-    // 2 x 24 MB of config 2: 64 blocks 17.7 us, 256 blocks 7.8, 1024 blocks 5.9 (round 3; it was 64).
-    size_t blocks = (n / 4 + 255) / 256;
-    static const int cap = diag_env("CTC_AMD_SCALE_BLOCKS", 1024);
-    if (blocks > (size_t)cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(scale_grad_kernel, dim3((unsigned)blocks), dim3(256), 0,
+    hipLaunchKernelGGL(scale_grad_kernel, scale_grad_grid(n), dim3(256), 0,
                        static_cast<hipStream_t>(stream), grad, grad_out, n);
     return (int)hipGetLastError();
 }
@@ -713,15 +774,11 @@ extern "C" int ctc_amd_scale_grad_typed(void *grad, int dtype, const float *grad
     if (dtype == CTC_AMD_F32) return ctc_amd_scale_grad(static_cast<float *>(grad), grad_out, n, stream);
     if ((dtype != CTC_AMD_BF16 && dtype != CTC_AMD_F16) || !grad || !grad_out) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (n == 0) return 0;
-    size_t blocks = (n / 4 + 255) / 256;                     // (the grid of ctc_amd_scale_grad)
-    static const int cap = diag_env("CTC_AMD_SCALE_BLOCKS", 1024);
-    if (blocks > (size_t)cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
     if (dtype == CTC_AMD_BF16)
-        hipLaunchKernelGGL(scale_grad_lowp_kernel<__bf16>, dim3((unsigned)blocks), dim3(256), 0,
+        hipLaunchKernelGGL(scale_grad_lowp_kernel<__bf16>, scale_grad_grid(n), dim3(256), 0,
                            static_cast<hipStream_t>(stream), static_cast<__bf16 *>(grad), grad_out, n);
     else
-        hipLaunchKernelGGL(scale_grad_lowp_kernel<_Float16>, dim3((unsigned)blocks), dim3(256), 0,
+        hipLaunchKernelGGL(scale_grad_lowp_kernel<_Float16>, scale_grad_grid(n), dim3(256), 0,
                            static_cast<hipStream_t>(stream), static_cast<_Float16 *>(grad), grad_out, n);
     return (int)hipGetLastError();
 }
@@ -733,55 +790,9 @@ extern "C" int ctc_amd_noblank_posteriors(const float *x, int64_t stride_t, int6
                                           float *nll, float *gamma,
                                           void *workspace, void *stream)
 {
-    if (!x || !labels || !in_len || !tgt_len || !nll || !gamma || !workspace) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (T < 1 || B < 1 || C < 1 || S < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
-    int K = 1;
-    while (K <= 4 && S > kWave * K) K *= 2;
-    if (K > 4) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
-    NoblankParams p;
-    p.x = x; p.st = stride_t; p.sb = stride_b;
-    p.lab = labels; p.lab64 = labels_i64;
-    p.in_len = in_len; p.tgt_len = tgt_len;
-    p.T = T; p.B = B; p.C = C; p.S = S;
-    p.SP = (S + K - 1) / K * K;
-    p.stop = 0;
-    p.loss_scale = 0.f; p.grad_scale = 0.f;
-    p.nll = nll; p.grad = nullptr; p.gamma = gamma;
-    // the batch-mean slot of the in-launch reduction lands in a spare workspace word
-    p.counter = static_cast<unsigned *>(workspace);
-    p.loss = reinterpret_cast<float *>(static_cast<char *>(workspace) + 32);
-    p.lattice = nullptr; p.slab = 0; p.next_round = 0; p.ls_a = 1.f; p.ls_b = 0.f; p.koff = 0;
-    size_t smem = noblank_smem_bytes(T, p.SP, C);
-    if (smem > kMaxLds) {
-        smem = noblank_tables_bytes(p.SP, C);
-        if (smem > kMaxLds) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
-        p.lattice = reinterpret_cast<float *>(static_cast<char *>(workspace) + 256 + acc_list_bytes(B));
-        p.slab = (int64_t)noblank_lattice_floats(T, p.SP);
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int ch = C <= 256 ? (C + kWave - 1) / kWave : 0;    // phase-serial kernel: any supported shape
-    {   // the four-rows-per-wave kernel of the loss (noblank_r16.hpp) wherever it takes the shape: same chains, the
-        // gradient phase cut off after the row-normalised posteriors
-        int n4 = 0, n2 = 0;
-        const bool aligned = C % 2 == 0 && stride_t % 2 == 0 && stride_b % 2 == 0 && reinterpret_cast<uintptr_t>(x) % 8 == 0;
-        const size_t rsmem = r16_smem_bytes(T, p.SP, C);
-        if (K == 1 && T <= kPipeMaxT && !p.lattice && aligned && r16_shape(C, n4, n2) && p.SP <= 31 && rsmem <= kMaxLds) {
-            const dim3 grid(B), block(kThreads);
-#define CTC_R16_CASE(K, A, Bq) case K: return launch<noblank_r16_kernel<A, Bq, false>>(grid, block, rsmem, s, p);
-            switch (4 * n4 + n2) {
-                CTC_R16_CASE(1, 0, 1) CTC_R16_CASE(2, 0, 2) CTC_R16_CASE(4, 1, 0) CTC_R16_CASE(5, 1, 1)
-                CTC_R16_CASE(6, 1, 2) CTC_R16_CASE(8, 2, 0) CTC_R16_CASE(9, 2, 1) CTC_R16_CASE(10, 2, 2)
-                CTC_R16_CASE(12, 3, 0) CTC_R16_CASE(13, 3, 1) CTC_R16_CASE(14, 3, 2)
-                default: return launch<noblank_r16_kernel<4, 0, false>>(grid, block, rsmem, s, p);
-            }
-#undef CTC_R16_CASE
-        }
-    }
-    switch (K) {
-        case 1: return launch_noblank<1>(ch, smem, s, p);
-        case 2: return launch_noblank<2>(ch, smem, s, p);
-        default: return launch_noblank<4>(ch, smem, s, p);
-    }
+    if (!gamma) return CTC_AMD_ERR_BAD_ARGUMENT;
+    return noblank_run(x, stride_t, stride_b, labels, labels_i64, in_len, tgt_len, T, B, C, S, 0.f, 0.f, nll, nullptr,
+                       nullptr, workspace, stream, -1.f, CTC_AMD_F32, gamma);
 }
 
 #ifdef CTC_AMD_DIAGNOSTICS
@@ -799,5 +810,23 @@ extern "C" int ctc_amd_debug_chain_probe(int T, int SP, int waves_alive, int gri
     const size_t smem = r16_smem_bytes(T, SP, 158);
     return launch<r16_chain_probe_kernel>(dim3(grid), dim3(kThreads), smem, static_cast<hipStream_t>(stream), p,
                                           static_cast<unsigned long long *>(out), waves_alive, mode, chain_b);
+}
+
+// Diagnostic entry point (tests/test_noblank_plan.py), not part of include/ctc_amd.h: noblank_plan() for a call with
+// these properties, no device touched.  switches: bit 0 CTC_AMD_NOPIPE, 1 _NOXR, 2 _NOR16, 3 _NOPS, 4 _KM.
+// out[0..12] = family (NoblankFamily), n4, n2, nt, ps, ch, dual, K, glb, grid, LDS bytes, next_round, koff.
+extern "C" int ctc_amd_debug_noblank_plan(int T, int B, int C, int S, int dtype, int64_t stride_t, int64_t stride_b,
+                                          unsigned x_low, unsigned grad_low, int want_grad, int want_gamma, int smooth,
+                                          int cus, int switches, int64_t *out)
+{
+    if (!out || T < 1 || B < 1 || C < 1 || S < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
+    const NoblankSwitches sw = {(switches & 1) != 0, (switches & 2) != 0, (switches & 4) != 0, (switches & 8) != 0,
+                                (switches & 16) != 0, false, 0};
+    const NoblankPlan pl = noblank_plan({T, B, C, S, dtype, stride_t, stride_b, x_low, grad_low, want_grad != 0,
+                                         want_gamma != 0, smooth != 0, cus, sw});
+    const int64_t v[13] = {pl.family, pl.n4, pl.n2, pl.nt, pl.ps, pl.ch, pl.dual, pl.K, pl.glb, pl.grid,
+                           (int64_t)pl.lds, pl.next_round, pl.koff};
+    for (int i = 0; i < 13; ++i) out[i] = v[i];
+    return 0;
 }
 #endif

@@ -35,7 +35,7 @@ class _ShardFn(torch.autograd.Function):
         want = ctx.needs_input_grad[0]
         loss, _nll, grad = F._launch(variant, x, targets, in_len, tgt_len, want, batch_total, blank)
         ctx.grad = grad
-        ctx.meta = (variant, batch_total, blank)
+        ctx.meta = (variant, batch_total, blank, None)
         if want:
             ctx.save_for_backward(x, targets)
             ctx.lens = (in_len, tgt_len)

@@ -183,6 +183,13 @@ def _lengths(v, B, lo_name, device, hi, lo=1):
     return v.to(device=device, dtype=torch.int64, non_blocking=True).contiguous()
 
 
+def _placed(t, dev, dtype=None):
+    """`t` as a contiguous tensor on `dev` (of `dtype` if given): itself when it already is one"""
+    if (dtype is None or t.dtype is dtype) and t.device == dev and t.is_contiguous():
+        return t
+    return t.to(device=dev, dtype=dtype, non_blocking=True).contiguous()
+
+
 def _variant_of(targets):
     if targets.dim() == 2 and not targets.dtype.is_floating_point:
         return _lib.NOBLANK
@@ -223,13 +230,11 @@ def _launch(variant, x, targets, in_len, tgt_len, want_grad, batch_total, blank=
     if variant == _lib.BINARY:
         if tshape[2] != C:
             raise ValueError("ctc_amd: binary targets last dim %d != C %d" % (tshape[2], C))
-        tg = targets if (tdt is torch.float32 and targets.device == dev and targets.is_contiguous()) \
-            else targets.to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()
+        tg = _placed(targets, dev, torch.float32)
     else:
         if tdt is not torch.int32 and tdt is not torch.int64:
             targets = targets.long()
-        tg = targets if (targets.device == dev and targets.is_contiguous()) else \
-            targets.to(device=dev, non_blocking=True).contiguous()
+        tg = _placed(targets, dev)
     il = _lengths(in_len, B, "input_lengths", dev, T)
     tl = _lengths(tgt_len, B, "target_lengths", dev, S, lo=0 if variant == _lib.BLANK else 1)
     scale = 1.0 / (B if batch_total is None else int(batch_total))
@@ -296,8 +301,7 @@ def _scaled_grad(ctx, gout):
     ctx.grad = None                         # the buffer is handed to autograd exactly once
     if grad is None:                        # backward again (retain_graph): recompute
         x, targets = ctx.saved_tensors
-        variant, batch_total, blank = ctx.meta[:3]
-        smoothing = ctx.meta[3] if len(ctx.meta) > 3 else None
+        variant, batch_total, blank, smoothing = ctx.meta
         _, _, grad = _launch(variant, x, targets, ctx.lens[0], ctx.lens[1], True, batch_total, blank, smoothing)
     g = gout
     if g.dtype is not torch.float32 or g.device != grad.device or not g.is_contiguous() or g.requires_grad:
@@ -438,7 +442,7 @@ class CTCLoss(torch.autograd.Function):
         loss, nll, grad = _launch(variant, log_probs, targets, input_lengths, target_lengths, want,
                                   batch_total)
         ctx.grad = grad
-        ctx.meta = (variant, batch_total, 0)
+        ctx.meta = (variant, batch_total, 0, None)
         if want:
             ctx.save_for_backward(log_probs, targets)
             ctx.lens = (input_lengths, target_lengths)
@@ -478,6 +482,63 @@ def blank_ctc_loss(log_probs, targets, input_lengths, target_lengths, blank=0, b
     return _LossFn.apply(log_probs, targets, input_lengths, target_lengths, _lib.BLANK, batch_total, blank)
 
 
+def _readout_inputs(x, name, targets, in_len, tgt_len, variant):
+    """What the read-outs (best path, posteriors) do before their launch -> (xs, tg, il, tl, T, B, C, S, dev): float32
+    logits [T,B,C] on a HIP device, detached and with unit class stride; targets of `variant` and int64 lengths on that
+    device.  The blank read-outs refuse empty shapes here (target lengths may be 0); the no-blank and binary ones leave
+    that to the library, which answers with its own error."""
+    blank = variant == _lib.BLANK
+    _require_hip(x, name)
+    if x.dim() != 3 or x.dtype != torch.float32:
+        raise ValueError("ctc_amd: %s must be float32 [T,B,C]" % name)
+    T, B, C = x.shape
+    if blank and (T < 1 or B < 1 or C < 1):
+        raise ValueError("ctc_amd: empty %s %s" % (name, tuple(x.shape)))
+    dev = x.device
+    xs = x.detach()
+    if xs.stride(2) != 1:
+        xs = xs.contiguous()
+    if variant == _lib.BINARY:
+        if _variant_of(targets) != _lib.BINARY or targets.shape[0] != B or targets.shape[2] != C:
+            raise ValueError("ctc_amd: targets must be [B,S,C] float")
+        tg = _placed(targets, dev, torch.float32)
+    else:
+        if (blank and not isinstance(targets, torch.Tensor)) or _variant_of(targets) != _lib.NOBLANK \
+                or targets.shape[0] != B:
+            raise ValueError("ctc_amd: targets must be [B,S] integer")
+        if targets.dtype not in (torch.int32, torch.int64):
+            targets = targets.long()
+        tg = _placed(targets, dev)
+    S = tg.shape[1]
+    if blank and S < 1:
+        raise ValueError("ctc_amd: targets need at least one label column")
+    il = _lengths(in_len, B, "input_lengths", dev, T)
+    tl = _lengths(tgt_len, B, "target_lengths", dev, S, lo=0 if blank else 1)
+    return xs, tg, il, tl, T, B, C, S, dev
+
+
+def _readout(entry, variant, x, name, targets, in_len, tgt_len, width, out_dtype, extra=(), workspace=True):
+    """One read-out launch -> (out[B,T,width] or out[B,T] of out_dtype, per_sample[B] fp32).  `entry`: the C-ABI call
+    (x, strides, targets[, labels_i64], lengths, T, B, C, S, *extra, per-sample or main output as the header orders
+    them, workspace, stream); `width(S)`: last dimension of the main output, None for [B,T]."""
+    xs, tg, il, tl, T, B, C, S, dev = _readout_inputs(x, name, targets, in_len, tgt_len, variant)
+    w = width(S) if width else None
+    out = torch.empty((B, T) if w is None else (B, T, w), dtype=out_dtype, device=dev)
+    per = torch.empty(B, dtype=torch.float32, device=dev)
+    lab = () if variant == _lib.BINARY else (int(tg.dtype is torch.int64),)
+    # best paths: (path, score); posteriors: (nll, gamma)
+    outs = (out.data_ptr(), per.data_ptr()) if w is None else (per.data_ptr(), out.data_ptr())
+    with _on_device(dev):
+        stream = _stream_handle(dev)
+        ws = _workspace(variant, T, B, C, S, dev, stream).data_ptr() if workspace else None
+        rc = getattr(_lib.load(), entry)(xs.data_ptr(), xs.stride(0), xs.stride(1), tg.data_ptr(), *lab, il.data_ptr(),
+                                         tl.data_ptr(), T, B, C, S, *extra, *outs, ws, stream)
+    _lib.check(rc, entry)
+    if variant == _lib.BLANK and _VALIDATE:
+        check_status(dev)
+    return out, per
+
+
 def noblank_best_path(logits, targets, input_lengths, target_lengths):
     """Best (Viterbi) alignment on the no-blank lattice -> (path[B,T] int32, score[B]).
 
@@ -485,59 +546,16 @@ def noblank_best_path(logits, targets, input_lengths, target_lengths):
     ``t >= T_b`` or when no alignment exists; ``score[b]`` its log-probability.  Max-semiring
     twin of the loss recursion (NoBlankCTC.py:71-87); SURVEY 8(f) rank 1.
     """
-    _require_hip(logits, "logits")
-    if logits.dim() != 3 or logits.dtype != torch.float32:
-        raise ValueError("ctc_amd: logits must be float32 [T,B,C]")
-    T, B, C = logits.shape
-    dev = logits.device
-    xs = logits.detach()
-    if xs.stride(2) != 1:
-        xs = xs.contiguous()
-    if _variant_of(targets) != _lib.NOBLANK or targets.shape[0] != B:
-        raise ValueError("ctc_amd: targets must be [B,S] integer")
-    if targets.dtype not in (torch.int32, torch.int64):
-        targets = targets.long()
-    tg = targets.to(device=dev, non_blocking=True).contiguous()
-    S = tg.shape[1]
-    il = _lengths(input_lengths, B, "input_lengths", dev, T)
-    tl = _lengths(target_lengths, B, "target_lengths", dev, S)
-    path = torch.empty((B, T), dtype=torch.int32, device=dev)
-    score = torch.empty(B, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.load().ctc_amd_noblank_best_path(
-            xs.data_ptr(), xs.stride(0), xs.stride(1), tg.data_ptr(), int(tg.dtype == torch.int64),
-            il.data_ptr(), tl.data_ptr(), T, B, C, S, path.data_ptr(), score.data_ptr(), None,
-            _stream_handle(dev))
-    _lib.check(rc, "ctc_amd_noblank_best_path")
-    return path, score
+    return _readout("ctc_amd_noblank_best_path", _lib.NOBLANK, logits, "logits", targets, input_lengths, target_lengths,
+                    None, torch.int32, workspace=False)
 
 
 def binary_best_path(logits, targets, input_lengths, target_lengths):
     """Best (Viterbi) alignment on the lattice of the binary variant -> (path[B,T] int32, score[B]); ``targets`` [B,S,C]
     float label rows, ``path[b,t]`` the label ROW occupied at step t (-1 for ``t >= T_b`` or when no alignment exists).
     Max-semiring twin of NoBlankBinaryCTC's recursion (NoBlankBinaryCTC.py:72-95); SURVEY 8(f) rank 1."""
-    _require_hip(logits, "logits")
-    if logits.dim() != 3 or logits.dtype != torch.float32:
-        raise ValueError("ctc_amd: logits must be float32 [T,B,C]")
-    T, B, C = logits.shape
-    dev = logits.device
-    xs = logits.detach()
-    if xs.stride(2) != 1:
-        xs = xs.contiguous()
-    if _variant_of(targets) != _lib.BINARY or targets.shape[0] != B or targets.shape[2] != C:
-        raise ValueError("ctc_amd: targets must be [B,S,C] float")
-    tg = targets.detach().to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()
-    S = tg.shape[1]
-    il = _lengths(input_lengths, B, "input_lengths", dev, T)
-    tl = _lengths(target_lengths, B, "target_lengths", dev, S)
-    path = torch.empty((B, T), dtype=torch.int32, device=dev)
-    score = torch.empty(B, dtype=torch.float32, device=dev)
-    with _on_device(dev):
-        rc = _lib.load().ctc_amd_binary_best_path(xs.data_ptr(), xs.stride(0), xs.stride(1), tg.data_ptr(), il.data_ptr(),
-                                                  tl.data_ptr(), T, B, C, S, path.data_ptr(), score.data_ptr(), None,
-                                                  _stream_handle(dev))
-    _lib.check(rc, "ctc_amd_binary_best_path")
-    return path, score
+    return _readout("ctc_amd_binary_best_path", _lib.BINARY, logits, "logits", targets, input_lengths, target_lengths,
+                    None, torch.int32, workspace=False)
 
 
 def blank_best_path(log_probs, targets, input_lengths, target_lengths, blank=0):
@@ -548,41 +566,8 @@ def blank_best_path(log_probs, targets, input_lengths, target_lengths, blank=0):
     (s-1)//2 of targets[b]) for ``t < T_b``, -1 beyond ``T_b`` and for samples with no alignment; ``score[b]`` the
     log-probability of that alignment (-inf when none exists).  include/ctc_amd.h: ctc_amd_blank_best_path.
     """
-    _require_hip(log_probs, "log_probs")
-    if log_probs.dim() != 3 or log_probs.dtype != torch.float32:
-        raise ValueError("ctc_amd: log_probs must be float32 [T,B,C]")
-    T, B, C = log_probs.shape
-    if T < 1 or B < 1 or C < 1:
-        raise ValueError("ctc_amd: empty log_probs %s" % (tuple(log_probs.shape),))
-    dev = log_probs.device
-    xs = log_probs.detach()
-    if xs.stride(2) != 1:
-        xs = xs.contiguous()
-    if not isinstance(targets, torch.Tensor) or targets.dim() != 2 or targets.dtype.is_floating_point \
-            or targets.shape[0] != B:
-        raise ValueError("ctc_amd: targets must be [B,S] integer")
-    if targets.dtype not in (torch.int32, torch.int64):
-        targets = targets.long()
-    tg = targets if (targets.device == dev and targets.is_contiguous()) else \
-        targets.to(device=dev, non_blocking=True).contiguous()
-    S = tg.shape[1]
-    if S < 1:
-        raise ValueError("ctc_amd: targets need at least one label column")
-    il = _lengths(input_lengths, B, "input_lengths", dev, T)
-    tl = _lengths(target_lengths, B, "target_lengths", dev, S, lo=0)
-    path = torch.empty((B, T), dtype=torch.int32, device=dev)
-    score = torch.empty(B, dtype=torch.float32, device=dev)
-    with _on_device(dev):
-        stream = _stream_handle(dev)
-        ws = _workspace(_lib.BLANK, T, B, C, S, dev, stream)
-        rc = _lib.load().ctc_amd_blank_best_path(
-            xs.data_ptr(), xs.stride(0), xs.stride(1), tg.data_ptr(), int(tg.dtype is torch.int64),
-            il.data_ptr(), tl.data_ptr(), T, B, C, S, int(blank), path.data_ptr(), score.data_ptr(), ws.data_ptr(),
-            stream)
-    _lib.check(rc, "ctc_amd_blank_best_path")
-    if _VALIDATE:
-        check_status(dev)
-    return path, score
+    return _readout("ctc_amd_blank_best_path", _lib.BLANK, log_probs, "log_probs", targets, input_lengths,
+                    target_lengths, None, torch.int32, extra=(int(blank),))
 
 
 def blank_forced_align(log_probs, targets, input_lengths, target_lengths, blank=0):
@@ -615,41 +600,8 @@ def blank_posteriors(log_probs, targets, input_lengths, target_lengths, blank=0)
     differentiable.  ``gamma[b, t, path[b, t]]`` with ``blank_best_path``'s path is the confidence of each aligned
     frame.  include/ctc_amd.h: ctc_amd_blank_posteriors.
     """
-    _require_hip(log_probs, "log_probs")
-    if log_probs.dim() != 3 or log_probs.dtype != torch.float32:
-        raise ValueError("ctc_amd: log_probs must be float32 [T,B,C]")
-    T, B, C = log_probs.shape
-    if T < 1 or B < 1 or C < 1:
-        raise ValueError("ctc_amd: empty log_probs %s" % (tuple(log_probs.shape),))
-    dev = log_probs.device
-    xs = log_probs.detach()
-    if xs.stride(2) != 1:
-        xs = xs.contiguous()
-    if not isinstance(targets, torch.Tensor) or targets.dim() != 2 or targets.dtype.is_floating_point \
-            or targets.shape[0] != B:
-        raise ValueError("ctc_amd: targets must be [B,S] integer")
-    if targets.dtype not in (torch.int32, torch.int64):
-        targets = targets.long()
-    tg = targets if (targets.device == dev and targets.is_contiguous()) else \
-        targets.to(device=dev, non_blocking=True).contiguous()
-    S = tg.shape[1]
-    if S < 1:
-        raise ValueError("ctc_amd: targets need at least one label column")
-    il = _lengths(input_lengths, B, "input_lengths", dev, T)
-    tl = _lengths(target_lengths, B, "target_lengths", dev, S, lo=0)
-    gamma = torch.empty((B, T, 2 * S + 1), dtype=torch.float32, device=dev)
-    nll = torch.empty(B, dtype=torch.float32, device=dev)
-    with _on_device(dev):
-        stream = _stream_handle(dev)
-        ws = _workspace(_lib.BLANK, T, B, C, S, dev, stream)
-        rc = _lib.load().ctc_amd_blank_posteriors(
-            xs.data_ptr(), xs.stride(0), xs.stride(1), tg.data_ptr(), int(tg.dtype is torch.int64),
-            il.data_ptr(), tl.data_ptr(), T, B, C, S, int(blank), nll.data_ptr(), gamma.data_ptr(), ws.data_ptr(),
-            stream)
-    _lib.check(rc, "ctc_amd_blank_posteriors")
-    if _VALIDATE:
-        check_status(dev)
-    return gamma, nll
+    return _readout("ctc_amd_blank_posteriors", _lib.BLANK, log_probs, "log_probs", targets, input_lengths,
+                    target_lengths, lambda S: 2 * S + 1, torch.float32, extra=(int(blank),))
 
 
 def noblank_posteriors(logits, targets, input_lengths, target_lengths):
@@ -658,61 +610,16 @@ def noblank_posteriors(logits, targets, input_lengths, target_lengths):
     ``gamma[b,t,l]`` = P(label position l at step t | logits, targets): the soft alignment whose
     class-scatter is the loss gradient; rows sum to 1 for ``t < T_b``.  SURVEY 8(f) rank 1.
     """
-    _require_hip(logits, "logits")
-    if logits.dim() != 3 or logits.dtype != torch.float32:
-        raise ValueError("ctc_amd: logits must be float32 [T,B,C]")
-    T, B, C = logits.shape
-    dev = logits.device
-    xs = logits.detach()
-    if xs.stride(2) != 1:
-        xs = xs.contiguous()
-    if _variant_of(targets) != _lib.NOBLANK or targets.shape[0] != B:
-        raise ValueError("ctc_amd: targets must be [B,S] integer")
-    if targets.dtype not in (torch.int32, torch.int64):
-        targets = targets.long()
-    tg = targets.to(device=dev, non_blocking=True).contiguous()
-    S = tg.shape[1]
-    il = _lengths(input_lengths, B, "input_lengths", dev, T)
-    tl = _lengths(target_lengths, B, "target_lengths", dev, S)
-    gamma = torch.empty((B, T, S), dtype=torch.float32, device=dev)
-    nll = torch.empty(B, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        ws = _workspace(_lib.NOBLANK, T, B, C, S, dev)
-        rc = _lib.load().ctc_amd_noblank_posteriors(
-            xs.data_ptr(), xs.stride(0), xs.stride(1), tg.data_ptr(), int(tg.dtype == torch.int64),
-            il.data_ptr(), tl.data_ptr(), T, B, C, S, nll.data_ptr(), gamma.data_ptr(), ws.data_ptr(),
-            _stream_handle(dev))
-    _lib.check(rc, "ctc_amd_noblank_posteriors")
-    return gamma, nll
+    return _readout("ctc_amd_noblank_posteriors", _lib.NOBLANK, logits, "logits", targets, input_lengths,
+                    target_lengths, lambda S: S, torch.float32)
 
 
 def binary_posteriors(logits, targets, input_lengths, target_lengths):
     """Per-step posteriors of the binary (multi-hot) lattice -> (gamma[B,T,S], nll[B]): ``gamma[b,t,l]`` =
     P(target row l at step t | logits, targets), rows sum to 1 for ``t < T_b``.  SURVEY 8(f) rank 1, the sibling of
     ``noblank_posteriors``; shapes of the pipelined binary kernel (S <= 64, T <= 168, C <= 256)."""
-    _require_hip(logits, "logits")
-    if logits.dim() != 3 or logits.dtype != torch.float32:
-        raise ValueError("ctc_amd: logits must be float32 [T,B,C]")
-    T, B, C = logits.shape
-    dev = logits.device
-    xs = logits.detach()
-    if xs.stride(2) != 1:
-        xs = xs.contiguous()
-    if _variant_of(targets) != _lib.BINARY or targets.shape[0] != B or targets.shape[2] != C:
-        raise ValueError("ctc_amd: targets must be [B,S,C] float")
-    tg = targets.to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()
-    S = tg.shape[1]
-    il = _lengths(input_lengths, B, "input_lengths", dev, T)
-    tl = _lengths(target_lengths, B, "target_lengths", dev, S)
-    gamma = torch.empty((B, T, S), dtype=torch.float32, device=dev)
-    nll = torch.empty(B, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        ws = _workspace(_lib.BINARY, T, B, C, S, dev)
-        rc = _lib.load().ctc_amd_binary_posteriors(
-            xs.data_ptr(), xs.stride(0), xs.stride(1), tg.data_ptr(), il.data_ptr(), tl.data_ptr(), T, B, C, S,
-            nll.data_ptr(), gamma.data_ptr(), ws.data_ptr(), _stream_handle(dev))
-    _lib.check(rc, "ctc_amd_binary_posteriors")
-    return gamma, nll
+    return _readout("ctc_amd_binary_posteriors", _lib.BINARY, logits, "logits", targets, input_lengths,
+                    target_lengths, lambda S: S, torch.float32)
 
 
 def dedup_multihot_targets(rows, exact_rows=False):
