@@ -1698,6 +1698,8 @@ static int run_blank(BlankParams &p, hipStream_t s)
 
 }  // namespace ctc
 
+#include "blank_wide.hpp"
+
 using namespace ctc;
 
 extern "C" int ctc_amd_blank_loss_grad(const float *log_probs, int64_t stride_t, int64_t stride_b,
@@ -1711,8 +1713,11 @@ extern "C" int ctc_amd_blank_loss_grad(const float *log_probs, int64_t stride_t,
     if (!log_probs || !targets || !in_len || !tgt_len || !nll || !loss || !workspace) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (T < 1 || B < 1 || C < 1 || S < 1 || blank < 0 || blank >= C) return CTC_AMD_ERR_BAD_ARGUMENT;
     const int ns = 2 * S + 1;
-    if (ns > kWave * 8) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;                 // S <= 255
-    if ((size_t)kGradWaves * (C + 4 + 2 * kWave * 8) * sizeof(float) > kMaxLds) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
+    if (S > 1023) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;                       // 2S+1 <= 2047 states: four waves of 512
+    const bool wide = ns > kWave * 8;                                         // S > 255: blank_wide.hpp
+    const int nsp = wide ? (ns + kWideSpan - 1) / kWideSpan * kWideSpan : kWave * 8;
+    // a gradient wave's occ[C] beside gam[] and the state table of the padded width
+    if ((size_t)kGradWaves * (C + 4 + 2 * nsp) * sizeof(float) > kMaxLds) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
     BlankParams p;
     p.lp = log_probs; p.st = stride_t; p.sb = stride_b;
     p.tgt = targets; p.tgt64 = targets_i64;
@@ -1722,6 +1727,7 @@ extern "C" int ctc_amd_blank_loss_grad(const float *log_probs, int64_t stride_t,
     p.nll = nll; p.loss = loss; p.grad = grad;
     p.counter = static_cast<unsigned *>(workspace);
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (wide) return run_blank_wide(p, s);                                    // whatever ctc_amd_blank_set_schedule says
     if (ns <= kWave * 2) return run_blank<2>(p, s);
     if (ns <= kWave * 4) return run_blank<4>(p, s);
     return run_blank<8>(p, s);

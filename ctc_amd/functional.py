@@ -134,9 +134,13 @@ def collective_gate(variant, batch, device=None, launch_stream=None, timeout_us=
     return True
 
 
+BLANK_MAX_LABELS = 1023            # ctc_amd_blank_loss_grad: S <= 1023; the blank read-outs stop at 255 (include/ctc_amd.h)
+
+
 def set_blank_schedule(mode):
     """-1: the library chooses (default); 1 / 0: force / forbid the persistent blank-CTC launch; 2: force it with the
-    worker pool gathering the emission rows."""
+    worker pool gathering the emission rows.  Targets of more than 255 label columns always take the wide
+    three-launch path, whatever is set here."""
     _lib.check(_lib.load().ctc_amd_blank_set_schedule(int(mode)), "ctc_amd_blank_set_schedule")
 
 
@@ -288,6 +292,10 @@ def _launch(variant, x, targets, in_len, tgt_len, want_grad, batch_total, blank=
                 xs.data_ptr(), st, sb, tg.data_ptr(), int(tg.dtype is torch.int64),
                 il.data_ptr(), tl.data_ptr(), T, B, C, S, int(blank), scale, scale,
                 op, lp_, gp, ws.data_ptr(), stream)
+            if rc == _lib.ERR_UNSUPPORTED_SHAPE and S > BLANK_MAX_LABELS:
+                raise _lib.CtcAmdError(
+                    "ctc_amd: the blank CTC loss takes targets of at most %d label columns (2S+1 <= %d lattice states), "
+                    "got S=%d" % (BLANK_MAX_LABELS, 2 * BLANK_MAX_LABELS + 1, S))
             if rc:
                 _lib.check(rc, "ctc_amd_blank_loss_grad")
     if _VALIDATE:
@@ -478,7 +486,8 @@ def binary_ctc_loss(logits, targets, input_lengths, target_lengths, batch_total=
 def blank_ctc_loss(log_probs, targets, input_lengths, target_lengths, blank=0, batch_total=None):
     """-> (loss, nll[B]); torch.nn.CTCLoss(blank, reduction='mean', zero_infinity=False)
     semantics (models/layers/AsyncTFCriterion.py:198): log_probs are normalised
-    log-probabilities, loss = mean_b(nll_b / max(L_b,1))."""
+    log-probabilities, loss = mean_b(nll_b / max(L_b,1)).  ``targets`` [B,S] with S <= 1023 label columns
+    (CtcAmdError beyond); more than 255 columns take the wide lattice path of the library (several waves per chain)."""
     return _LossFn.apply(log_probs, targets, input_lengths, target_lengths, _lib.BLANK, batch_total, blank)
 
 
@@ -564,7 +573,8 @@ def blank_best_path(log_probs, targets, input_lengths, target_lengths, blank=0):
     Same inputs as ``blank_ctc_loss``: ``log_probs`` [T,B,C] normalised log-probabilities (used as given),
     ``targets`` [B,S] int32/int64.  ``path[b,t]`` is the extended-label STATE s_t (even = blank, odd s = label
     (s-1)//2 of targets[b]) for ``t < T_b``, -1 beyond ``T_b`` and for samples with no alignment; ``score[b]`` the
-    log-probability of that alignment (-inf when none exists).  include/ctc_amd.h: ctc_amd_blank_best_path.
+    log-probability of that alignment (-inf when none exists).  S <= 255 label columns: the read-outs did not follow
+    the loss to the wide lattice (S <= 1023) and raise CtcAmdError beyond.  include/ctc_amd.h: ctc_amd_blank_best_path.
     """
     return _readout("ctc_amd_blank_best_path", _lib.BLANK, log_probs, "log_probs", targets, input_lengths,
                     target_lengths, None, torch.int32, extra=(int(blank),))
@@ -576,7 +586,8 @@ def blank_forced_align(log_probs, targets, input_lengths, target_lengths, blank=
 
     ``tokens[b,t]`` is the class of the best path's state at frame t (``blank`` or the target label), -1 beyond
     ``T_b`` / without an alignment; ``frame_scores[b,t] = log_probs[t,b,tokens[b,t]]`` (0 where tokens is -1), so
-    that their sum over t in order is ``blank_best_path``'s score.  Derived on the device from the path."""
+    that their sum over t in order is ``blank_best_path``'s score.  Derived on the device from the path, so S <= 255
+    label columns as there (the loss itself takes up to 1023)."""
     path, _ = blank_best_path(log_probs, targets, input_lengths, target_lengths, blank)
     dev = path.device
     tg = targets.to(device=dev, dtype=torch.int64)
@@ -598,7 +609,8 @@ def blank_posteriors(log_probs, targets, input_lengths, target_lengths, blank=0)
     (even s = blank, odd s = label (s-1)//2 of targets[b]); rows sum to 1 for ``t < T_b``, and are 0 for ``t >= T_b``,
     for ``s > 2 L_b`` and for samples with no alignment (``nll`` +inf, as ``blank_ctc_loss`` reports it).  Not
     differentiable.  ``gamma[b, t, path[b, t]]`` with ``blank_best_path``'s path is the confidence of each aligned
-    frame.  include/ctc_amd.h: ctc_amd_blank_posteriors.
+    frame.  S <= 255 label columns (CtcAmdError beyond; the loss itself takes up to 1023).
+    include/ctc_amd.h: ctc_amd_blank_posteriors.
     """
     return _readout("ctc_amd_blank_posteriors", _lib.BLANK, log_probs, "log_probs", targets, input_lengths,
                     target_lengths, lambda S: 2 * S + 1, torch.float32, extra=(int(blank),))

@@ -33,7 +33,7 @@ extern "C" {
 #define CTC_AMD_ABI_VERSION 2
 
 #define CTC_AMD_ERR_BAD_ARGUMENT      (-1)  /* null pointer, non-positive size ... */
-#define CTC_AMD_ERR_UNSUPPORTED_SHAPE (-2)  /* S > 256 (255 for blank-CTC); binary: T*S beyond LDS */
+#define CTC_AMD_ERR_UNSUPPORTED_SHAPE (-2)  /* S > 256 (blank-CTC: 1023 for the loss, 255 for its read-outs); binary: T*S beyond LDS */
 #define CTC_AMD_ERR_CODE_OVERFLOW     (-3)  /* target dedup in the reference's int32 row codes with C > 64: the
                                              * reference raises OverflowError there (2**o at o >= 64) */
 
@@ -134,6 +134,13 @@ int ctc_amd_binary_loss_grad(const float *x, int64_t stride_t, int64_t stride_b,
  *   nll   [B]  out: un-normalised negative log-likelihood (+inf if infeasible)
  *   loss  [1]  out: loss_scale * sum_b nll[b] / max(L_b,1)
  *   grad  [T,B,C] out or NULL: (exp(lp) - occupancy) * grad_scale / max(L_b,1)
+ * 1 <= S <= 1023 label columns (2S+1 <= 2047 lattice states; CTC_AMD_ERR_UNSUPPORTED_SHAPE beyond, and when C no
+ * longer fits beside the padded lattice row in a gradient wave's LDS: 4 (C + 2 NSP) floats <= 160 KB, NSP = 512 for
+ * S <= 255).  Up to 255 labels a chain is one wave; 256..1023 labels take the WIDE path: three launches, a chain
+ * spread over 2..4 waves of one workgroup (512 states each, NSP = 512 ceil((2S+1)/512)) that hand their edge states
+ * on through LDS with one workgroup barrier per step -- no polling, so no bounded wait and no status bit there;
+ * ctc_amd_blank_set_schedule() does not apply to it.  Everything else in this comment holds for both.  The read-outs
+ * below (best path, posteriors) stop at S = 255.
  * Long sequences (T >= 256) on batches of #CUs/11..#CUs/2 samples with >= 4 lattice states per lane and
  * B*C >= 16384 (BASELINE config 5 and its neighbourhood) run as ONE persistent
  * launch of at most one workgroup per CU in which workgroups wait for each other (bounded: a wait
@@ -145,6 +152,10 @@ int ctc_amd_binary_loss_grad(const float *x, int64_t stride_t, int64_t stride_b,
  * at every tested shape (8e-6 at BASELINE config 5, where torch's fp32 CPU kernel is 1.9e-4 off), but the un-normalised
  * per-sample occupancies behind it -- grad * max(L_b,1) / grad_scale -- are only good to ~1e-2 at T = 2000 (7e-3
  * measured).  A caller that rescales the gradient per sample by factors >> 1 inherits that.
+ * Wide path (S > 255): the same arithmetic step for step, plus one exact cross-wave sum at the end.  Its accuracy has not
+ * been measured on a device yet; the tests hold its batch-mean gradient to twice the error of torch's own fp32 CPU kernel
+ * against float64 on the same inputs (1.1e-6 .. 4.9e-6 on the tested shapes up to T = 1250, S = 1023), and never looser
+ * than the narrow path's bound.
  */
 int ctc_amd_blank_loss_grad(const float *log_probs, int64_t stride_t, int64_t stride_b,
                             const void *targets, int targets_i64,
@@ -231,7 +242,8 @@ int ctc_amd_binary_best_path(const float *x, int64_t stride_t, int64_t stride_b,
  *         v(2L) > v(2L-1), else 2L-1; 0 when L = 0), -1 for t >= T_b and for samples with no alignment
  *   score [B]   out: v of the final state (-inf: no alignment -- too short for L plus its adjacent repeats)
  * workspace: at least ctc_amd_workspace_bytes(CTC_AMD_BLANK, T, B, C, S) bytes; the 256-byte header is left alone
- * except for status bit 8.  S <= 255, any T (back-pointers beyond LDS go to the workspace). */
+ * except for status bit 8.  S <= 255 (CTC_AMD_ERR_UNSUPPORTED_SHAPE beyond: the loss's wide path up to S = 1023 has no
+ * read-out twin), any T (back-pointers beyond LDS go to the workspace). */
 int ctc_amd_blank_best_path(const float *log_probs, int64_t stride_t, int64_t stride_b,
                             const void *targets, int targets_i64,
                             const int64_t *in_len, const int64_t *tgt_len,
@@ -254,7 +266,8 @@ int ctc_amd_blank_best_path(const float *log_probs, int64_t stride_t, int64_t st
  * nll), so gamma keeps its resolution at long T: within 5e-4 of float64 at T = 2000 (the loss's occupancies: ~1e-2).
  * workspace: at least ctc_amd_workspace_bytes(CTC_AMD_BLANK, T, B, C, S) bytes; only the lattice areas behind the
  * 256-byte header are written (not the loss's state tables and hand-off words behind them; the header is left alone
- * except for status bit 16).  S <= 255 (CTC_AMD_ERR_UNSUPPORTED_SHAPE beyond), any T.  Deterministic. */
+ * except for status bit 16).  S <= 255 (CTC_AMD_ERR_UNSUPPORTED_SHAPE beyond, also where the loss itself goes on to
+ * S = 1023), any T.  Deterministic. */
 int ctc_amd_blank_posteriors(const float *log_probs, int64_t stride_t, int64_t stride_b,
                              const void *targets, int targets_i64,
                              const int64_t *in_len, const int64_t *tgt_len,
