@@ -5,6 +5,7 @@
 namespace ctc {
 size_t noblank_extra_workspace(int T, int B, int C, int S);   // noblank.hip
 int blank_sync_ints(int T, int B);                              // blank.hip
+size_t blank_padded_states(int S);                              // blank.hip
 }
 
 extern "C" int ctc_amd_abi_version(void) { return CTC_AMD_ABI_VERSION; }
@@ -28,11 +29,8 @@ extern "C" size_t ctc_amd_workspace_bytes(int variant, int T, int B, int C, int 
     size_t bytes = 256;
     if (variant == CTC_AMD_BLANK) {
         // emissions, alpha, beta lattices [B][T][NSP] fp32 + three [B][NSP] int state tables + [B] int2 lengths
-        // + the hand-off counters of the fused schedule; NSP = 2S+1 padded to 64*K states (K = 2, 4, 8
-        // states per lane) up to S = 255, see blank.hip
-        const size_t ns = 2 * (size_t)S + 1;
-        // beyond 255 labels (blank_wide.hpp): W waves of 512 states, 512 W -- not the next power of two
-        const size_t nsp = ns <= 128 ? 128 : (ns <= 256 ? 256 : (ns + 511) / 512 * 512);
+        // + the hand-off counters of the fused schedule (blank_layout, blank.hip)
+        const size_t nsp = ctc::blank_padded_states(S);
         bytes += 3 * (size_t)B * (size_t)T * nsp * sizeof(float) + 3 * (size_t)B * nsp * sizeof(int) +
                  (2 * (((size_t)B + 63) & ~(size_t)63) + (size_t)ctc::blank_sync_ints(T, B)) * sizeof(int);
     }

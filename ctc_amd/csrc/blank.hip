@@ -38,8 +38,6 @@
 //    (about a second); a wait that runs out raises the status word and poisons its outputs with NaN.
 //    Cross-XCD visibility (each XCD has its own L2): lattice rows are written with agent-scope
 //    (sc1, write-through) stores and read with sc1 loads; the counters are agent-scope atomics.
-#include <cstdlib>
-
 #include "common.hpp"
 #include <atomic>
 #include <cstdlib>
@@ -71,35 +69,8 @@ constexpr size_t kFusedLdsHead = 64; // bytes of LDS flags in front of the rings
 constexpr int kPastLattice = 1 << 30; // a byte offset beyond any sample's lattice (out-of-range buffer accesses are dropped)
 // Persistent launch: only every other lattice row goes to memory -- alpha on even rows, beta' on odd rows -- and the
 // worker of a row PAIR (2P, 2P+1) redoes one forward and one backward step from the two log_probs rows it holds
-// anyway (0.2 GB less traffic at B=64 T=2000 S=100, and half the chains' stores).
-#ifdef CTC_X_FULL_LATTICE
-constexpr bool kHalfLattice = false;
-#else
-constexpr bool kHalfLattice = true;
-#endif
-// Persistent launch, float4 loaders: every log_probs row is gathered ONCE.  The loaders of a direction gather the first
-// half of its steps from log_probs; its CHAIN, which has each emission row in registers anyway, leaves it in the
-// workspace (p.em, the three-launch schedule's emission table; plain stores -- producer and consumer are waves of ONE
-// workgroup, so the CU's L2 is the meeting point); the loaders of the OTHER direction -- for which these rows are the
-// second half -- read the 4 K bytes per lane back instead of whole log_probs rows (0.3 GB less traffic at B=64 T=2000
-// C=1000 S=100, and light loaders while the row workers use the memory system).
-// Tried on the way: a storer wave per direction (ten waves per workgroup leave 168 VGPRs per wave, the loaders' twelve
-// rows in flight spill: 860 us); the loaders storing their own rows (one more line request per row on the busiest
-// unit of the phase: first half 50 instead of 41 us per 256 steps); one loader loop with a branch per row (the
-// compiler must then assume the fewest memory operations behind a row it waits for: three rows in flight, 730 us).
-// (Also measured and removed again: the chains of this launch on (mantissa, exponent) states as in noblank_r16.hpp --
-// 52 plain VALU operations per step at four states per lane instead of twelve transcendentals + 40, the loaders
-// splitting each emission into (2^frac, floor), lattice rows still stored as log2 values: correct, and 463 against
-// 430 us on the same device.  The chain's own time per step did not move (0.155 us: it is not bound by its arithmetic
-// but by the per-group hand-offs and the landing window of its stores) and it waited longer for its loaders.)
-// MEASURED, NOT ON: 1.94 instead of 2.13 GB and a second half of the chains at 36-46 instead of 44-67 us per 256 steps,
-// but the extra store per step sits on the busiest unit of the first half (the sample's CU issues every log_probs
-// line request of six loaders): the chains cross at 209 instead of 170 us and the launch takes 459 against 447 us.
-#ifdef CTC_X_GATHER_ONCE
-constexpr bool kGatherOnce = true;
-#else
-constexpr bool kGatherOnce = false;
-#endif
+// anyway (0.2 GB less traffic at B=64 T=2000 S=100, and half the chains' stores).  What was built beside this and
+// lost (the whole lattice in memory, every log_probs row gathered once, (mantissa, exponent) chains) is in DESIGN.md 3.3.
 
 // Persistent launch, float4 rows: the IDLE WORKER POOL gathers the emission rows.  Until the chains cross in the middle
 // of the samples the row workers have nothing to do (38 % of the launch at B=64 T=2000: 192 CUs idle, HBM a third
@@ -268,28 +239,37 @@ __device__ __forceinline__ void blank_classes(const BlankParams &p, int b, int n
     __syncthreads();
 }
 
+// a log-probability as an emission in the lattice's log2 units.  States beyond the sample's n carry kNegB instead; that
+// choice stays at the call site, in front of the load: the class of such a state must not cost a memory operation
+__device__ __forceinline__ float blank_emission(float x) { return fmaxf(x * kLog2e, kNegB); }
+
+// the table entry of state s, from the classes in LDS: its class, the next state with that class, and whether s is
+// the first state that carries it
+__device__ __forceinline__ void blank_table_entry(const BlankParams &p, int b, int n, int s, const int *s_cls)
+{
+    const int c = s_cls[s];
+    p.cls[b * p.NSP + s] = c;
+    // one pass over the labels, no early exit: the LDS reads are independent (and the same address for
+    // every thread), so they pipeline -- two scans that stop at the first match cost 14 us at L = 100
+    const bool label = s < n && (s & 1);
+    int nx = -1, fi = label ? 1 : 0;
+    if (label) {
+#pragma unroll 8
+        for (int s2 = 1; s2 < n; s2 += 2) {
+            const bool same = s_cls[s2] == c;
+            if (same && s2 < s) fi = 0;
+            if (same && s2 > s && nx < 0) nx = s2;
+        }
+    }
+    p.nxt[b * p.NSP + s] = nx;
+    p.first[b * p.NSP + s] = fi;
+}
+
 // per-sample state tables + (effective length, target length), from the classes in LDS
 __device__ __forceinline__ void blank_tables(const BlankParams &p, int b, int Tb, int L, const int *s_cls)
 {
     const int n = 2 * L + 1;
-    for (int s = threadIdx.x; s < p.NSP; s += blockDim.x) {
-        const int c = s_cls[s];
-        p.cls[b * p.NSP + s] = c;
-        // one pass over the labels, no early exit: the LDS reads are independent (and the same address for
-        // every thread), so they pipeline -- two scans that stop at the first match cost 14 us at L = 100
-        const bool label = s < n && (s & 1);
-        int nx = -1, fi = label ? 1 : 0;
-        if (label) {
-#pragma unroll 8
-            for (int s2 = 1; s2 < n; s2 += 2) {
-                const bool same = s_cls[s2] == c;
-                if (same && s2 < s) fi = 0;
-                if (same && s2 > s && nx < 0) nx = s2;
-            }
-        }
-        p.nxt[b * p.NSP + s] = nx;
-        p.first[b * p.NSP + s] = fi;
-    }
+    for (int s = threadIdx.x; s < p.NSP; s += blockDim.x) blank_table_entry(p, b, n, s, s_cls);
     if (threadIdx.x == 0) {                                  // an alignment needs one step per label plus a blank
         int need = L;                                        // between every two equal neighbours
         for (int l = 1; l < L; ++l) need += s_cls[2 * l + 1] == s_cls[2 * l - 1] ? 1 : 0;
@@ -312,7 +292,7 @@ __global__ __launch_bounds__(256) void blank_gather_kernel(BlankParams p, int ro
     for (int t = t_begin; t < t_end; ++t) {
         const float *row = p.lp + (int64_t)t * p.st + (int64_t)b * p.sb;
         float *out = p.em + ((int64_t)b * p.T + t) * p.NSP;
-        for (int s = tid; s < p.NSP; s += blockDim.x) out[s] = s < n ? fmaxf(row[s_cls[s]] * kLog2e, kNegB) : kNegB;
+        for (int s = tid; s < p.NSP; s += blockDim.x) out[s] = s < n ? blank_emission(row[s_cls[s]]) : kNegB;
     }
 }
 
@@ -338,16 +318,14 @@ __device__ __forceinline__ float lse2_2(float a, float b)
     return m + __builtin_amdgcn_logf(1.0f + __builtin_amdgcn_exp2f(-fabsf(a - b)));
 }
 
-// per-lane constants of a chain: which of its K states are real, and which take the s-2 edge
+// per-lane constants of a chain: which of the lane's K states, s0 on, take the s-2 edge
 template <int K, bool FWD>
-__device__ __forceinline__ void blank_state_flags(const BlankParams &p, int b, int n, bool (&skip)[K], bool (&valid)[K])
+__device__ __forceinline__ void blank_state_flags(const BlankParams &p, int b, int n, int s0, bool (&skip)[K])
 {
-    const int s0 = lane_id() * K;
     const int *cls = p.cls + b * p.NSP;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         const int s = s0 + k;
-        valid[k] = s < n;
         // alpha: from s-2 when l'_s is a label differing from l'_{s-2};  beta: from s+2 likewise
         const int s2 = FWD ? s - 2 : s + 2;
         skip[k] = (s & 1) && s2 >= 0 && s2 < n && cls[s] != cls[s2];
@@ -431,11 +409,10 @@ __device__ __forceinline__ void blank_step(float (&a)[K], const float (&e)[K], c
     }
 }
 
-// the first row: the two entry states only
+// the first row: the two entry states only (s0: the lane's first state)
 template <int K, bool FWD>
-__device__ __forceinline__ void blank_first(float (&a)[K], const float (&e0)[K], int n)
+__device__ __forceinline__ void blank_first(float (&a)[K], const float (&e0)[K], int n, int s0)
 {
-    const int s0 = lane_id() * K;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         const int s = s0 + k;
@@ -453,8 +430,8 @@ __device__ __forceinline__ void blank_chain(const BlankParams &p, int b, int Tb,
     const int lane = lane_id(), s0 = lane * K, n = 2 * L + 1;
     const float *em = p.em + (int64_t)b * p.T * p.NSP + s0;
     float *out = (FWD ? p.al : p.be) + (int64_t)b * p.T * p.NSP + s0;
-    bool skip[K], valid[K];
-    blank_state_flags<K, FWD>(p, b, n, skip, valid);
+    bool skip[K];
+    blank_state_flags<K, FWD>(p, b, n, s0, skip);
     auto row_of = [&](int i) { return FWD ? i : Tb - 1 - i; };
     auto fetch = [&](float (&dst)[K], int i) {
         const float *r = em + (int64_t)row_of(i < Tb ? i : Tb - 1) * p.NSP;
@@ -470,7 +447,7 @@ __device__ __forceinline__ void blank_chain(const BlankParams &p, int b, int Tb,
     {
         float e0[K];
         fetch(e0, 0);
-        blank_first<K, FWD>(a, e0, n);
+        blank_first<K, FWD>(a, e0, n, s0);
         store(0);
     }
     int i = 1;
@@ -497,7 +474,8 @@ __device__ __forceinline__ void blank_chain(const BlankParams &p, int b, int Tb,
 
 // ---- fused schedule, the sample's workgroup -------------------------------------------------------
 // LDS of a chain workgroup: flags[4 d + j] rows finished by loader j of direction d (0 alpha,
-// 1 beta), flags[4 d + 3] steps consumed by that chain; then the two rings of kRingRows/K emission
+// 1 beta), flags[4 d + 3] steps consumed by that chain, flags[12 + d] chunks of pool-gathered rows
+// the scout of that direction has seen complete; then the two rings of kRingRows/K emission
 // rows of NSP floats, row i of a direction in slot i mod ring; then a row of staging per loader.
 struct FusedLds {
     int *flags;
@@ -575,7 +553,7 @@ __device__ __forceinline__ void blank_loader(const BlankParams &p, int b, int Tb
                 if (rr - R + 1 > seen && !lds_wait_ge(p, consumed, rr - R + 1, seen)) return;   // slot still being read
                 float e[K];
 #pragma unroll
-                for (int k = 0; k < K; ++k) e[k] = s0 + k < n ? fmaxf(x[q][k] * kLog2e, kNegB) : kNegB;
+                for (int k = 0; k < K; ++k) e[k] = s0 + k < n ? blank_emission(x[q][k]) : kNegB;
                 lds_put<K>(ring + (rr & (R - 1)) * p.NSP, e);
                 ++done;                                      // (LDS keeps a wave's program order: row, then count)
                 if (lane == 0) wg_store(done_flag, done);
@@ -603,90 +581,49 @@ __device__ __forceinline__ void blank_loader_rows(const BlankParams &p, int b, i
     int *done_flag = f.flags + 4 * dir + j;
     const int *consumed = f.flags + 4 * dir + 3;
     int seen = 0;                                            // steps the chain is known to have consumed
-    // Steps [0, H) of this direction are gathered here (its chain leaves them in the workspace as well); steps >= H are rows
-    // the OTHER direction gathered in its first half: they come back from the workspace, K floats per lane.  Two loops, each
-    // with a FIXED number of memory operations per row in flight: with one loop and a branch per row the compiler must
-    // assume the fewest operations behind a row it waits for, and the twelve rows in flight shrink to three.
-    const int H = kGatherOnce ? (Tb + 1) >> 1 : Tb;
-    const __amdgpu_buffer_rsrc_t ersrc = lattice_rsrc(p.em + (int64_t)b * p.T * p.NSP, p.T, p.NSP);
-    const int lane_off = s0 < n ? s0 * (int)sizeof(float) : kPastLattice;
     auto issue = [&](f4_t (&x)[kMaxV4], int r) {             // row r of the step order (clamped: loaded, not used)
-        const int rr = r < H ? r : H - 1;
+        const int rr = r < Tb ? r : Tb - 1;
         const f4_t *row = reinterpret_cast<const f4_t *>(base + (int64_t)(dir == 0 ? rr : Tb - 1 - rr) * p.st);
 #pragma unroll
         for (int q = 0; q < kMaxV4; ++q) x[q] = row[min(lane + kWave * q, c4 - 1)];   // (past the row: its last float4 again)
     };
-    auto put = [&](const float (&e)[K], int rr, int &done) { // false: the wait ran out
+    auto finish = [&](const f4_t (&x)[kMaxV4], int rr, int &done) {   // false: the wait ran out
+#pragma unroll
+        for (int v = 0; v < kMaxV4; ++v) reinterpret_cast<f4_t *>(stage)[lane + kWave * v] = x[v];   // (stage holds 4 x 64 float4)
+        asm volatile("" ::: "memory");                       // (same wave: LDS keeps program order)
+        float e[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) e[k] = s0 + k < n ? blank_emission(stage[c[k]]) : kNegB;
         if (rr - R + 1 > seen && !lds_wait_ge(p, consumed, rr - R + 1, seen)) return false;   // slot still being read
         lds_put<K>(ring + (rr & (R - 1)) * p.NSP, e);
         ++done;                                              // (LDS keeps a wave's program order: row, then count)
         if (lane == 0) wg_store(done_flag, done);
         return true;
     };
-    auto finish = [&](const f4_t (&x)[kMaxV4], int rr, int &done) {
-#pragma unroll
-        for (int v = 0; v < kMaxV4; ++v) reinterpret_cast<f4_t *>(stage)[lane + kWave * v] = x[v];   // (stage holds 4 x 64 float4)
-        asm volatile("" ::: "memory");                       // (same wave: LDS keeps program order)
-        float e[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) e[k] = s0 + k < n ? fmaxf(stage[c[k]] * kLog2e, kNegB) : kNegB;
-        return put(e, rr, done);
-    };
     // kLoadAhead rows in flight, each in its own small array: one big array would stay in scratch
-    // memory (the backend only keeps arrays up to a quarter of the register budget in registers)
+    // memory (the backend only keeps arrays up to a quarter of the register budget in registers).
+    // Every row in flight has a FIXED number of memory operations behind it: with a branch per row the compiler
+    // must assume the fewest operations behind a row it waits for, and the twelve rows in flight shrink to three.
     static_assert(P == 12, "one named buffer per row in flight");
+    if (j >= Tb) return;                                     // fewer rows than loaders
     int done = 0;
-    if (j < H) {
-        f4_t x0[kMaxV4], x1[kMaxV4], x2[kMaxV4], x3[kMaxV4], x4[kMaxV4], x5[kMaxV4], x6[kMaxV4], x7[kMaxV4], x8[kMaxV4],
-            x9[kMaxV4], x10[kMaxV4], x11[kMaxV4];
+    f4_t x0[kMaxV4], x1[kMaxV4], x2[kMaxV4], x3[kMaxV4], x4[kMaxV4], x5[kMaxV4], x6[kMaxV4], x7[kMaxV4], x8[kMaxV4],
+        x9[kMaxV4], x10[kMaxV4], x11[kMaxV4];
 #define CTC_EACH_ROW(F) F(0, x0) F(1, x1) F(2, x2) F(3, x3) F(4, x4) F(5, x5) F(6, x6) F(7, x7) F(8, x8) F(9, x9) F(10, x10) F(11, x11)
 #define CTC_FIRST(Q, X) issue(X, j + kLoaders * (Q));
 #define CTC_TURN(Q, X)                                        \
     {                                                         \
         const int rr = r + kLoaders * (Q);                    \
-        if (rr < H && !finish(X, rr, done)) return;           \
+        if (rr < Tb && !finish(X, rr, done)) return;          \
         issue(X, rr + kLoaders * P);                          \
     }
-        CTC_EACH_ROW(CTC_FIRST)
-        for (int r = j; r < H; r += kLoaders * P) { CTC_EACH_ROW(CTC_TURN) }
+    CTC_EACH_ROW(CTC_FIRST)
+    for (int r = j; r < Tb; r += kLoaders * P) { CTC_EACH_ROW(CTC_TURN) }
 #undef CTC_TURN
 #undef CTC_FIRST
 #undef CTC_EACH_ROW
-    }
-    if (!kGatherOnce) return;
-    const int r0 = H + (j + kLoaders - H % kLoaders) % kLoaders;   // this loader's first row >= H (rows r = j mod kLoaders)
-    if (r0 >= Tb) return;
-    {
-        // Row r of our step order is the other direction's step Tb-1-r; its CHAIN stored the emission row and publishes
-        // how many of its steps have landed.  Later rows need fewer of them: one wait, for our first row.
-        int seen_landed = 0;
-        if (!lds_wait_ge(p, f.flags + 10 + (1 - dir), Tb - r0, seen_landed)) return;
-    }
-    auto fetch = [&](float (&y)[K], int r) {                 // sc0: past the L1 -- the CU's L2 has the row (same workgroup wrote it)
-        const int rr = r < Tb ? r : Tb - 1;
-        agent_load_row<K, 1>(ersrc, (dir == 0 ? rr : Tb - 1 - rr) * p.NSP * (int)sizeof(float) + lane_off, y);
-    };
-    float y[P][K];
-#pragma unroll
-    for (int q = 0; q < P; ++q) fetch(y[q], r0 + kLoaders * q);
-    for (int r = r0; r < Tb; r += kLoaders * P) {
-#pragma unroll
-        for (int q = 0; q < P; ++q) {
-            const int rr = r + kLoaders * q;
-            if (rr < Tb) {                                   // wave-uniform
-                float e[K];
-#pragma unroll
-                for (int k = 0; k < K; ++k) e[k] = s0 + k < n ? y[q][k] : kNegB;   // (lanes past the states read 0)
-                if (!put(e, rr, done)) return;
-            }
-            fetch(y[q], rr + kLoaders * P);
-        }
-    }
 }
 
-// One chain of the fused schedule: emissions from the LDS ring, kGroup steps per hand-off check;
-// lattice rows written through to memory (beta WITHOUT its own emission), and the number of steps
-// whose rows have landed published per group.
 // ---- pool gather (see kPoolGather) -------------------------------------------------------------------------------
 // rows of chunk c of a sample with T_b frames the pool will gather: distances [c kPoolChunk, min(.., H)), both ends,
 // the middle row of an odd T_b once
@@ -739,10 +676,10 @@ __device__ __forceinline__ void blank_pool_gather(const BlankParams &p, int wid,
                 const int c0 = cl[k].x, c1 = cl[k].y, c2 = cl[k].z, c3 = cl[k].w;
                 const int cc[4] = {c0, c1, c2, c3};
 #pragma unroll
-                for (int j = 0; j < K; ++j) e[j] = s0 + j < nq[k] ? fmaxf(stage[cc[j]] * kLog2e, kNegB) : kNegB;
+                for (int j = 0; j < K; ++j) e[j] = s0 + j < nq[k] ? blank_emission(stage[cc[j]]) : kNegB;
             } else {
 #pragma unroll
-                for (int j = 0; j < K; ++j) e[j] = s0 + j < nq[k] ? fmaxf(stage[p.cls[bq[k] * p.NSP + s0 + j]] * kLog2e, kNegB) : kNegB;
+                for (int j = 0; j < K; ++j) e[j] = s0 + j < nq[k] ? blank_emission(stage[p.cls[bq[k] * p.NSP + s0 + j]]) : kNegB;
             }
             asm volatile("" ::: "memory");                   // (the staged row is read before the next one overwrites it)
             const __amdgpu_buffer_rsrc_t ersrc = lattice_rsrc(p.em + (int64_t)bq[k] * p.T * p.NSP, p.T, p.NSP);
@@ -821,8 +758,11 @@ __device__ __forceinline__ void blank_pool_loader(const BlankParams &p, int b, i
     if (dead) { agent_store(p.sync, 1); raise_status(p.counter, kStatusBlankStarved); }
 }
 
+// One chain of the fused schedule: emissions from the LDS ring, kGroup steps per hand-off check;
+// lattice rows written through to memory (beta WITHOUT its own emission), and the number of steps
+// whose rows have landed published per group.
 template <int K, bool FWD, int NL>
-__device__ __forceinline__ void blank_chain_fused(const BlankParams &p, int b, int Tb, int L, float (&a)[K], const FusedLds &f, bool once)
+__device__ __forceinline__ void blank_chain_fused(const BlankParams &p, int b, int Tb, int L, float (&a)[K], const FusedLds &f)
 {
     constexpr int kLoaders = NL;                             // data loader waves of this direction (shadows the global)
     constexpr int R = kRingRows / K, G = kGroup < R / 2 ? kGroup : R / 2;
@@ -833,8 +773,8 @@ __device__ __forceinline__ void blank_chain_fused(const BlankParams &p, int b, i
     const float *ring = f.ring(dir) + s0;
     const int *loaded = f.flags + 4 * dir;
     int *consumed = f.flags + 4 * dir + 3;
-    bool skip[K], valid[K], starved = false;
-    blank_state_flags<K, FWD>(p, b, n, skip, valid);
+    bool skip[K], starved = false;
+    blank_state_flags<K, FWD>(p, b, n, s0, skip);
     // rows <= last of the step order are in the ring: loader j has then finished (last - j)/kLoaders + 1 rows
     int have[kLoaders] = {};
     unsigned long long waited = 0, polls = 0;                // (diagnostics)
@@ -870,14 +810,9 @@ __device__ __forceinline__ void blank_chain_fused(const BlankParams &p, int b, i
     // lanes whose K states all lie beyond the sample's n states get an offset past the end of the buffer:
     // the hardware drops their part of the store (config 5: 13 of 64 lanes, a fifth of the lattice bytes)
     const int lane_off = s0 < n ? s0 * (int)sizeof(float) : kPastLattice;
-    // gather-once: the emission rows of the first-half steps go to the workspace for the other direction's second half
-    const int H = once ? (Tb + 1) >> 1 : 0;
-    const __amdgpu_buffer_rsrc_t ersrc = lattice_rsrc(p.em + (int64_t)b * p.T * p.NSP, p.T, p.NSP);
-    int *landed = f.flags + 10 + dir;
     auto store = [&](int i, const float (&e)[K]) {
         const int t = FWD ? i : Tb - 1 - i;
-        if (i < H) agent_store_row<K, 0>(ersrc, t * p.NSP * (int)sizeof(float) + lane_off, e);   // (wave-uniform)
-        if (kHalfLattice && (t & 1) != (FWD ? 0 : 1)) return;   // (wave-uniform) the workers recompute this row
+        if ((t & 1) != (FWD ? 0 : 1)) return;                // (wave-uniform) the workers recompute this row
         const int off = t * p.NSP * (int)sizeof(float) + lane_off;
         if (FWD) {
             agent_store_row<K>(orsrc, off, a);
@@ -892,69 +827,48 @@ __device__ __forceinline__ void blank_chain_fused(const BlankParams &p, int b, i
         need_rows(0);
         float e0[K];
         em_row(e0, 0);
-        blank_first<K, FWD>(a, e0, n);
+        blank_first<K, FWD>(a, e0, n, s0);
         store(0, e0);
     }
-    // Two segments when the emission rows are shared (gather-once): steps [1, H) need only this direction's own
-    // loaders; before the first step >= H everything stored so far is drained and published -- the other direction's
-    // second half waits for exactly these rows, and with the usual lag both chains would wait for each other at H.
     int i = 1;
-#pragma nounroll
-    for (int seg = 0; seg < 2; ++seg) {
-        const int hi = (seg == 0 && H > 0) ? (H < Tb ? H : Tb) : Tb;
-        for (; i + G <= hi; i += G) {
-            if (FWD && b == 0 && (i - 1) % 256 < G) bstamp(p, 1 + (i - 1) / 256);
-            // (diagnostics, CTC_AMD_BLANK_DEBUG & 256: where a group of G steps of sample 0's alpha chain spends its cycles)
-            const unsigned long long q0 = probe ? __builtin_amdgcn_s_memtime() : 0;
-            need_rows(i + G - 1);
-            const unsigned long long q1 = probe ? __builtin_amdgcn_s_memtime() : 0;
-            float e[G][K];
+    for (; i + G <= Tb; i += G) {
+        if (FWD && b == 0 && (i - 1) % 256 < G) bstamp(p, 1 + (i - 1) / 256);
+        // (diagnostics, CTC_AMD_BLANK_DEBUG & 256: where a group of G steps of sample 0's alpha chain spends its cycles)
+        const unsigned long long q0 = probe ? __builtin_amdgcn_s_memtime() : 0;
+        need_rows(i + G - 1);
+        const unsigned long long q1 = probe ? __builtin_amdgcn_s_memtime() : 0;
+        float e[G][K];
 #pragma unroll
-            for (int j = 0; j < G; ++j) em_row(e[j], i + j);
-            if (probe) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            const unsigned long long q2 = probe ? __builtin_amdgcn_s_memtime() : 0;
+        for (int j = 0; j < G; ++j) em_row(e[j], i + j);
+        if (probe) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        const unsigned long long q2 = probe ? __builtin_amdgcn_s_memtime() : 0;
 #pragma unroll
-            for (int j = 0; j < G; ++j) {
-                blank_step<K, FWD>(a, e[j], skip);
-                store(i + j, e[j]);
-            }
-            const unsigned long long q3 = probe ? __builtin_amdgcn_s_memtime() : 0;
-            if (lane == 0) wg_store(consumed, i + G);        // the loaders may refill these slots
-            // Only stores go through this wave's vector-memory counter, it retires in order, and a step
-            // issues at least one: at most kLandLag outstanding => the rows of the steps before
-            // i + G - kLandLag have landed.
-            // (every other step stores when only half of the lattice is kept: half as many may be outstanding; groups that
-            // also store their emission rows have kLandLag more in the last kLandLag steps)
-            if (i + G <= H) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((kHalfLattice ? kLandLag / 2 : kLandLag) + kLandLag) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kHalfLattice ? kLandLag / 2 : kLandLag) : "memory");
-            const unsigned long long q4 = probe ? __builtin_amdgcn_s_memtime() : 0;
-            if (lane == 0 && i + G > kLandLag) {
-                agent_store(prog, i + G - kLandLag);
-                if (once) wg_store(landed, i + G - kLandLag);
-            }
-            if (probe) {
-                const unsigned long long q5 = __builtin_amdgcn_s_memtime();
-                const int half = 2 * i >= Tb ? 1 : 0;         // first half: worker pool idle; second: beside the streaming workers
-                pr[half][0] += q1 - q0; pr[half][1] += q2 - q1; pr[half][2] += q3 - q2; pr[half][3] += q4 - q3; pr[half][4] += q5 - q4;
-                pr[half][5] += 1;
-            }
+        for (int j = 0; j < G; ++j) {
+            blank_step<K, FWD>(a, e[j], skip);
+            store(i + j, e[j]);
         }
-        if (i < hi) {
-            need_rows(hi - 1);
-            for (; i < hi; ++i) {
-                float e[K];
-                em_row(e, i);
-                blank_step<K, FWD>(a, e, skip);
-                store(i, e);
-            }
-            if (lane == 0 && hi < Tb) wg_store(consumed, i);
+        const unsigned long long q3 = probe ? __builtin_amdgcn_s_memtime() : 0;
+        if (lane == 0) wg_store(consumed, i + G);            // the loaders may refill these slots
+        // Only stores go through this wave's vector-memory counter, it retires in order, and every other step
+        // issues one (half of the lattice is kept): at most kLandLag / 2 outstanding => the rows of the steps
+        // before i + G - kLandLag have landed.
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kLandLag / 2) : "memory");
+        const unsigned long long q4 = probe ? __builtin_amdgcn_s_memtime() : 0;
+        if (lane == 0 && i + G > kLandLag) agent_store(prog, i + G - kLandLag);
+        if (probe) {
+            const unsigned long long q5 = __builtin_amdgcn_s_memtime();
+            const int half = 2 * i >= Tb ? 1 : 0;             // first half: worker pool idle; second: beside the streaming workers
+            pr[half][0] += q1 - q0; pr[half][1] += q2 - q1; pr[half][2] += q3 - q2; pr[half][3] += q4 - q3; pr[half][4] += q5 - q4;
+            pr[half][5] += 1;
         }
-        if (seg == 0 && H > 0 && hi < Tb) {                  // the end of the first half: drain, publish
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (lane == 0) {
-                agent_store(prog, hi);
-                wg_store(landed, hi);
-            }
+    }
+    if (i < Tb) {
+        need_rows(Tb - 1);
+        for (; i < Tb; ++i) {
+            float e[K];
+            em_row(e, i);
+            blank_step<K, FWD>(a, e, skip);
+            store(i, e);
         }
     }
     if (lane == 0) wg_store(consumed, Tb + R);               // (nothing left to protect)
@@ -969,7 +883,6 @@ __device__ __forceinline__ void blank_chain_fused(const BlankParams &p, int b, i
             for (int k = 0; k < 6; ++k) reinterpret_cast<unsigned long long *>(p.counter)[8 + 6 * h + k] = pr[h][k];
     }
     if (lane == 0) agent_store(prog, starved ? -1 : Tb);     // (a starved chain never releases its rows)
-    if (lane == 0 && once && !starved) wg_store(landed, Tb);
     if (starved) a[0] = __builtin_nanf("");
 }
 
@@ -1023,100 +936,6 @@ __global__ __launch_bounds__(128) void blank_chain_kernel(BlankParams p)
 // ---- K2: gamma -> gradient rows ----------------------------------------------------------------
 constexpr int kGradWaves = 4;
 
-
-// One (t,b) row of work for a wave: everything it loads from HBM.
-template <int K>
-struct BlankRow {
-    float4 xr[kMaxV4];
-    float al[K], be[K], em[K];
-    int t, b, Tb, L;
-    bool live;                                               // false: a zero row (beyond T_b, or no alignment)
-    bool poison;                                             // fused schedule: the wait for the chains ran out
-};
-
-// SYNC = false (three launches): idx = t B + b, the lattice is complete.
-// SYNC = true (fused): idx = (2 m + side) B + b names the row at distance m from the FAR end of
-// its sample -- side 0 is t = m (a real row while m >= T_b-1-m, a zero row from T_b on), side 1
-// is t = T_b-1-m (while 0 <= t < m) -- i.e. the rows in the order in which they get both alpha
-// and beta; the loads wait until both chains have published the row; beta comes without its
-// emission, so none is loaded.  r.t < 0: no row here.
-// How far the two chains of a sample were when this wave last looked.  A look is a round trip to memory
-// (two when done one after the other) in front of a row's own loads, and the poll retires behind every
-// load the wave has in flight: with a look per row the worker pool did 310 rows/us.  A wave mostly stays
-// with one sample and the chains run ahead of a busy worker, so most rows need no look at all.
-struct ChainsSeen {
-    int b = -1, fwd = 0, bwd = 0;
-};
-
-// both chains of sample b have landed `need_f` / `need_b` steps; false when the bounded wait ran out
-__device__ __forceinline__ bool wait_chains(const BlankParams &p, int b, int need_f, int need_b, ChainsSeen &ps)
-{
-    if (ps.b != b) { ps.b = b; ps.fwd = ps.bwd = 0; }        // wave-uniform
-    if (ps.fwd >= need_f && ps.bwd >= need_b) return true;
-    const int *pf = p.sync + kSyncHead + b * kProgPitch, *pb = pf + p.Bp * kProgPitch;
-    bool ok = false;
-    for (int it = 0; it < kSpinLimit; ++it) {
-        const int vf = agent_load(pf), vb = agent_load(pb);  // (one round trip for the two)
-        ps.fwd = vf; ps.bwd = vb;
-        if (vf >= need_f && vb >= need_b) { ok = true; break; }
-        if (vf < 0 || vb < 0 || ((it & 255) == 255 && agent_load(p.sync) != 0)) break;   // a chain gave up / somebody did
-        const int naps = max(min(max(need_f - vf, need_b - vb), 64), 24);   // ~ a nap (1 us) per 8 missing steps, 3 to 8
-        for (int q = 0; q < naps; q += 8) __builtin_amdgcn_s_sleep(40);
-    }
-    if (!ok) { agent_store(p.sync, 1); raise_status(p.counter, kStatusBlankStarved); }
-    asm volatile("" ::: "memory");                           // nothing below moves above the poll
-    return ok;
-}
-
-template <int K, bool VEC4, bool SYNC>
-__device__ __forceinline__ void blank_row_load(const BlankParams &p, int idx, BlankRow<K> &r, ChainsSeen &ps)
-{
-    const int lane = lane_id();
-    const int q = idx / p.B;
-    r.b = __builtin_amdgcn_readfirstlane(idx - q * p.B);     // consecutive waves -> consecutive b: contiguous rows
-    // (through the scalar cache, and the SAME loads on every path -- dead rows and indices past the end load a clamped
-    // row and ignore it: see blank_pair_load on what a vector load of the lengths or an early exit costs the rows in flight)
-    int2 meta;
-    {
-        unsigned long long bits;
-        asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(bits) : "s"(p.meta + r.b) : "memory");
-        meta.x = (int)(unsigned)bits;
-        meta.y = (int)(bits >> 32);
-    }
-    const int Te = meta.x;                                   // 0 without an alignment: every row is a zero row
-    r.Tb = Te;
-    r.L = meta.y;
-    r.poison = false;
-    if (!SYNC) {
-        r.t = q < p.T ? q : -1;
-    } else {
-        const int m = q >> 1;
-        if ((q & 1) == 0) r.t = (m < p.T && (m >= Te || 2 * m >= Te - 1)) ? m : -1;
-        else r.t = (m < Te && Te - 1 - m < m) ? Te - 1 - m : -1;
-        r.t = __builtin_amdgcn_readfirstlane(r.t);
-    }
-    r.live = r.t >= 0 && r.t < Te;
-    const int te = r.live ? r.t : 0;
-    // (lanes beyond the sample's states: past the end of the buffer, they load nothing and read 0)
-    const int off = te * p.NSP * (int)sizeof(float) + (lane * K < 2 * r.L + 1 ? lane * K * (int)sizeof(float) : kPastLattice);
-    if (SYNC) {
-        if (r.live && !wait_chains(p, r.b, r.t + 1, Te - r.t, ps)) r.poison = true;
-        agent_load_row<K>(lattice_rsrc(p.al + (int64_t)r.b * p.T * p.NSP, p.T, p.NSP), off, r.al);
-        agent_load_row<K>(lattice_rsrc(p.be + (int64_t)r.b * p.T * p.NSP, p.T, p.NSP), off, r.be);
-    }
-    const int64_t o = ((int64_t)r.b * p.T + te) * p.NSP + lane * K;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        if (!SYNC) { r.al[k] = p.al[o + k]; r.be[k] = p.be[o + k]; r.em[k] = p.em[o + k]; }
-    }
-    if (VEC4) {
-        const float4 *row = reinterpret_cast<const float4 *>(p.lp + (int64_t)te * p.st + (int64_t)r.b * p.sb);
-        const int c4 = p.C >> 2;
-#pragma unroll
-        for (int i = 0; i < kMaxV4; ++i) r.xr[i] = row[min(lane + kWave * i, c4 - 1)];   // (past the row: its last float4 again)
-    }
-}
-
 // The state tables of the sample a wave is working on: this lane's K states in registers, the
 // repeat chain `nxt` in the wave's LDS (walked per row: from global memory every hop was a
 // dependent L2 round trip on the row's critical path).  Reloaded when the sample changes; a
@@ -1141,37 +960,62 @@ __device__ __forceinline__ void blank_tables_for(const BlankParams &p, int b, Bl
         tb.first[k] = p.first[b * p.NSP + s0 + k] != 0;
         nxt_l[s0 + k] = tb.nxt[k];
     }
-    if (kHalfLattice) {
-        bool valid[K];
-        const int n = 2 * p.meta[b].y + 1;
-        blank_state_flags<K, true>(p, b, n, tb.skipf, valid);
-        blank_state_flags<K, false>(p, b, n, tb.skipb, valid);
+    const int n = 2 * p.meta[b].y + 1;
+    blank_state_flags<K, true>(p, b, n, s0, tb.skipf);
+    blank_state_flags<K, false>(p, b, n, s0, tb.skipb);
+}
+
+// a gradient row of one value: 0 beyond T_b or without an alignment, NaN when a wait ran out
+template <bool VEC4>
+__device__ __forceinline__ void blank_row_fill(const BlankParams &p, int t, int b, float z)
+{
+    const int lane = lane_id();
+    float *g = p.grad + ((int64_t)t * p.B + b) * p.C;
+    if (VEC4) {
+        for (int q = lane; q < (p.C >> 2); q += kWave) stream_store(reinterpret_cast<float4 *>(g) + q, make_float4(z, z, z, z));
+    } else {
+        for (int c = lane; c < p.C; c += kWave) stream_store(&g[c], z);
     }
 }
 
-template <int K, bool VEC4, bool SYNC>
-__device__ __forceinline__ void blank_row_finish(const BlankParams &p, const BlankRow<K> &r, float *occ, float *gam, BlankTables<K> &tb)
+// the dense row (exp(lp) - occupancy) gs.  VEC4: C % 4 == 0 and 16-byte aligned rows -> float4 per lane (4x fewer
+// memory instructions), the log_probs row already in xr (kMaxV4 float4 per lane cover C <= 1024)
+template <bool VEC4>
+__device__ __forceinline__ void blank_row_dense(const BlankParams &p, int t, int b, const float4 (&xr)[kMaxV4], const float *occ, float gs)
 {
-    const int lane = lane_id(), s0 = lane * K;
-    int *nxt_l = reinterpret_cast<int *>(gam + p.NSP);
-    if (r.t < 0) return;                                     // (fused) this index names no row
-    float *g = p.grad + ((int64_t)r.t * p.B + r.b) * p.C;
-    if (!r.live || r.poison) {
-        const float z = r.poison ? __builtin_nanf("") : 0.f;
-        if (VEC4) {
-            for (int q = lane; q < (p.C >> 2); q += kWave) stream_store(reinterpret_cast<float4 *>(g) + q, make_float4(z, z, z, z));
-        } else {
-            for (int c = lane; c < p.C; c += kWave) stream_store(&g[c], z);
+    const int lane = lane_id();
+    float *g = p.grad + ((int64_t)t * p.B + b) * p.C;
+    if (VEC4) {
+#pragma unroll
+        for (int i = 0; i < kMaxV4; ++i) {
+            const int q = lane + kWave * i;
+            if (q < (p.C >> 2)) {
+                const float4 o = reinterpret_cast<const float4 *>(occ)[q];
+                float4 out;
+                out.x = (fast_exp(xr[i].x) - o.x) * gs;
+                out.y = (fast_exp(xr[i].y) - o.y) * gs;
+                out.z = (fast_exp(xr[i].z) - o.z) * gs;
+                out.w = (fast_exp(xr[i].w) - o.w) * gs;
+                stream_store(reinterpret_cast<float4 *>(g) + q, out);
+            }
         }
-        return;
+    } else {
+        const float *row = p.lp + (int64_t)t * p.st + (int64_t)b * p.sb;
+        for (int c = lane; c < p.C; c += kWave) stream_store(&g[c], (fast_exp(row[c]) - occ[c]) * gs);
     }
-    const int n = 2 * r.L + 1;
-    blank_tables_for<K>(p, r.b, tb, nxt_l);
-    float v[K];
+}
+
+// gamma of one row (v: alpha + beta - e in log2 units, this lane's K states) -> its gradient row:
+// gamma_t = softmax_s(v), folded per class into occ[] (wave-local LDS, all zero between rows), then the dense row
+template <int K, bool VEC4>
+__device__ __forceinline__ void blank_row_emit(const BlankParams &p, int t, int b, int L, float (&v)[K], const float4 (&xr)[kMaxV4],
+                                               float *occ, float *gam, const int *nxt_l, const BlankTables<K> &tb)
+{
+    const int lane = lane_id(), s0 = lane * K, n = 2 * L + 1;
     float m = kNegB;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        v[k] = s0 + k < n ? (SYNC ? r.al[k] + r.be[k] : r.al[k] + r.be[k] - r.em[k]) : kNegB;
+        v[k] = s0 + k < n ? v[k] : kNegB;
         m = fmaxf(m, v[k]);
     }
     m = wave_max(m);
@@ -1197,25 +1041,7 @@ __device__ __forceinline__ void blank_row_finish(const BlankParams &p, const Bla
             occ[tb.cls[k]] = tot;
         }
     }
-    const float gs = p.grad_scale / (float)(r.L > 1 ? r.L : 1);
-    if (VEC4) {
-#pragma unroll
-        for (int i = 0; i < kMaxV4; ++i) {
-            const int q = lane + kWave * i;
-            if (q < (p.C >> 2)) {
-                const float4 o = reinterpret_cast<const float4 *>(occ)[q];
-                float4 out;
-                out.x = (fast_exp(r.xr[i].x) - o.x) * gs;
-                out.y = (fast_exp(r.xr[i].y) - o.y) * gs;
-                out.z = (fast_exp(r.xr[i].z) - o.z) * gs;
-                out.w = (fast_exp(r.xr[i].w) - o.w) * gs;
-                stream_store(reinterpret_cast<float4 *>(g) + q, out);
-            }
-        }
-    } else {
-        const float *row = p.lp + (int64_t)r.t * p.st + (int64_t)r.b * p.sb;
-        for (int c = lane; c < p.C; c += kWave) stream_store(&g[c], (fast_exp(row[c]) - occ[c]) * gs);
-    }
+    blank_row_dense<VEC4>(p, t, b, xr, occ, p.grad_scale / (float)(L > 1 ? L : 1));
     // un-set only what this row touched
     if (lane == 0) occ[p.blank] = 0.f;
 #pragma unroll
@@ -1225,7 +1051,96 @@ __device__ __forceinline__ void blank_row_finish(const BlankParams &p, const Bla
     }
 }
 
-// ---- row PAIRS (persistent launch with half of the lattice in memory) -----------------------------------
+// ---- three-launch schedule: one (t,b) row of work for a wave, the lattice complete in the workspace ----
+// everything the wave loads from HBM for the row
+template <int K>
+struct BlankRow {
+    float4 xr[kMaxV4];
+    float al[K], be[K], em[K];
+    int t, b, Tb, L;                                         // t < 0: no row here
+    bool live;                                               // false: a zero row (beyond T_b, or no alignment)
+};
+
+// idx = t B + b
+template <int K, bool VEC4>
+__device__ __forceinline__ void blank_row_load(const BlankParams &p, int idx, BlankRow<K> &r)
+{
+    const int lane = lane_id();
+    const int q = idx / p.B;
+    r.b = __builtin_amdgcn_readfirstlane(idx - q * p.B);     // consecutive waves -> consecutive b: contiguous rows
+    // (through the scalar cache, and the SAME loads on every path -- dead rows and indices past the end load a clamped
+    // row and ignore it: see blank_pair_load on what a vector load of the lengths or an early exit costs the rows in flight)
+    int2 meta;
+    {
+        unsigned long long bits;
+        asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(bits) : "s"(p.meta + r.b) : "memory");
+        meta.x = (int)(unsigned)bits;
+        meta.y = (int)(bits >> 32);
+    }
+    const int Te = meta.x;                                   // 0 without an alignment: every row is a zero row
+    r.Tb = Te;
+    r.L = meta.y;
+    r.t = q < p.T ? q : -1;
+    r.live = r.t >= 0 && r.t < Te;
+    const int te = r.live ? r.t : 0;
+    const int64_t o = ((int64_t)r.b * p.T + te) * p.NSP + lane * K;
+#pragma unroll
+    for (int k = 0; k < K; ++k) { r.al[k] = p.al[o + k]; r.be[k] = p.be[o + k]; r.em[k] = p.em[o + k]; }
+    if (VEC4) {
+        const float4 *row = reinterpret_cast<const float4 *>(p.lp + (int64_t)te * p.st + (int64_t)r.b * p.sb);
+        const int c4 = p.C >> 2;
+#pragma unroll
+        for (int i = 0; i < kMaxV4; ++i) r.xr[i] = row[min(lane + kWave * i, c4 - 1)];   // (past the row: its last float4 again)
+    }
+}
+
+template <int K, bool VEC4>
+__device__ __forceinline__ void blank_row_finish(const BlankParams &p, const BlankRow<K> &r, float *occ, float *gam, BlankTables<K> &tb)
+{
+    int *nxt_l = reinterpret_cast<int *>(gam + p.NSP);
+    if (r.t < 0) return;                                     // an index past the end names no row
+    if (!r.live) {
+        blank_row_fill<VEC4>(p, r.t, r.b, 0.f);
+        return;
+    }
+    blank_tables_for<K>(p, r.b, tb, nxt_l);
+    float v[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = r.al[k] + r.be[k] - r.em[k];
+    blank_row_emit<K, VEC4>(p, r.t, r.b, r.L, v, r.xr, occ, gam, nxt_l, tb);
+}
+
+// Rows are double-buffered: the loads of a wave's NEXT row (lattice triples + the whole log-prob row) are in flight
+// while the current row is reduced and written.  Wave `first` of `stride` takes rows first, first+stride, ...
+template <int K, bool VEC4>
+__device__ __forceinline__ void blank_grad_rows(const BlankParams &p, int first, int stride, int total_rows, float *occ, float *gam)
+{
+    int idx = first;
+    if (idx >= total_rows) return;
+    BlankTables<K> tb;
+    BlankRow<K> ra, rb;
+    blank_row_load<K, VEC4>(p, idx, ra);
+    for (; idx < total_rows; idx += 2 * stride) {            // (loads past the end name no row: see blank_row_load)
+        blank_row_load<K, VEC4>(p, idx + stride, rb);
+        blank_row_finish<K, VEC4>(p, ra, occ, gam, tb);
+        blank_row_load<K, VEC4>(p, idx + 2 * stride, ra);
+        if (idx + stride < total_rows) blank_row_finish<K, VEC4>(p, rb, occ, gam, tb);
+    }
+}
+
+template <int K, bool VEC4>
+__global__ __launch_bounds__(kGradWaves * kWave) void blank_grad_kernel(BlankParams p, int total_rows)
+{
+    extern __shared__ float4 s_buf4[];                       // per wave: occ[C4] + gam[NSP] + nxt[NSP]
+    const int w = wave_id(), lane = lane_id();
+    const int C4 = (p.C + 3) & ~3;
+    float *occ = reinterpret_cast<float *>(s_buf4) + (size_t)w * (C4 + 2 * p.NSP);
+    float *gam = occ + C4;
+    for (int c = lane; c < C4; c += kWave) occ[c] = 0.f;
+    blank_grad_rows<K, VEC4>(p, blockIdx.x * kGradWaves + w, gridDim.x * kGradWaves, total_rows, occ, gam);
+}
+
+// ---- persistent launch: row PAIRS (half of the lattice in memory) -----------------------------------------
 // A pair is rows t = 2P and t + 1 of a sample.  Memory holds alpha_t and beta'_{t+1}; with e = the emissions of
 // row t + 1 gathered from the log_probs row the wave holds anyway:
 //     alpha_{t+1} = step_fwd(alpha_t) + e          (bit-identical to the chain's own row)
@@ -1237,10 +1152,41 @@ struct BlankPair {
     float al[K], be[K];
     int t, b, Tb, L;                                         // t: the even row, < 0: no pair here
     bool live0, live1, exist1;                               // rows t / t+1 inside T_b; row t+1 inside T
-    bool poison;
+    bool poison;                                             // the wait for the chains ran out
 };
 
-// idx = (2 m + side) B + b over PAIR distances m, the analogue of blank_row_load<SYNC>'s order
+// How far the two chains of a sample were when this wave last looked.  A look is a round trip to memory
+// (two when done one after the other) in front of a pair's own loads, and the poll retires behind every
+// load the wave has in flight: with a look per row the worker pool did 310 rows/us.  A wave mostly stays
+// with one sample and the chains run ahead of a busy worker, so most pairs need no look at all.
+struct ChainsSeen {
+    int b = -1, fwd = 0, bwd = 0;
+};
+
+// both chains of sample b have landed `need_f` / `need_b` steps; false when the bounded wait ran out
+__device__ __forceinline__ bool wait_chains(const BlankParams &p, int b, int need_f, int need_b, ChainsSeen &ps)
+{
+    if (ps.b != b) { ps.b = b; ps.fwd = ps.bwd = 0; }        // wave-uniform
+    if (ps.fwd >= need_f && ps.bwd >= need_b) return true;
+    const int *pf = p.sync + kSyncHead + b * kProgPitch, *pb = pf + p.Bp * kProgPitch;
+    bool ok = false;
+    for (int it = 0; it < kSpinLimit; ++it) {
+        const int vf = agent_load(pf), vb = agent_load(pb);  // (one round trip for the two)
+        ps.fwd = vf; ps.bwd = vb;
+        if (vf >= need_f && vb >= need_b) { ok = true; break; }
+        if (vf < 0 || vb < 0 || ((it & 255) == 255 && agent_load(p.sync) != 0)) break;   // a chain gave up / somebody did
+        const int naps = max(min(max(need_f - vf, need_b - vb), 64), 24);   // ~ a nap (1 us) per 8 missing steps, 3 to 8
+        for (int q = 0; q < naps; q += 8) __builtin_amdgcn_s_sleep(40);
+    }
+    if (!ok) { agent_store(p.sync, 1); raise_status(p.counter, kStatusBlankStarved); }
+    asm volatile("" ::: "memory");                           // nothing below moves above the poll
+    return ok;
+}
+
+// idx = (2 m + side) B + b names the pair at distance m (in pairs) from the FAR end of its sample -- side 0 is
+// P = m (a real pair while m >= P_b-1-m, a zero pair from P_b = ceil(T_b / 2) on), side 1 is P = P_b-1-m (while
+// 0 <= P < m) -- i.e. the pairs in the order in which they get both alpha and beta: the chains cross in the middle
+// of the sample.  The loads wait until both chains have published the pair.  r.t < 0: no pair here.
 template <int K, bool VEC4>
 __device__ __forceinline__ void blank_pair_load(const BlankParams &p, int idx, BlankPair<K> &r, ChainsSeen &ps)
 {
@@ -1289,81 +1235,6 @@ __device__ __forceinline__ void blank_pair_load(const BlankParams &p, int idx, B
     }
 }
 
-// gamma of one row (v: alpha + beta' in log2 units, this lane's K states) -> its gradient row
-template <int K, bool VEC4>
-__device__ __forceinline__ void blank_row_emit(const BlankParams &p, int t, int b, int L, float (&v)[K], const float4 (&xr)[kMaxV4],
-                                               float *occ, float *gam, const int *nxt_l, const BlankTables<K> &tb)
-{
-    const int lane = lane_id(), s0 = lane * K, n = 2 * L + 1;
-    float *g = p.grad + ((int64_t)t * p.B + b) * p.C;
-    float m = kNegB;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        v[k] = s0 + k < n ? v[k] : kNegB;
-        m = fmaxf(m, v[k]);
-    }
-    m = wave_max(m);
-    float ssum = 0.f, blank_part = 0.f;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        v[k] = s0 + k < n ? __builtin_amdgcn_exp2f(v[k] - m) : 0.f;     // lattice is in log2 units
-        ssum += v[k];
-        if (((s0 + k) & 1) == 0) blank_part += v[k];
-    }
-    ssum = wave_sum(ssum);
-    blank_part = wave_sum(blank_part);
-    const float inv = 1.0f / ssum;
-#pragma unroll
-    for (int k = 0; k < K; ++k) gam[s0 + k] = v[k] * inv;            // wave-local LDS, in order
-    if (lane == 0) occ[p.blank] = blank_part * inv;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        if (tb.first[k]) {                                    // label states only; repeats are chained
-            float tot = gam[s0 + k];
-            for (int q = tb.nxt[k]; q >= 0; q = nxt_l[q]) tot += gam[q];
-            occ[tb.cls[k]] = tot;
-        }
-    }
-    const float gs = p.grad_scale / (float)(L > 1 ? L : 1);
-    if (VEC4) {
-#pragma unroll
-        for (int i = 0; i < kMaxV4; ++i) {
-            const int q = lane + kWave * i;
-            if (q < (p.C >> 2)) {
-                const float4 o = reinterpret_cast<const float4 *>(occ)[q];
-                float4 out;
-                out.x = (fast_exp(xr[i].x) - o.x) * gs;
-                out.y = (fast_exp(xr[i].y) - o.y) * gs;
-                out.z = (fast_exp(xr[i].z) - o.z) * gs;
-                out.w = (fast_exp(xr[i].w) - o.w) * gs;
-                stream_store(reinterpret_cast<float4 *>(g) + q, out);
-            }
-        }
-    } else {
-        const float *row = p.lp + (int64_t)t * p.st + (int64_t)b * p.sb;
-        for (int c = lane; c < p.C; c += kWave) stream_store(&g[c], (fast_exp(row[c]) - occ[c]) * gs);
-    }
-    // un-set only what this row touched
-    if (lane == 0) occ[p.blank] = 0.f;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int s = s0 + k;
-        if ((s & 1) && s < n) occ[tb.cls[k]] = 0.f;
-    }
-}
-
-template <bool VEC4>
-__device__ __forceinline__ void blank_row_fill(const BlankParams &p, int t, int b, float z)
-{
-    const int lane = lane_id();
-    float *g = p.grad + ((int64_t)t * p.B + b) * p.C;
-    if (VEC4) {
-        for (int q = lane; q < (p.C >> 2); q += kWave) stream_store(reinterpret_cast<float4 *>(g) + q, make_float4(z, z, z, z));
-    } else {
-        for (int c = lane; c < p.C; c += kWave) stream_store(&g[c], z);
-    }
-}
-
 template <int K, bool VEC4>
 __device__ __forceinline__ void blank_pair_finish(const BlankParams &p, const BlankPair<K> &r, float *occ, float *gam, float *stage,
                                                   BlankTables<K> &tb)
@@ -1389,11 +1260,11 @@ __device__ __forceinline__ void blank_pair_finish(const BlankParams &p, const Bl
             for (int i = 0; i < kMaxV4; ++i) reinterpret_cast<float4 *>(stage)[lane + kWave * i] = r.x1[i];
             asm volatile("" ::: "memory");                   // (same wave: LDS keeps program order)
 #pragma unroll
-            for (int k = 0; k < K; ++k) e1[k] = s0 + k < n ? fmaxf(stage[tb.cls[k]] * kLog2e, kNegB) : kNegB;
+            for (int k = 0; k < K; ++k) e1[k] = s0 + k < n ? blank_emission(stage[tb.cls[k]]) : kNegB;
         } else {
             const float *row1 = p.lp + (int64_t)(r.t + 1) * p.st + (int64_t)r.b * p.sb;
 #pragma unroll
-            for (int k = 0; k < K; ++k) e1[k] = s0 + k < n ? fmaxf(row1[tb.cls[k]] * kLog2e, kNegB) : kNegB;
+            for (int k = 0; k < K; ++k) e1[k] = s0 + k < n ? blank_emission(row1[tb.cls[k]]) : kNegB;
         }
         float a1[K], b1[K], zero[K];
 #pragma unroll
@@ -1449,64 +1320,6 @@ __device__ __forceinline__ void blank_grad_pairs(const BlankParams &p, int first
 #undef CTC_TURN
 }
 
-// VEC4: C % 4 == 0 and 16-byte aligned rows -> the dense part moves float4 per lane (4x fewer
-// memory instructions).  Rows are double-buffered: the loads of a wave's NEXT row (lattice
-// triples + the whole log-prob row, kMaxV4 float4 per lane cover C <= 1024) are in flight while
-// the current row is reduced and written.  Wave `first` of `stride` takes rows first, first+stride, ...
-template <int K, bool VEC4, bool SYNC>
-__device__ __forceinline__ void blank_grad_rows(const BlankParams &p, int first, int stride, int total_rows, float *occ, float *gam)
-{
-    int idx = first;
-    if (idx >= total_rows) return;
-    BlankTables<K> tb;
-    ChainsSeen ps;
-    if (!SYNC) {
-        BlankRow<K> ra, rb;
-        blank_row_load<K, VEC4, SYNC>(p, idx, ra, ps);
-        for (; idx < total_rows; idx += 2 * stride) {        // (loads past the end name no row: see blank_row_load)
-            blank_row_load<K, VEC4, SYNC>(p, idx + stride, rb, ps);
-            blank_row_finish<K, VEC4, SYNC>(p, ra, occ, gam, tb);
-            blank_row_load<K, VEC4, SYNC>(p, idx + 2 * stride, ra, ps);
-            if (idx + stride < total_rows) blank_row_finish<K, VEC4, SYNC>(p, rb, occ, gam, tb);
-        }
-    } else {
-        // fused launch: two waves per SIMD instead of eight, so each keeps six rows in flight (four: +3 %).
-        // (Holding the workers back to one row while chains are still running, to leave HBM to the loaders,
-        // was slower: 559 against 536 us at config 5.)
-        BlankRow<K> r0, r1, r2, r3, r4, r5;
-        constexpr int NB = 6;                                // rows in flight
-        blank_row_load<K, VEC4, SYNC>(p, idx, r0, ps);
-        blank_row_load<K, VEC4, SYNC>(p, idx + stride, r1, ps);
-        blank_row_load<K, VEC4, SYNC>(p, idx + 2 * stride, r2, ps);
-        blank_row_load<K, VEC4, SYNC>(p, idx + 3 * stride, r3, ps);
-        blank_row_load<K, VEC4, SYNC>(p, idx + 4 * stride, r4, ps);
-#define CTC_TURN(Q, CUR, NEXT)                                                                                 \
-    blank_row_load<K, VEC4, SYNC>(p, idx + ((Q) + NB - 1) * stride, NEXT, ps);                                 \
-    if (idx + (Q)*stride < total_rows) blank_row_finish<K, VEC4, SYNC>(p, CUR, occ, gam, tb);
-        for (; idx < total_rows; idx += NB * stride) {
-            CTC_TURN(0, r0, r5)
-            CTC_TURN(1, r1, r0)
-            CTC_TURN(2, r2, r1)
-            CTC_TURN(3, r3, r2)
-            CTC_TURN(4, r4, r3)
-            CTC_TURN(5, r5, r4)
-        }
-#undef CTC_TURN
-    }
-}
-
-template <int K, bool VEC4>
-__global__ __launch_bounds__(kGradWaves * kWave) void blank_grad_kernel(BlankParams p, int total_rows)
-{
-    extern __shared__ float4 s_buf4[];                       // per wave: occ[C4] + gam[NSP] + nxt[NSP]
-    const int w = wave_id(), lane = lane_id();
-    const int C4 = (p.C + 3) & ~3;
-    float *occ = reinterpret_cast<float *>(s_buf4) + (size_t)w * (C4 + 2 * p.NSP);
-    float *gam = occ + C4;
-    for (int c = lane; c < C4; c += kWave) occ[c] = 0.f;
-    blank_grad_rows<K, VEC4, false>(p, blockIdx.x * kGradWaves + w, gridDim.x * kGradWaves, total_rows, occ, gam);
-}
-
 // ---- fused schedule: the launch -----------------------------------------------------------------
 template <int K, bool VEC4, bool POOL = false>
 __global__ __launch_bounds__(kFusedThreads) void blank_fused_kernel(BlankParams p)
@@ -1530,10 +1343,10 @@ __global__ __launch_bounds__(kFusedThreads) void blank_fused_kernel(BlankParams 
         if (role == 0) {
             __builtin_amdgcn_s_setprio(3);
             if (dir == 0) {
-                if (run) blank_chain_fused<K, true, NL>(p, b, Tb, L, a, f, VEC4 && kGatherOnce && !kPool);
+                if (run) blank_chain_fused<K, true, NL>(p, b, Tb, L, a, f);
                 blank_publish<K>(p, b, ok, Tb, L, a);
             } else if (run) {
-                blank_chain_fused<K, false, NL>(p, b, Tb, L, a, f, VEC4 && kGatherOnce && !kPool);
+                blank_chain_fused<K, false, NL>(p, b, Tb, L, a, f);
             }
         } else if (run) {
             const int j = role - 1;
@@ -1549,33 +1362,29 @@ __global__ __launch_bounds__(kFusedThreads) void blank_fused_kernel(BlankParams 
         }
         return;
     }
-    // a row worker: per wave occ[C4] + gam[NSP] + nxt[NSP] (+ a staged log_probs row when it works on row pairs)
+    // a row worker: per wave occ[C4] + gam[NSP] + nxt[NSP] (+ a staged log_probs row of float4)
     const int C4 = (p.C + 3) & ~3;
-    const int per_wave = C4 + 2 * p.NSP + (kHalfLattice && VEC4 ? 4 * kWave * kMaxV4 : 0);
+    const int per_wave = C4 + 2 * p.NSP + (VEC4 ? 4 * kWave * kMaxV4 : 0);
     float *occ = reinterpret_cast<float *>(s_buf4) + (size_t)w * per_wave;
     float *gam = occ + C4;
     for (int c = lane; c < C4; c += kWave) occ[c] = 0.f;
     const int wid = ((int)blockIdx.x - p.B) * kFusedWaves + w, nw = ((int)gridDim.x - p.B) * kFusedWaves;
     if (wid == 0) bstamp(p, 0);
     if (wid == nw - 1) bstamp(p, 15);
-    // rows exist from distance (T_b - 1)/2 on (the middle of the sample): start at the smallest one of the batch
-    // (row pairs: the same in units of pairs)
+    // pairs exist from distance (P_b - 1)/2 on (the middle of the sample): start at the smallest one of the batch
     int m0 = p.T;
     for (int bb = lane; bb < p.B; bb += kWave) {
-        const int len = kHalfLattice ? (p.meta[bb].x + 1) >> 1 : p.meta[bb].x;
+        const int len = (p.meta[bb].x + 1) >> 1;
         m0 = min(m0, (max(len, 1) - 1) >> 1);
     }
 #pragma unroll
     for (int sh = 1; sh < kWave; sh <<= 1) m0 = min(m0, __shfl_xor(m0, sh));
     m0 = __builtin_amdgcn_readfirstlane(m0);
     if (VEC4 && POOL && kPoolGather) {                       // the pool's first job: the emission rows, in the chains' order
-        blank_pool_gather<K>(p, wid, nw, kHalfLattice ? gam + 2 * p.NSP : occ);
-        if (!kHalfLattice)
-            for (int c = lane; c < C4; c += kWave) occ[c] = 0.f;
+        blank_pool_gather<K>(p, wid, nw, gam + 2 * p.NSP);
         if (wid == 0) bstamp(p, 11);
     }
-    if (kHalfLattice) blank_grad_pairs<K, VEC4>(p, m0 * 2 * p.B + wid, nw, 2 * ((p.T + 1) >> 1) * p.B, occ, gam, gam + 2 * p.NSP);
-    else blank_grad_rows<K, VEC4, true>(p, m0 * 2 * p.B + wid, nw, 2 * p.T * p.B, occ, gam);
+    blank_grad_pairs<K, VEC4>(p, m0 * 2 * p.B + wid, nw, 2 * ((p.T + 1) >> 1) * p.B, occ, gam, gam + 2 * p.NSP);
     if (wid == 0) bstamp(p, 12);
     if (wid == nw - 1) bstamp(p, 13);
     if (wid == nw / 2) bstamp(p, 14);
@@ -1619,10 +1428,20 @@ static int blank_schedule()
     return v;
 }
 
-template <int K>
-static int run_blank(BlankParams &p, hipStream_t s)
+// ---- host side ------------------------------------------------------------------------------------------
+// 2S+1 states padded to what the kernels work on: 64 K (K = 2, 4, 8 states per lane) up to S = 255, beyond that
+// (blank_wide.hpp) W waves of 512 states, 512 W -- not the next power of two
+size_t blank_padded_states(int S)
 {
-    p.NSP = kWave * K;
+    const size_t ns = 2 * (size_t)S + 1, span = kWave * 8;
+    return ns <= kWave * 2 ? kWave * 2 : (ns <= kWave * 4 ? kWave * 4 : (ns + span - 1) / span * span);
+}
+
+// The workspace behind its 256-byte header (ctc_amd_workspace_bytes): emissions, alpha, beta [B][T][nsp], the three
+// state tables [B][nsp], the lengths [Bp], the hand-off state of the persistent launch (blank_sync_ints)
+static void blank_layout(BlankParams &p, int nsp)
+{
+    p.NSP = nsp;
     const size_t lattice = (size_t)p.B * p.T * p.NSP;
     float *base = reinterpret_cast<float *>(reinterpret_cast<char *>(p.counter) + 256);
     p.em = base;
@@ -1637,11 +1456,39 @@ static int run_blank(BlankParams &p, hipStream_t s)
     p.nsync = blank_sync_ints(p.T, p.B);
     p.nchunk = blank_pool_chunks(p.T);
     p.chunk = p.sync + kSyncHead + 2 * p.Bp * kProgPitch;
+    p.debug = 0;                                             // (diagnostics: run_blank sets it)
+}
+
+// rows of log_probs and of the gradient can move as float4 (and fit in kMaxV4 of them per lane)
+static bool blank_rows_vec4(const BlankParams &p)
+{
+    return (p.C % 4 == 0) && p.C <= 4 * kWave * kMaxV4 && (p.st % 4 == 0) && (p.sb % 4 == 0) &&
+           (reinterpret_cast<uintptr_t>(p.lp) % 16 == 0) && (reinterpret_cast<uintptr_t>(p.grad) % 16 == 0);
+}
+
+// a gradient wave's occ[] + gam[] + nxt[]
+static size_t blank_row_lds(const BlankParams &p) { return (((p.C + 3) & ~3) + 2 * p.NSP) * sizeof(float); }
+
+// the gradient launch of the three-launch schedules: one wave per (t,b) row, at most eight workgroups per CU's worth
+template <auto kern_vec4, auto kern_scalar>
+static int blank_launch_grad(const BlankParams &p, bool vec4, hipStream_t s)
+{
+    const int total = p.T * p.B;
+    int blocks = (total + kGradWaves - 1) / kGradWaves;
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    const size_t lds = kGradWaves * blank_row_lds(p);
+    const dim3 grid(blocks), block(kGradWaves * kWave);
+    return vec4 ? launch<kern_vec4>(grid, block, lds, s, p, total) : launch<kern_scalar>(grid, block, lds, s, p, total);
+}
+
+// S <= 255; p.NSP = 64 K (blank_layout)
+template <int K>
+static int run_blank(BlankParams &p, hipStream_t s)
+{
     static const int debug = diag_env("CTC_AMD_BLANK_DEBUG");
     p.debug = debug;
-    const size_t row_lds = (((p.C + 3) & ~3) + 2 * p.NSP) * sizeof(float);   // a grad wave's occ[] + gam[] + nxt[]
-    const bool vec4 = (p.C % 4 == 0) && p.C <= 4 * kWave * kMaxV4 && (p.st % 4 == 0) && (p.sb % 4 == 0) &&
-                      (reinterpret_cast<uintptr_t>(p.lp) % 16 == 0) && (reinterpret_cast<uintptr_t>(p.grad) % 16 == 0);
+    const size_t row_lds = blank_row_lds(p);
+    const bool vec4 = blank_rows_vec4(p);
 
     // Persistent launch.  Hard conditions: a gradient is wanted, every workgroup resident with at least as
     // many workers as chains, 32-bit row offsets.  Where it PAYS was measured (tools/blank_sweep.py, T = 1000,
@@ -1658,7 +1505,7 @@ static int run_blank(BlankParams &p, hipStream_t s)
         // more than half of a CU's LDS per workgroup: one workgroup per CU, the chains share their SIMDs with nobody
         size_t lds = kFusedLdsHead + 2 * (size_t)(kRingRows / K) * p.NSP * sizeof(float) +
                      (vec4 ? 2 * kLoaders * (size_t)(4 * kWave * kMaxV4) * sizeof(float) : 0);   // + a row per loader
-        const size_t worker_lds = row_lds + (kHalfLattice && vec4 ? (size_t)4 * kWave * kMaxV4 * sizeof(float) : 0);
+        const size_t worker_lds = row_lds + (vec4 ? (size_t)4 * kWave * kMaxV4 * sizeof(float) : 0);
         if (lds < kFusedWaves * worker_lds) lds = kFusedWaves * worker_lds;
         if (lds < kMaxLds / 2 + 1024) lds = kMaxLds / 2 + 1024;
         const int cap = lds <= kMaxLds ? (vec4 ? fused_capacity<K, true>(lds) : fused_capacity<K, false>(lds)) : 0;
@@ -1688,12 +1535,7 @@ static int run_blank(BlankParams &p, hipStream_t s)
     if (rc) return rc;
     rc = launch<blank_chain_kernel<K>>(dim3(p.B), dim3(128), 0, s, p);
     if (rc || !p.grad) return rc;
-    const int total = p.T * p.B;
-    int blocks = (total + kGradWaves - 1) / kGradWaves;
-    if (blocks > 256 * 8) blocks = 256 * 8;
-    const size_t lds = kGradWaves * row_lds;
-    if (vec4) return launch<blank_grad_kernel<K, true>>(dim3(blocks), dim3(kGradWaves * kWave), lds, s, p, total);
-    return launch<blank_grad_kernel<K, false>>(dim3(blocks), dim3(kGradWaves * kWave), lds, s, p, total);
+    return blank_launch_grad<blank_grad_kernel<K, true>, blank_grad_kernel<K, false>>(p, vec4, s);
 }
 
 }  // namespace ctc
@@ -1712,12 +1554,12 @@ extern "C" int ctc_amd_blank_loss_grad(const float *log_probs, int64_t stride_t,
 {
     if (!log_probs || !targets || !in_len || !tgt_len || !nll || !loss || !workspace) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (T < 1 || B < 1 || C < 1 || S < 1 || blank < 0 || blank >= C) return CTC_AMD_ERR_BAD_ARGUMENT;
-    const int ns = 2 * S + 1;
     if (S > 1023) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;                       // 2S+1 <= 2047 states: four waves of 512
-    const bool wide = ns > kWave * 8;                                         // S > 255: blank_wide.hpp
-    const int nsp = wide ? (ns + kWideSpan - 1) / kWideSpan * kWideSpan : kWave * 8;
-    // a gradient wave's occ[C] beside gam[] and the state table of the padded width
-    if ((size_t)kGradWaves * (C + 4 + 2 * nsp) * sizeof(float) > kMaxLds) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
+    const int nsp = (int)blank_padded_states(S);
+    // a gradient wave's occ[C] beside gam[] and the state table -- of 512 states up to S = 255, whatever K is
+    // (the bound of the accepted shapes), of the padded width beyond
+    const int nsp_bound = nsp < kWave * 8 ? kWave * 8 : nsp;
+    if ((size_t)kGradWaves * (C + 4 + 2 * nsp_bound) * sizeof(float) > kMaxLds) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
     BlankParams p;
     p.lp = log_probs; p.st = stride_t; p.sb = stride_b;
     p.tgt = targets; p.tgt64 = targets_i64;
@@ -1726,10 +1568,11 @@ extern "C" int ctc_amd_blank_loss_grad(const float *log_probs, int64_t stride_t,
     p.loss_scale = loss_scale; p.grad_scale = grad_scale;
     p.nll = nll; p.loss = loss; p.grad = grad;
     p.counter = static_cast<unsigned *>(workspace);
+    blank_layout(p, nsp);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (wide) return run_blank_wide(p, s);                                    // whatever ctc_amd_blank_set_schedule says
-    if (ns <= kWave * 2) return run_blank<2>(p, s);
-    if (ns <= kWave * 4) return run_blank<4>(p, s);
+    if (nsp > kWave * 8) return run_blank_wide(p, s);                         // S > 255, whatever ctc_amd_blank_set_schedule says
+    if (nsp == kWave * 2) return run_blank<2>(p, s);
+    if (nsp == kWave * 4) return run_blank<4>(p, s);
     return run_blank<8>(p, s);
 }
 

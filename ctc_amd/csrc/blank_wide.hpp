@@ -17,6 +17,7 @@ namespace ctc {
 
 constexpr int kWideK = 8;                            // states per lane
 constexpr int kWideSpan = kWave * kWideK;            // states per wave / per pass of a gradient wave
+static_assert(kWideSpan == kWave * 8, "blank_padded_states pads to this");
 constexpr int kWideMaxWaves = 4;                     // 2047 states
 constexpr int kWideNxtBits = 12;                     // packed state table of a gradient wave: class << 12 | next + 1
 
@@ -32,22 +33,7 @@ __global__ __launch_bounds__(256) void blank_wide_gather_kernel(BlankParams p, i
     const int n = 2 * L + 1;
     if (tid == 0) s_cls[p.NSP] = 0;
     blank_classes(p, b, n, s_cls);
-    for (int s = blockIdx.x * blockDim.x + tid; s < p.NSP; s += gridDim.x * blockDim.x) {
-        const int c = s_cls[s];
-        p.cls[b * p.NSP + s] = c;
-        const bool label = s < n && (s & 1);
-        int nx = -1, fi = label ? 1 : 0;
-        if (label) {
-#pragma unroll 8
-            for (int s2 = 1; s2 < n; s2 += 2) {              // (no early exit: see blank_tables)
-                const bool same = s_cls[s2] == c;
-                if (same && s2 < s) fi = 0;
-                if (same && s2 > s && nx < 0) nx = s2;
-            }
-        }
-        p.nxt[b * p.NSP + s] = nx;
-        p.first[b * p.NSP + s] = fi;
-    }
+    for (int s = blockIdx.x * blockDim.x + tid; s < p.NSP; s += gridDim.x * blockDim.x) blank_table_entry(p, b, n, s, s_cls);
     if (blockIdx.x == 0) {                                   // an alignment needs one step per label plus a blank
         int rep = 0;                                         // between every two equal neighbours
         for (int l = 1 + tid; l < L; l += blockDim.x) rep += s_cls[2 * l + 1] == s_cls[2 * l - 1] ? 1 : 0;
@@ -60,7 +46,7 @@ __global__ __launch_bounds__(256) void blank_wide_gather_kernel(BlankParams p, i
     for (int t = t_begin; t < t_end; ++t) {
         const float *row = p.lp + (int64_t)t * p.st + (int64_t)b * p.sb;
         float *out = p.em + ((int64_t)b * p.T + t) * p.NSP;
-        for (int s = tid; s < p.NSP; s += blockDim.x) out[s] = s < n ? fmaxf(row[s_cls[s]] * kLog2e, kNegB) : kNegB;
+        for (int s = tid; s < p.NSP; s += blockDim.x) out[s] = s < n ? blank_emission(row[s_cls[s]]) : kNegB;
     }
 }
 
@@ -110,14 +96,7 @@ __device__ __forceinline__ void blank_wide_chain(const BlankParams &p, int b, in
     const float *em = p.em + (int64_t)b * p.T * p.NSP + s0;
     float *out = (FWD ? p.al : p.be) + (int64_t)b * p.T * p.NSP + s0;
     bool skip[K];
-    {
-        const int *cls = p.cls + b * p.NSP;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int s = s0 + k, s2 = FWD ? s - 2 : s + 2;
-            skip[k] = (s & 1) && s2 >= 0 && s2 < n && cls[s] != cls[s2];
-        }
-    }
+    blank_state_flags<K, FWD>(p, b, n, s0, skip);
     const int from = FWD ? w - 1 : w + 1;                    // the wave whose edge this one needs, and the one that
     const bool hears = from >= 0 && from < W;                // needs this one's
     const bool tells = FWD ? w + 1 < W : w > 0;
@@ -153,12 +132,7 @@ __device__ __forceinline__ void blank_wide_chain(const BlankParams &p, int b, in
     {
         float e0[K];
         fetch(e0, 0);
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int s = s0 + k;
-            const bool entry = FWD ? (s == 0 || s == 1) : (s == n - 1 || s == n - 2);
-            a[k] = (entry && s < n) ? e0[k] : kNegB;
-        }
+        blank_first<K, FWD>(a, e0, n, s0);
         if (!FWD) pb0 = lse2_2(a[0], a[1]);
         hand_on(0);
     }
@@ -224,7 +198,8 @@ __global__ __launch_bounds__(kWideMaxWaves * kWave) void blank_wide_chain_kernel
 }
 
 // ---- gamma -> gradient rows -----------------------------------------------------------------------------
-// blank_row_finish of the narrow path with the row's states in W passes of 64 x 8.  Per wave in LDS: occ[C4],
+// blank_row_emit of the narrow path with the row's states in W passes of 64 x 8 (the zero rows and the dense row
+// are the narrow path's own: blank_row_fill, blank_row_dense).  Per wave in LDS: occ[C4],
 // gam[NSP] and the sample's packed state table tab[NSP] (class << 12 | next state of that class + 1; 0 ends the
 // chain); which of a lane's 8 W states are the first of their class is a bit mask in a register.
 template <int W, bool VEC4>
@@ -245,13 +220,8 @@ __global__ __launch_bounds__(kGradWaves * kWave) void blank_wide_grad_kernel(Bla
         const int b = __builtin_amdgcn_readfirstlane(idx - t * p.B);
         const int2 meta = p.meta[b];
         const int Te = __builtin_amdgcn_readfirstlane(meta.x), L = __builtin_amdgcn_readfirstlane(meta.y);
-        float *g = p.grad + ((int64_t)t * p.B + b) * p.C;
         if (t >= Te) {                                       // beyond T_b, or no alignment: a zero row
-            if (VEC4) {
-                for (int q = lane; q < (p.C >> 2); q += kWave) stream_store(reinterpret_cast<float4 *>(g) + q, make_float4(0.f, 0.f, 0.f, 0.f));
-            } else {
-                for (int c = lane; c < p.C; c += kWave) stream_store(&g[c], 0.f);
-            }
+            blank_row_fill<VEC4>(p, t, b, 0.f);
             continue;
         }
         const int n = 2 * L + 1;
@@ -329,25 +299,7 @@ __global__ __launch_bounds__(kGradWaves * kWave) void blank_wide_grad_kernel(Bla
                 }
             }
         }
-        const float gs = p.grad_scale / (float)(L > 1 ? L : 1);
-        if (VEC4) {
-#pragma unroll
-            for (int i = 0; i < kMaxV4; ++i) {
-                const int q = lane + kWave * i;
-                if (q < (p.C >> 2)) {
-                    const float4 oc = reinterpret_cast<const float4 *>(occ)[q];
-                    float4 out;
-                    out.x = (fast_exp(xr[i].x) - oc.x) * gs;
-                    out.y = (fast_exp(xr[i].y) - oc.y) * gs;
-                    out.z = (fast_exp(xr[i].z) - oc.z) * gs;
-                    out.w = (fast_exp(xr[i].w) - oc.w) * gs;
-                    stream_store(reinterpret_cast<float4 *>(g) + q, out);
-                }
-            }
-        } else {
-            const float *row = p.lp + (int64_t)t * p.st + (int64_t)b * p.sb;
-            for (int c = lane; c < p.C; c += kWave) stream_store(&g[c], (fast_exp(row[c]) - occ[c]) * gs);
-        }
+        blank_row_dense<VEC4>(p, t, b, xr, occ, p.grad_scale / (float)(L > 1 ? L : 1));
         // un-set only what this row touched
         if (lane == 0) occ[p.blank] = 0.f;
 #pragma unroll
@@ -361,44 +313,21 @@ __global__ __launch_bounds__(kGradWaves * kWave) void blank_wide_grad_kernel(Bla
     }
 }
 
-// the launches; p.S > 255 (the caller has checked 2S+1 <= 2047 and the LDS of a gradient wave)
+// the launches; p.S > 255 (the caller has checked 2S+1 <= 2047 and the LDS of a gradient wave, and laid out the
+// workspace: p.NSP = 512 W; the hand-off state in it stays unused, the persistent launch is not taken)
 static int run_blank_wide(BlankParams &p, hipStream_t s)
 {
-    const int W = (2 * p.S + 1 + kWideSpan - 1) / kWideSpan;
-    p.NSP = kWideSpan * W;
-    const size_t lattice = (size_t)p.B * p.T * p.NSP;        // the layout of run_blank (and of ctc_amd_workspace_bytes)
-    float *base = reinterpret_cast<float *>(reinterpret_cast<char *>(p.counter) + 256);
-    p.em = base;
-    p.al = base + lattice;
-    p.be = base + 2 * lattice;
-    p.cls = reinterpret_cast<int *>(base + 3 * lattice);
-    p.nxt = p.cls + (size_t)p.B * p.NSP;
-    p.first = p.nxt + (size_t)p.B * p.NSP;
-    p.meta = reinterpret_cast<int2 *>(p.first + (size_t)p.B * p.NSP);
-    p.Bp = (p.B + 63) & ~63;
-    p.sync = nullptr;                                        // no hand-off state: the persistent launch is not taken
-    p.chunk = nullptr;
-    p.nsync = p.nchunk = 0;
-    p.debug = 0;
-    const bool vec4 = (p.C % 4 == 0) && p.C <= 4 * kWave * kMaxV4 && (p.st % 4 == 0) && (p.sb % 4 == 0) &&
-                      (reinterpret_cast<uintptr_t>(p.lp) % 16 == 0) && (reinterpret_cast<uintptr_t>(p.grad) % 16 == 0);
+    const int W = p.NSP / kWideSpan;
+    const bool vec4 = blank_rows_vec4(p);
     const int rows_per_block = 8;
     const dim3 ggrid((p.T + rows_per_block - 1) / rows_per_block, p.B);
     int rc = launch<blank_wide_gather_kernel>(ggrid, dim3(256), (p.NSP + 1) * sizeof(int), s, p, rows_per_block);
     if (rc) return rc;
     rc = launch<blank_wide_chain_kernel>(dim3(p.B, p.grad ? 2 : 1), dim3(W * kWave), 0, s, p);
     if (rc || !p.grad) return rc;
-    const int total = p.T * p.B;
-    int blocks = (total + kGradWaves - 1) / kGradWaves;
-    if (blocks > 256 * 8) blocks = 256 * 8;
-    const size_t lds = kGradWaves * (size_t)(((p.C + 3) & ~3) + 2 * p.NSP) * sizeof(float);
-    const dim3 grid(blocks), block(kGradWaves * kWave);
-    if (W == 2) return vec4 ? launch<blank_wide_grad_kernel<2, true>>(grid, block, lds, s, p, total)
-                            : launch<blank_wide_grad_kernel<2, false>>(grid, block, lds, s, p, total);
-    if (W == 3) return vec4 ? launch<blank_wide_grad_kernel<3, true>>(grid, block, lds, s, p, total)
-                            : launch<blank_wide_grad_kernel<3, false>>(grid, block, lds, s, p, total);
-    return vec4 ? launch<blank_wide_grad_kernel<4, true>>(grid, block, lds, s, p, total)
-                : launch<blank_wide_grad_kernel<4, false>>(grid, block, lds, s, p, total);
+    if (W == 2) return blank_launch_grad<blank_wide_grad_kernel<2, true>, blank_wide_grad_kernel<2, false>>(p, vec4, s);
+    if (W == 3) return blank_launch_grad<blank_wide_grad_kernel<3, true>, blank_wide_grad_kernel<3, false>>(p, vec4, s);
+    return blank_launch_grad<blank_wide_grad_kernel<4, true>, blank_wide_grad_kernel<4, false>>(p, vec4, s);
 }
 
 }  // namespace ctc
