@@ -51,6 +51,8 @@ PROTOTYPES = {
     "ctc_amd_binary_best_path": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _int, _int, _int, _int, _vp, _vp, _vp, _vp]),
     "ctc_amd_blank_best_path": (_int, [_vp, _i64, _i64, _vp, _int, _vp, _vp, _int, _int, _int, _int, _int,
                                        _vp, _vp, _vp, _vp]),
+    "ctc_amd_blank_best_path_wide": (_int, [_vp, _i64, _i64, _vp, _int, _vp, _vp, _int, _int, _int, _int, _int,
+                                            _vp, _vp, _vp, _vp]),
     "ctc_amd_noblank_posteriors": (_int, [_vp, _i64, _i64, _vp, _int, _vp, _vp, _int, _int, _int, _int,
                                           _vp, _vp, _vp, _vp]),
     "ctc_amd_blank_posteriors": (_int, [_vp, _i64, _i64, _vp, _int, _vp, _vp, _int, _int, _int, _int, _int,

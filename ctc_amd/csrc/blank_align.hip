@@ -19,6 +19,8 @@
 //                               are 2 bits per state and step, packed per lane into one 32-bit word per 16/K steps
 //                               (16 K bytes per step): in LDS while they fit, in the workspace beyond.  Wave 0 then
 //                               walks them back with one readlane per step and writes the path 64 steps per store.
+// These take 2S+1 <= 512 states (S <= 255); blank_align_wide.hpp, included below, takes 513..2047 with several waves
+// per sample (ctc_amd_blank_best_path_wide).
 #include "common.hpp"
 #include "launch.hpp"
 
@@ -752,7 +754,28 @@ static int run_blank_post(PostParams &pp, hipStream_t s)
 
 }  // namespace ctc
 
+#include "blank_align_wide.hpp"
+
 using namespace ctc;
+
+extern "C" int ctc_amd_blank_best_path_wide(const float *log_probs, int64_t stride_t, int64_t stride_b,
+                                            const void *targets, int targets_i64,
+                                            const int64_t *in_len, const int64_t *tgt_len,
+                                            int T, int B, int C, int S, int blank,
+                                            int32_t *path, float *score, void *workspace, void *stream)
+{
+    if (!log_probs || !targets || !in_len || !tgt_len || !path || !score || !workspace) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (T < 1 || B < 1 || C < 1 || S < 1 || blank < 0 || blank >= C) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (S < 256 || S > 1023) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;           // 513 <= 2S+1 <= 2047: two to four waves of 512
+    AlignParams p;
+    p.lp = log_probs; p.st = stride_t; p.sb = stride_b;
+    p.tgt = targets; p.tgt64 = targets_i64;
+    p.in_len = in_len; p.tgt_len = tgt_len;
+    p.T = T; p.B = B; p.C = C; p.S = S; p.blank = blank;
+    p.path = path; p.score = score;
+    p.counter = static_cast<unsigned *>(workspace);
+    return run_blank_align_wide(p, static_cast<hipStream_t>(stream));
+}
 
 extern "C" int ctc_amd_blank_best_path(const float *log_probs, int64_t stride_t, int64_t stride_b,
                                        const void *targets, int targets_i64,

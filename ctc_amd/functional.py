@@ -134,7 +134,8 @@ def collective_gate(variant, batch, device=None, launch_stream=None, timeout_us=
     return True
 
 
-BLANK_MAX_LABELS = 1023            # ctc_amd_blank_loss_grad: S <= 1023; the blank read-outs stop at 255 (include/ctc_amd.h)
+BLANK_MAX_LABELS = 1023            # ctc_amd_blank_loss_grad and the best path: S <= 1023; the posteriors stop at 255
+BLANK_NARROW_LABELS = 255          # beyond: the wide entries (ctc_amd_blank_best_path_wide; include/ctc_amd.h)
 
 
 def set_blank_schedule(mode):
@@ -487,7 +488,8 @@ def blank_ctc_loss(log_probs, targets, input_lengths, target_lengths, blank=0, b
     """-> (loss, nll[B]); torch.nn.CTCLoss(blank, reduction='mean', zero_infinity=False)
     semantics (models/layers/AsyncTFCriterion.py:198): log_probs are normalised
     log-probabilities, loss = mean_b(nll_b / max(L_b,1)).  ``targets`` [B,S] with S <= 1023 label columns
-    (CtcAmdError beyond); more than 255 columns take the wide lattice path of the library (several waves per chain)."""
+    (CtcAmdError beyond); more than 255 columns take the wide lattice path of the library (several waves per chain).
+    ``blank_best_path`` / ``blank_forced_align`` take the same widths; ``blank_posteriors`` stays at S <= 255."""
     return _LossFn.apply(log_probs, targets, input_lengths, target_lengths, _lib.BLANK, batch_total, blank)
 
 
@@ -573,10 +575,17 @@ def blank_best_path(log_probs, targets, input_lengths, target_lengths, blank=0):
     Same inputs as ``blank_ctc_loss``: ``log_probs`` [T,B,C] normalised log-probabilities (used as given),
     ``targets`` [B,S] int32/int64.  ``path[b,t]`` is the extended-label STATE s_t (even = blank, odd s = label
     (s-1)//2 of targets[b]) for ``t < T_b``, -1 beyond ``T_b`` and for samples with no alignment; ``score[b]`` the
-    log-probability of that alignment (-inf when none exists).  S <= 255 label columns: the read-outs did not follow
-    the loss to the wide lattice (S <= 1023) and raise CtcAmdError beyond.  include/ctc_amd.h: ctc_amd_blank_best_path.
+    log-probability of that alignment (-inf when none exists).  S <= 1023 label columns, as the loss (CtcAmdError
+    beyond): up to 255 columns ctc_amd_blank_best_path runs, 256..1023 take ctc_amd_blank_best_path_wide (several
+    waves per sample; the same arithmetic, the same bits for a sample whichever entry serves it).  include/ctc_amd.h.
     """
-    return _readout("ctc_amd_blank_best_path", _lib.BLANK, log_probs, "log_probs", targets, input_lengths,
+    S = targets.shape[1] if isinstance(targets, torch.Tensor) and targets.dim() == 2 else 0   # (_readout validates)
+    if S > BLANK_MAX_LABELS:
+        raise _lib.CtcAmdError(
+            "ctc_amd: the blank CTC best path takes targets of at most %d label columns (2S+1 <= %d lattice states), "
+            "got S=%d" % (BLANK_MAX_LABELS, 2 * BLANK_MAX_LABELS + 1, S))
+    entry = "ctc_amd_blank_best_path_wide" if S > BLANK_NARROW_LABELS else "ctc_amd_blank_best_path"
+    return _readout(entry, _lib.BLANK, log_probs, "log_probs", targets, input_lengths,
                     target_lengths, None, torch.int32, extra=(int(blank),))
 
 
@@ -586,8 +595,8 @@ def blank_forced_align(log_probs, targets, input_lengths, target_lengths, blank=
 
     ``tokens[b,t]`` is the class of the best path's state at frame t (``blank`` or the target label), -1 beyond
     ``T_b`` / without an alignment; ``frame_scores[b,t] = log_probs[t,b,tokens[b,t]]`` (0 where tokens is -1), so
-    that their sum over t in order is ``blank_best_path``'s score.  Derived on the device from the path, so S <= 255
-    label columns as there (the loss itself takes up to 1023)."""
+    that their sum over t in order is ``blank_best_path``'s score.  Derived on the device from the path, so S <= 1023
+    label columns as there and as the loss."""
     path, _ = blank_best_path(log_probs, targets, input_lengths, target_lengths, blank)
     dev = path.device
     tg = targets.to(device=dev, dtype=torch.int64)
@@ -609,7 +618,8 @@ def blank_posteriors(log_probs, targets, input_lengths, target_lengths, blank=0)
     (even s = blank, odd s = label (s-1)//2 of targets[b]); rows sum to 1 for ``t < T_b``, and are 0 for ``t >= T_b``,
     for ``s > 2 L_b`` and for samples with no alignment (``nll`` +inf, as ``blank_ctc_loss`` reports it).  Not
     differentiable.  ``gamma[b, t, path[b, t]]`` with ``blank_best_path``'s path is the confidence of each aligned
-    frame.  S <= 255 label columns (CtcAmdError beyond; the loss itself takes up to 1023).
+    frame.  The posteriors stay at S <= 255 label columns (CtcAmdError beyond), where the loss and
+    ``blank_best_path`` take up to 1023: their rescaling has not been carried across several waves.
     include/ctc_amd.h: ctc_amd_blank_posteriors.
     """
     return _readout("ctc_amd_blank_posteriors", _lib.BLANK, log_probs, "log_probs", targets, input_lengths,

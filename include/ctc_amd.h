@@ -33,7 +33,7 @@ extern "C" {
 #define CTC_AMD_ABI_VERSION 2
 
 #define CTC_AMD_ERR_BAD_ARGUMENT      (-1)  /* null pointer, non-positive size ... */
-#define CTC_AMD_ERR_UNSUPPORTED_SHAPE (-2)  /* S > 256 (blank-CTC: 1023 for the loss, 255 for its read-outs); binary: T*S beyond LDS */
+#define CTC_AMD_ERR_UNSUPPORTED_SHAPE (-2)  /* S > 256 (blank-CTC: 1023 for the loss and the best path, 255 for the posteriors); binary: T*S beyond LDS */
 #define CTC_AMD_ERR_CODE_OVERFLOW     (-3)  /* target dedup in the reference's int32 row codes with C > 64: the
                                              * reference raises OverflowError there (2**o at o >= 64) */
 
@@ -139,8 +139,8 @@ int ctc_amd_binary_loss_grad(const float *x, int64_t stride_t, int64_t stride_b,
  * S <= 255).  Up to 255 labels a chain is one wave; 256..1023 labels take the WIDE path: three launches, a chain
  * spread over 2..4 waves of one workgroup (512 states each, NSP = 512 ceil((2S+1)/512)) that hand their edge states
  * on through LDS with one workgroup barrier per step -- no polling, so no bounded wait and no status bit there;
- * ctc_amd_blank_set_schedule() does not apply to it.  Everything else in this comment holds for both.  The read-outs
- * below (best path, posteriors) stop at S = 255.
+ * ctc_amd_blank_set_schedule() does not apply to it.  Everything else in this comment holds for both.  Of the read-outs
+ * below the best path follows to S = 1023 (ctc_amd_blank_best_path_wide); the posteriors stop at S = 255.
  * Long sequences (T >= 256) on batches of #CUs/11..#CUs/2 samples with >= 4 lattice states per lane and
  * B*C >= 16384 (BASELINE config 5 and its neighbourhood) run as ONE persistent
  * launch of at most one workgroup per CU in which workgroups wait for each other (bounded: a wait
@@ -242,13 +242,34 @@ int ctc_amd_binary_best_path(const float *x, int64_t stride_t, int64_t stride_b,
  *         v(2L) > v(2L-1), else 2L-1; 0 when L = 0), -1 for t >= T_b and for samples with no alignment
  *   score [B]   out: v of the final state (-inf: no alignment -- too short for L plus its adjacent repeats)
  * workspace: at least ctc_amd_workspace_bytes(CTC_AMD_BLANK, T, B, C, S) bytes; the 256-byte header is left alone
- * except for status bit 8.  S <= 255 (CTC_AMD_ERR_UNSUPPORTED_SHAPE beyond: the loss's wide path up to S = 1023 has no
- * read-out twin), any T (back-pointers beyond LDS go to the workspace). */
+ * except for status bit 8.  S <= 255 (CTC_AMD_ERR_UNSUPPORTED_SHAPE beyond: 256..1023 label columns are
+ * ctc_amd_blank_best_path_wide's), any T (back-pointers beyond LDS go to the workspace). */
 int ctc_amd_blank_best_path(const float *log_probs, int64_t stride_t, int64_t stride_b,
                             const void *targets, int targets_i64,
                             const int64_t *in_len, const int64_t *tgt_len,
                             int T, int B, int C, int S, int blank,
                             int32_t *path, float *score, void *workspace, void *stream);
+
+/* ctc_amd_blank_best_path for 256 <= S <= 1023 label columns (513 <= 2S+1 <= 2047 lattice states, the widths of
+ * ctc_amd_blank_loss_grad's wide path; CTC_AMD_ERR_UNSUPPORTED_SHAPE outside that range -- S <= 255 is the entry
+ * above).  The same inputs, the same contract and the same arithmetic step for step: v_t(s) with the candidates in
+ * the order stay, advance, skip, a later one taken only when strictly greater, one fp32 add per step in natural log,
+ * -inf kept; the final state is 2L when v(2L) > v(2L-1), else 2L-1 (0 when L = 0).  A sample's path and score do not
+ * depend on which of the two entries served it (L_b <= 255 inside a wide call included).
+ *   path  [B,T] int32 out: state s_t for t < T_b, -1 for t >= T_b and for samples with no alignment
+ *   score [B]   out: v of the final state (-inf: no alignment)
+ * Null pointers, T, B, C, S < 1 and a blank outside [0, C) return CTC_AMD_ERR_BAD_ARGUMENT before anything is
+ * dereferenced or launched.  One workgroup of ceil((2S+1)/512) waves per sample; the waves hand their edge state on
+ * through LDS with one workgroup barrier per step -- no polling, so no bounded wait, and no status bit is ever set.
+ * workspace: at least ctc_amd_workspace_bytes(CTC_AMD_BLANK, T, B, C, S) bytes; only the lattice areas behind the
+ * 256-byte header are written (the emission table and the back-pointers: (288 W + 4) of their 1536 W words per
+ * (b, t), W = ceil((2S+1)/512)), not the header and not the loss's state tables and hand-off words behind the areas.
+ * Any T.  Deterministic. */
+int ctc_amd_blank_best_path_wide(const float *log_probs, int64_t stride_t, int64_t stride_b,
+                                 const void *targets, int targets_i64,
+                                 const int64_t *in_len, const int64_t *tgt_len,
+                                 int T, int B, int C, int S, int blank,
+                                 int32_t *path, float *score, void *workspace, void *stream);
 
 /* Per-frame state posteriors on the blank-CTC lattice: gamma_t(s) = P(state s at frame t | log_probs, targets), the soft
  * alignment beside ctc_amd_blank_best_path's hard one.  Inputs: the same layout and contract as ctc_amd_blank_loss_grad
