@@ -518,20 +518,22 @@ struct PostChain {
     double coff;                                 // alpha: the emission maxima c_t subtracted so far (natural log)
 
     // pre[] = log-sum-exp over the predecessors (alpha) / successors (beta) of each state; a label state's third term is
-    // folded into the neighbouring blank's two-term sum (as in blank.hip), so every state is one two-term LSE
-    __device__ __forceinline__ void pre(float (&q)[K]) const
+    // folded into the neighbouring blank's two-term sum (as in blank.hip), so every state is one two-term LSE.
+    // in_a / in_q: what the wave's edge lane takes from beyond the wave (blank_post_wide.hpp) -- alpha: the state below
+    // the wave's first; beta: the state above its last and that state's two-term sum
+    __device__ __forceinline__ void pre(float (&q)[K], float in_a = kPostNeg, float in_q = kPostNeg) const
     {
         if (FWD) {
-            const float nb1 = wave_shr1(a[K - 1], kPostNeg);
+            const float nb1 = wave_shr1(a[K - 1], in_a);
 #pragma unroll
             for (int k = 0; k < K; k += 2) q[k] = post_lse2(a[k], k ? a[k - 1] : nb1);
 #pragma unroll
             for (int k = 1; k < K; k += 2) q[k] = post_lse2(a[k], skip[k] ? q[k - 1] : a[k - 1]);
         } else {
-            const float n1 = wave_shl1(a[0], kPostNeg);
+            const float n1 = wave_shl1(a[0], in_a);
 #pragma unroll
             for (int k = 0; k < K; k += 2) q[k] = post_lse2(a[k], a[k + 1]);
-            const float nb = wave_shl1(q[0], kPostNeg);
+            const float nb = wave_shl1(q[0], in_q);
 #pragma unroll
             for (int k = 1; k < K; k += 2)
                 q[k] = post_lse2(a[k], skip[k] ? (k + 1 < K ? q[k + 1] : nb) : (k + 1 < K ? a[k + 1] : n1));
@@ -555,17 +557,28 @@ struct PostChain {
         }
     }
 
-    // subtract the row maximum (when anything is reachable); clamp what is not at kPostNeg
-    __device__ __forceinline__ void rescale()
+    // the maximum of the wave's states (wave-uniform)
+    __device__ __forceinline__ float state_max() const
     {
         float mx = a[0];
 #pragma unroll
         for (int k = 1; k < K; ++k) mx = vmax(mx, a[k]);
-        float m = wave_max(mx);
-        m = m > kPostLive ? m : 0.f;
+        return wave_max(mx);
+    }
+
+    // subtract m from every state; clamp what is not reachable at kPostNeg
+    __device__ __forceinline__ void subtract(float m)
+    {
 #pragma unroll
         for (int k = 0; k < K; ++k) a[k] = vmax(a[k] - m, kPostNeg);
         if (FWD) off += (double)m;
+    }
+
+    // subtract the row maximum (when anything is reachable)
+    __device__ __forceinline__ void rescale()
+    {
+        const float m = state_max();
+        subtract(m > kPostLive ? m : 0.f);
     }
 
     __device__ __forceinline__ void step(const AlignRow<K> &e, float c, float *dst, bool st)
@@ -755,6 +768,7 @@ static int run_blank_post(PostParams &pp, hipStream_t s)
 }  // namespace ctc
 
 #include "blank_align_wide.hpp"
+#include "blank_post_wide.hpp"
 
 using namespace ctc;
 
@@ -822,4 +836,24 @@ extern "C" int ctc_amd_blank_posteriors(const float *log_probs, int64_t stride_t
     if (ns <= kWave * 2) return run_blank_post<2>(pp, s);
     if (ns <= kWave * 4) return run_blank_post<4>(pp, s);
     return run_blank_post<8>(pp, s);
+}
+
+extern "C" int ctc_amd_blank_posteriors_wide(const float *log_probs, int64_t stride_t, int64_t stride_b,
+                                             const void *targets, int targets_i64,
+                                             const int64_t *in_len, const int64_t *tgt_len,
+                                             int T, int B, int C, int S, int blank,
+                                             float *nll, float *gamma, void *workspace, void *stream)
+{
+    if (!log_probs || !targets || !in_len || !tgt_len || !nll || !gamma || !workspace) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (T < 1 || B < 1 || C < 1 || S < 1 || blank < 0 || blank >= C) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (S < 256 || S > 1023) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;           // 513 <= 2S+1 <= 2047: two to four waves of 512
+    PostParams pp = {};
+    AlignParams &p = pp.a;
+    p.lp = log_probs; p.st = stride_t; p.sb = stride_b;
+    p.tgt = targets; p.tgt64 = targets_i64;
+    p.in_len = in_len; p.tgt_len = tgt_len;
+    p.T = T; p.B = B; p.C = C; p.S = S; p.blank = blank;
+    p.counter = static_cast<unsigned *>(workspace);
+    pp.nll = nll; pp.gamma = gamma;
+    return run_blank_post_wide(pp, static_cast<hipStream_t>(stream));
 }

@@ -38,7 +38,8 @@ struct AlignWideParams {
 
 // ---- launch 1: the compact emission rows ---------------------------------------------------------
 // grid (ceil(T / (4 * kWideAlignGatherRows)), B); a wave takes kWideAlignGatherRows rows, a row's 256 W + 1 columns dealt
-// over its lanes in M passes, all loads in flight at once
+// over its lanes in M passes, all loads in flight at once.  (blank_post_wide_gather_kernel in blank_post_wide.hpp is a
+// copy of this body plus the row maximum: a change to the table's layout goes into both.)
 template <int W>
 __global__ __launch_bounds__(kAlignGatherThreads) void blank_align_wide_gather_kernel(AlignWideParams q)
 {

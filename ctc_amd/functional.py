@@ -134,8 +134,8 @@ def collective_gate(variant, batch, device=None, launch_stream=None, timeout_us=
     return True
 
 
-BLANK_MAX_LABELS = 1023            # ctc_amd_blank_loss_grad and the best path: S <= 1023; the posteriors stop at 255
-BLANK_NARROW_LABELS = 255          # beyond: the wide entries (ctc_amd_blank_best_path_wide; include/ctc_amd.h)
+BLANK_MAX_LABELS = 1023            # ctc_amd_blank_loss_grad, the best path and the posteriors: S <= 1023
+BLANK_NARROW_LABELS = 255          # beyond: the wide entries (ctc_amd_blank_best_path_wide, ctc_amd_blank_posteriors_wide)
 
 
 def set_blank_schedule(mode):
@@ -489,7 +489,7 @@ def blank_ctc_loss(log_probs, targets, input_lengths, target_lengths, blank=0, b
     semantics (models/layers/AsyncTFCriterion.py:198): log_probs are normalised
     log-probabilities, loss = mean_b(nll_b / max(L_b,1)).  ``targets`` [B,S] with S <= 1023 label columns
     (CtcAmdError beyond); more than 255 columns take the wide lattice path of the library (several waves per chain).
-    ``blank_best_path`` / ``blank_forced_align`` take the same widths; ``blank_posteriors`` stays at S <= 255."""
+    ``blank_best_path`` / ``blank_forced_align`` and ``blank_posteriors`` take the same widths."""
     return _LossFn.apply(log_probs, targets, input_lengths, target_lengths, _lib.BLANK, batch_total, blank)
 
 
@@ -575,8 +575,8 @@ def blank_best_path(log_probs, targets, input_lengths, target_lengths, blank=0):
     Same inputs as ``blank_ctc_loss``: ``log_probs`` [T,B,C] normalised log-probabilities (used as given),
     ``targets`` [B,S] int32/int64.  ``path[b,t]`` is the extended-label STATE s_t (even = blank, odd s = label
     (s-1)//2 of targets[b]) for ``t < T_b``, -1 beyond ``T_b`` and for samples with no alignment; ``score[b]`` the
-    log-probability of that alignment (-inf when none exists).  S <= 1023 label columns, as the loss (CtcAmdError
-    beyond): up to 255 columns ctc_amd_blank_best_path runs, 256..1023 take ctc_amd_blank_best_path_wide (several
+    log-probability of that alignment (-inf when none exists).  S <= 1023 label columns, as the loss and
+    ``blank_posteriors`` (CtcAmdError beyond): up to 255 columns ctc_amd_blank_best_path runs, 256..1023 take ctc_amd_blank_best_path_wide (several
     waves per sample; the same arithmetic, the same bits for a sample whichever entry serves it).  include/ctc_amd.h.
     """
     S = targets.shape[1] if isinstance(targets, torch.Tensor) and targets.dim() == 2 else 0   # (_readout validates)
@@ -618,11 +618,17 @@ def blank_posteriors(log_probs, targets, input_lengths, target_lengths, blank=0)
     (even s = blank, odd s = label (s-1)//2 of targets[b]); rows sum to 1 for ``t < T_b``, and are 0 for ``t >= T_b``,
     for ``s > 2 L_b`` and for samples with no alignment (``nll`` +inf, as ``blank_ctc_loss`` reports it).  Not
     differentiable.  ``gamma[b, t, path[b, t]]`` with ``blank_best_path``'s path is the confidence of each aligned
-    frame.  The posteriors stay at S <= 255 label columns (CtcAmdError beyond), where the loss and
-    ``blank_best_path`` take up to 1023: their rescaling has not been carried across several waves.
-    include/ctc_amd.h: ctc_amd_blank_posteriors.
+    frame.  S <= 1023 label columns, as the loss and ``blank_best_path`` (CtcAmdError beyond): up to 255 columns
+    ctc_amd_blank_posteriors runs, 256..1023 take ctc_amd_blank_posteriors_wide (several waves per chain, one
+    rescaling for all of them).  include/ctc_amd.h.
     """
-    return _readout("ctc_amd_blank_posteriors", _lib.BLANK, log_probs, "log_probs", targets, input_lengths,
+    S = targets.shape[1] if isinstance(targets, torch.Tensor) and targets.dim() == 2 else 0   # (_readout validates)
+    if S > BLANK_MAX_LABELS:
+        raise _lib.CtcAmdError(
+            "ctc_amd: the blank CTC posteriors take targets of at most %d label columns (2S+1 <= %d lattice states), "
+            "got S=%d" % (BLANK_MAX_LABELS, 2 * BLANK_MAX_LABELS + 1, S))
+    entry = "ctc_amd_blank_posteriors_wide" if S > BLANK_NARROW_LABELS else "ctc_amd_blank_posteriors"
+    return _readout(entry, _lib.BLANK, log_probs, "log_probs", targets, input_lengths,
                     target_lengths, lambda S: 2 * S + 1, torch.float32, extra=(int(blank),))
 
 

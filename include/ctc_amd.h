@@ -33,7 +33,7 @@ extern "C" {
 #define CTC_AMD_ABI_VERSION 2
 
 #define CTC_AMD_ERR_BAD_ARGUMENT      (-1)  /* null pointer, non-positive size ... */
-#define CTC_AMD_ERR_UNSUPPORTED_SHAPE (-2)  /* S > 256 (blank-CTC: 1023 for the loss and the best path, 255 for the posteriors); binary: T*S beyond LDS */
+#define CTC_AMD_ERR_UNSUPPORTED_SHAPE (-2)  /* S > 256 (blank-CTC: 1023 for the loss, the best path and the posteriors); binary: T*S beyond LDS */
 #define CTC_AMD_ERR_CODE_OVERFLOW     (-3)  /* target dedup in the reference's int32 row codes with C > 64: the
                                              * reference raises OverflowError there (2**o at o >= 64) */
 
@@ -140,7 +140,8 @@ int ctc_amd_binary_loss_grad(const float *x, int64_t stride_t, int64_t stride_b,
  * spread over 2..4 waves of one workgroup (512 states each, NSP = 512 ceil((2S+1)/512)) that hand their edge states
  * on through LDS with one workgroup barrier per step -- no polling, so no bounded wait and no status bit there;
  * ctc_amd_blank_set_schedule() does not apply to it.  Everything else in this comment holds for both.  Of the read-outs
- * below the best path follows to S = 1023 (ctc_amd_blank_best_path_wide); the posteriors stop at S = 255.
+ * below the best path and the posteriors follow to S = 1023 (ctc_amd_blank_best_path_wide,
+ * ctc_amd_blank_posteriors_wide): one width limit for the loss, the alignment and the posteriors.
  * Long sequences (T >= 256) on batches of #CUs/11..#CUs/2 samples with >= 4 lattice states per lane and
  * B*C >= 16384 (BASELINE config 5 and its neighbourhood) run as ONE persistent
  * launch of at most one workgroup per CU in which workgroups wait for each other (bounded: a wait
@@ -287,13 +288,33 @@ int ctc_amd_blank_best_path_wide(const float *log_probs, int64_t stride_t, int64
  * nll), so gamma keeps its resolution at long T: within 5e-4 of float64 at T = 2000 (the loss's occupancies: ~1e-2).
  * workspace: at least ctc_amd_workspace_bytes(CTC_AMD_BLANK, T, B, C, S) bytes; only the lattice areas behind the
  * 256-byte header are written (not the loss's state tables and hand-off words behind them; the header is left alone
- * except for status bit 16).  S <= 255 (CTC_AMD_ERR_UNSUPPORTED_SHAPE beyond, also where the loss itself goes on to
- * S = 1023), any T.  Deterministic. */
+ * except for status bit 16).  S <= 255 (CTC_AMD_ERR_UNSUPPORTED_SHAPE beyond: 256..1023 label columns are
+ * ctc_amd_blank_posteriors_wide's), any T.  Deterministic. */
 int ctc_amd_blank_posteriors(const float *log_probs, int64_t stride_t, int64_t stride_b,
                              const void *targets, int targets_i64,
                              const int64_t *in_len, const int64_t *tgt_len,
                              int T, int B, int C, int S, int blank,
                              float *nll, float *gamma, void *workspace, void *stream);
+
+/* ctc_amd_blank_posteriors for 256 <= S <= 1023 label columns (513 <= 2S+1 <= 2047 lattice states, the widths of
+ * ctc_amd_blank_loss_grad's wide path and of ctc_amd_blank_best_path_wide; CTC_AMD_ERR_UNSUPPORTED_SHAPE outside that
+ * range -- S <= 255 is the entry above).  The same inputs, outputs and contract, the same arithmetic step for step.
+ * Null pointers, T, B, C, S < 1 and a blank outside [0, C) return CTC_AMD_ERR_BAD_ARGUMENT before anything is
+ * dereferenced or launched, and before the range of S is looked at.
+ * W = ceil((2S+1)/512) waves span a lattice row.  alpha and beta' run in two workgroups of W waves per sample; the
+ * waves hand their edge states on through LDS with one workgroup barrier per step -- no polling, so no bounded wait, and
+ * no status bit is ever set (bit 16 stays reserved).  What is subtracted from the chains is the same in every wave of a
+ * sample: the per-frame emission maximum is formed once per row by the gather launch, and the state maximum taken off
+ * every few steps is the maximum over all W waves (exchanged through LDS with a step's hand-off), so alpha' + beta' has
+ * no seam where two waves meet.  gamma is normalised per row over all 2S+1 states.
+ * workspace: at least ctc_amd_workspace_bytes(CTC_AMD_BLANK, T, B, C, S) bytes; only the lattice areas behind the
+ * 256-byte header are written (the emission table and the alpha' / beta' rows: (1280 W + 4) of their 1536 W words per
+ * (b, t)), not the header and not the loss's state tables and hand-off words behind the areas.  Any T.  Deterministic. */
+int ctc_amd_blank_posteriors_wide(const float *log_probs, int64_t stride_t, int64_t stride_b,
+                                  const void *targets, int targets_i64,
+                                  const int64_t *in_len, const int64_t *tgt_len,
+                                  int T, int B, int C, int S, int blank,
+                                  float *nll, float *gamma, void *workspace, void *stream);
 
 /* Target construction: the dedup step of the reference's dataset preparation,
  * datasets/charades_ctc_next_pred.py:646-651,663-678 (same code at :503-505,523-531) -- out[b] = the rows of

@@ -7,8 +7,8 @@ the same process.
 Routes, per shape T x B x C x S (synth_blank inputs, full-length samples):
     best_path   ctc_amd_blank_best_path (S <= 255) or ctc_amd_blank_best_path_wide (256 <= S <= 1023): path [B,T] int32
                 + score [B]
-    posteriors  ctc_amd_blank_posteriors: gamma [B,T,2S+1] fp32 + nll [B]; S <= 255 only -- a wider shape runs the routes
-                that exist at its S, and gamma is not allocated
+    posteriors  ctc_amd_blank_posteriors (S <= 255) or ctc_amd_blank_posteriors_wide (256 <= S <= 1023): gamma
+                [B,T,2S+1] fp32 + nll [B]
     loss_grad   ctc_amd_blank_loss_grad: nll, loss and the whole input gradient (the library's own schedule)
 Each route is captured into a hipGraph of --per-graph back-to-back calls (no host launch cost in the number); after a
 warm-up the graph is replayed --reps times and the MEDIAN per call is reported (device events), with min and max.
@@ -35,11 +35,10 @@ def routes(T, B, C, S, dev, lib):
     lp, tgt, Tb, L = lp.to(dev), tgt.to(dev), Tb.to(dev), L.to(dev)
     need = lib.ctc_amd_workspace_bytes(_lib.BLANK, T, B, C, S)
     ws_a = torch.zeros(need, dtype=torch.uint8, device=dev)
-    narrow = S <= 255                                    # the posteriors and the narrow best-path entry stop there
-    if narrow:
-        ws_p = torch.zeros(need, dtype=torch.uint8, device=dev)
-        gamma = torch.empty((B, T, 2 * S + 1), device=dev)
-        pnll = torch.empty(B, device=dev)
+    narrow = S <= 255                                    # the narrow entries stop there
+    ws_p = torch.zeros(need, dtype=torch.uint8, device=dev)
+    gamma = torch.empty((B, T, 2 * S + 1), device=dev)
+    pnll = torch.empty(B, device=dev)
     ws_l = torch.zeros(need, dtype=torch.uint8, device=dev)
     path = torch.empty((B, T), dtype=torch.int32, device=dev)
     score = torch.empty(B, device=dev)
@@ -55,17 +54,17 @@ def routes(T, B, C, S, dev, lib):
         return entry(lp.data_ptr(), st, sb, tgt.data_ptr(), 1, Tb.data_ptr(), L.data_ptr(),
                      T, B, C, S, 0, path.data_ptr(), score.data_ptr(), ws_a.data_ptr(), stream)
 
+    pentry = lib.ctc_amd_blank_posteriors if narrow else lib.ctc_amd_blank_posteriors_wide
+
     def posteriors(stream):
-        return lib.ctc_amd_blank_posteriors(lp.data_ptr(), st, sb, tgt.data_ptr(), 1, Tb.data_ptr(), L.data_ptr(),
-                                            T, B, C, S, 0, pnll.data_ptr(), gamma.data_ptr(), ws_p.data_ptr(), stream)
+        return pentry(lp.data_ptr(), st, sb, tgt.data_ptr(), 1, Tb.data_ptr(), L.data_ptr(),
+                      T, B, C, S, 0, pnll.data_ptr(), gamma.data_ptr(), ws_p.data_ptr(), stream)
 
     def loss_grad(stream):
         return lib.ctc_amd_blank_loss_grad(lp.data_ptr(), st, sb, tgt.data_ptr(), 1, Tb.data_ptr(), L.data_ptr(),
                                            T, B, C, S, 0, sc, sc, nll.data_ptr(), loss.data_ptr(), grad.data_ptr(),
                                            ws_l.data_ptr(), stream)
 
-    if not narrow:
-        return {"best_path": best_path, "loss_grad": loss_grad}
     return {"best_path": best_path, "posteriors": posteriors, "loss_grad": loss_grad}
 
 
