@@ -5,7 +5,7 @@ Drop-in for the loss path of gotaku6629/CTC: ``CTCLoss.apply`` plus ``NoBlankCTC
 """
 from ._lib import CtcAmdError, SO_PATH  # noqa: F401
 from .functional import (CTCLoss, binary_best_path, binary_ctc_loss, binary_posteriors, blank_best_path, blank_ctc_loss,  # noqa: F401
-                         blank_posteriors,
+                         blank_posteriors, blank_token_spans, BlankTokenSpans,
                          blank_forced_align, check_status, collective_gate,
                          dedup_multihot_targets,
                          noblank_best_path, noblank_ctc_loss, noblank_posteriors, release_workspaces, set_blank_schedule,
@@ -16,4 +16,4 @@ from .producer import LSTM_cell, head_forward, lstm_cell_step, lstm_series  # no
 __all__ = ["CTCLoss", "NoBlankCTC", "NoBlankBinaryCTC", "BlankCTC", "noblank_ctc_loss",
            "binary_ctc_loss", "blank_ctc_loss", "noblank_best_path", "noblank_posteriors", "CtcAmdError",
            "workspace_status", "release_workspaces", "check_status", "set_blank_schedule", "dedup_multihot_targets", "collective_gate", "LSTM_cell", "head_forward", "lstm_cell_step", "lstm_series", "binary_posteriors", "binary_best_path",
-           "blank_best_path", "blank_forced_align", "blank_posteriors"]
+           "blank_best_path", "blank_forced_align", "blank_posteriors", "blank_token_spans", "BlankTokenSpans"]

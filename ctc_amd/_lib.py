@@ -59,6 +59,8 @@ PROTOTYPES = {
                                         _vp, _vp, _vp, _vp]),
     "ctc_amd_blank_posteriors_wide": (_int, [_vp, _i64, _i64, _vp, _int, _vp, _vp, _int, _int, _int, _int, _int,
                                              _vp, _vp, _vp, _vp]),
+    "ctc_amd_blank_token_spans": (_int, [_vp, _i64, _i64, _vp, _int, _vp, _vp, _int, _int, _int, _int, _int,
+                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

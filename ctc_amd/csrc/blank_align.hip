@@ -20,7 +20,8 @@
 //                               (16 K bytes per step): in LDS while they fit, in the workspace beyond.  Wave 0 then
 //                               walks them back with one readlane per step and writes the path 64 steps per store.
 // These take 2S+1 <= 512 states (S <= 255); blank_align_wide.hpp, included below, takes 513..2047 with several waves
-// per sample (ctc_amd_blank_best_path_wide).
+// per sample (ctc_amd_blank_best_path_wide).  blank_spans.hpp, included last, turns the path and the posteriors into
+// one record per target label (ctc_amd_blank_token_spans).
 #include "common.hpp"
 #include "launch.hpp"
 
@@ -690,6 +691,30 @@ __global__ __launch_bounds__(2 * kWave) void blank_post_chain_kernel(PostParams 
     else post_chain<K, false>(p, b, Tb, L);
 }
 
+// The row arithmetic of the combine launches (blank_post_gamma_kernel below, blank_post_conf_kernel in blank_spans.hpp):
+// rows t0 .. t0 + kPostRows - 1 of a sample, state s = lane + 64 k.  In: z[r][k] = alpha' + beta' (-inf outside the
+// support) and m[r] = the lane's maximum over its k.  Out: m[r] = the row maximum, z[r][k] = exp2(z - m) (0 outside the
+// support), sum[r] = the row sum, both in every lane.  gamma = z * post_row_inv(sum).
+// (The masked loads in front stay in each kernel's body: moved in here -- by value, by reference, whole or per element --
+// they changed the order of blank_post_gamma_kernel's instructions)
+template <int K>
+__device__ __forceinline__ void post_row_terms(float (&z)[kPostRows][K], float (&m)[kPostRows], float (&sum)[kPostRows])
+{
+    wave_max4(m[0], m[1], m[2], m[3]);
+#pragma unroll
+    for (int r = 0; r < kPostRows; ++r) {
+        sum[r] = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            z[r][k] = z[r][k] > -__builtin_inff() ? __builtin_amdgcn_exp2f(z[r][k] - m[r]) : 0.f;
+            sum[r] += z[r][k];
+        }
+    }
+    wave_sum4(sum[0], sum[1], sum[2], sum[3]);
+}
+
+__device__ __forceinline__ float post_row_inv(float sum) { return sum > 0.f ? 1.0f / sum : 0.f; }
+
 // grid (ceil(T / (4 * kPostRows)), B): wave w of block x takes rows t0 .. t0 + kPostRows - 1, state s = lane + 64 k
 template <int K>
 __global__ __launch_bounds__(kPostThreads) void blank_post_gamma_kernel(PostParams p)
@@ -715,23 +740,13 @@ __global__ __launch_bounds__(kPostThreads) void blank_post_gamma_kernel(PostPara
             m[r] = fmaxf(m[r], z[r][k]);
         }
     }
-    wave_max4(m[0], m[1], m[2], m[3]);
     float sum[kPostRows];
-#pragma unroll
-    for (int r = 0; r < kPostRows; ++r) {
-        sum[r] = 0.f;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            z[r][k] = z[r][k] > -__builtin_inff() ? __builtin_amdgcn_exp2f(z[r][k] - m[r]) : 0.f;
-            sum[r] += z[r][k];
-        }
-    }
-    wave_sum4(sum[0], sum[1], sum[2], sum[3]);
+    post_row_terms<K>(z, m, sum);
     float *out = p.gamma + r0 * p.NS;
 #pragma unroll
     for (int r = 0; r < kPostRows; ++r) {
         if (t0 + r >= T) break;
-        const float inv = sum[r] > 0.f ? 1.0f / sum[r] : 0.f;
+        const float inv = post_row_inv(sum[r]);
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const int s = lane + kWave * k;
@@ -740,8 +755,10 @@ __global__ __launch_bounds__(kPostThreads) void blank_post_gamma_kernel(PostPara
     }
 }
 
+// where the posteriors' rows lie: the gather's table em, then alpha', then beta' (ctc_amd_blank_token_spans lays its
+// posterior stage out with this too)
 template <int K>
-static int run_blank_post(PostParams &pp, hipStream_t s)
+static int blank_post_layout(PostParams &pp)
 {
     constexpr int RW = align_row_pitch(K);
     AlignParams &p = pp.a;
@@ -755,9 +772,18 @@ static int run_blank_post(PostParams &pp, hipStream_t s)
     pp.be = pp.al + cells * pp.NSP;
     // the three lattice areas of the blank loss ([B][T][NSP] each, NSP = 64 K) hold em + al + be; nothing behind them
     if ((size_t)RW + 2 * (size_t)pp.NSP > 3 * (size_t)pp.NSP) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
+    return 0;
+}
+
+template <int K>
+static int run_blank_post(PostParams &pp, hipStream_t s)
+{
+    int rc = blank_post_layout<K>(pp);
+    if (rc) return rc;
+    AlignParams &p = pp.a;
     const int rows_per_block = (kAlignGatherThreads / kWave) * kAlignGatherRows;
-    int rc = launch<blank_align_gather_kernel<K>>(dim3((p.T + rows_per_block - 1) / rows_per_block, p.B),
-                                                  dim3(kAlignGatherThreads), 0, s, p);
+    rc = launch<blank_align_gather_kernel<K>>(dim3((p.T + rows_per_block - 1) / rows_per_block, p.B),
+                                              dim3(kAlignGatherThreads), 0, s, p);
     if (rc) return rc;
     rc = launch<blank_post_chain_kernel<K>>(dim3(p.B), dim3(2 * kWave), 0, s, pp);
     if (rc) return rc;
@@ -769,6 +795,7 @@ static int run_blank_post(PostParams &pp, hipStream_t s)
 
 #include "blank_align_wide.hpp"
 #include "blank_post_wide.hpp"
+#include "blank_spans.hpp"
 
 using namespace ctc;
 
@@ -856,4 +883,35 @@ extern "C" int ctc_amd_blank_posteriors_wide(const float *log_probs, int64_t str
     p.counter = static_cast<unsigned *>(workspace);
     pp.nll = nll; pp.gamma = gamma;
     return run_blank_post_wide(pp, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int ctc_amd_blank_token_spans(const float *log_probs, int64_t stride_t, int64_t stride_b,
+                                         const void *targets, int targets_i64,
+                                         const int64_t *in_len, const int64_t *tgt_len,
+                                         int T, int B, int C, int S, int blank,
+                                         int32_t *path, float *score, float *nll, float *frame_conf,
+                                         int32_t *start, int32_t *end, float *conf,
+                                         void *workspace, void *stream)
+{
+    if (!log_probs || !targets || !in_len || !tgt_len || !path || !score || !nll || !frame_conf || !start || !end ||
+        !conf || !workspace)
+        return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (T < 1 || B < 1 || C < 1 || S < 1 || blank < 0 || blank >= C) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (S > 1023) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;                       // 2S+1 <= 2047: four waves of 512
+    SpanParams q = {};
+    AlignParams &p = q.p.a;
+    p.lp = log_probs; p.st = stride_t; p.sb = stride_b;
+    p.tgt = targets; p.tgt64 = targets_i64;
+    p.in_len = in_len; p.tgt_len = tgt_len;
+    p.T = T; p.B = B; p.C = C; p.S = S; p.blank = blank;
+    p.path = path; p.score = score;
+    p.counter = static_cast<unsigned *>(workspace);
+    q.p.nll = nll;
+    q.frame_conf = frame_conf; q.start = start; q.end = end; q.conf = conf;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int ns = 2 * S + 1;
+    if (ns <= kWave * 2) return run_blank_spans<2>(q, s);
+    if (ns <= kWave * 4) return run_blank_spans<4>(q, s);
+    if (ns <= kWave * 8) return run_blank_spans<8>(q, s);
+    return run_blank_spans_wide(q, s);
 }

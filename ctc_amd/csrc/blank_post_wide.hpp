@@ -245,8 +245,9 @@ __global__ __launch_bounds__(kWideAlignMaxWaves * kWave) void blank_post_wide_ch
     else post_wide_chain<false>(q, b, Tb, L);
 }
 
+// the gather and the chains: the alpha' / beta' rows and nll are out when these two have run
 template <int W>
-static int launch_blank_post_wide(PostWideParams &q, hipStream_t s)
+static int launch_blank_post_wide_chains(PostWideParams &q, hipStream_t s)
 {
     AlignWideParams g;
     g.a = q.p.a;
@@ -256,7 +257,14 @@ static int launch_blank_post_wide(PostWideParams &q, hipStream_t s)
     const int grows = (kAlignGatherThreads / kWave) * kWideAlignGatherRows;
     int rc = launch<blank_post_wide_gather_kernel<W>>(dim3((p.T + grows - 1) / grows, p.B), dim3(kAlignGatherThreads), 0, s, g);
     if (rc) return rc;
-    rc = launch<blank_post_wide_chain_kernel>(dim3(p.B, 2), dim3(W * kWave), 0, s, q);
+    return launch<blank_post_wide_chain_kernel>(dim3(p.B, 2), dim3(W * kWave), 0, s, q);
+}
+
+template <int W>
+static int launch_blank_post_wide(PostWideParams &q, hipStream_t s)
+{
+    const AlignParams &p = q.p.a;
+    int rc = launch_blank_post_wide_chains<W>(q, s);
     if (rc) return rc;
     const int rows = (kPostThreads / kWave) * kPostRows;
     return launch<blank_post_gamma_kernel<kWideAlignK * W>>(dim3((p.T + rows - 1) / rows, p.B), dim3(kPostThreads), 0, s, q.p);
@@ -265,9 +273,8 @@ static int launch_blank_post_wide(PostWideParams &q, hipStream_t s)
 // 256 <= S <= 1023 (the caller has checked); the table and the alpha' / beta' rows lie in the three lattice areas of
 // ctc_amd_workspace_bytes(CTC_AMD_BLANK, ...): (256 W + 4) + 2 * 512 W floats per (b, t) of 1536 W; nothing is written to
 // the header or behind the areas
-static int run_blank_post_wide(PostParams &pp, hipStream_t s)
+static int blank_post_wide_layout(PostParams &pp, PostWideParams &q)
 {
-    PostWideParams q;
     AlignParams &p = pp.a;
     q.W = (2 * p.S + 1 + kWideAlignSpan - 1) / kWideAlignSpan;
     const int RW = align_wide_row_pitch(q.W);
@@ -283,6 +290,14 @@ static int run_blank_post_wide(PostParams &pp, hipStream_t s)
     pp.al = p.em + cells * RW;
     pp.be = pp.al + cells * pp.NSP;
     q.p = pp;
+    return 0;
+}
+
+static int run_blank_post_wide(PostParams &pp, hipStream_t s)
+{
+    PostWideParams q;
+    const int rc = blank_post_wide_layout(pp, q);
+    if (rc) return rc;
     if (q.W == 2) return launch_blank_post_wide<2>(q, s);
     if (q.W == 3) return launch_blank_post_wide<3>(q, s);
     return launch_blank_post_wide<4>(q, s);

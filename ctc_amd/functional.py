@@ -19,6 +19,7 @@ gradient on the device (a no-op launch when it is 1.0, i.e. ``loss.backward()``)
 There is no CPU path: non-HIP tensors raise.
 """
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -630,6 +631,59 @@ def blank_posteriors(log_probs, targets, input_lengths, target_lengths, blank=0)
     entry = "ctc_amd_blank_posteriors_wide" if S > BLANK_NARROW_LABELS else "ctc_amd_blank_posteriors"
     return _readout(entry, _lib.BLANK, log_probs, "log_probs", targets, input_lengths,
                     target_lengths, lambda S: 2 * S + 1, torch.float32, extra=(int(blank),))
+
+
+class BlankTokenSpans(NamedTuple):
+    """What ``blank_token_spans`` returns (shapes and meanings: its docstring)."""
+    start: torch.Tensor
+    end: torch.Tensor
+    conf: torch.Tensor
+    frame_conf: torch.Tensor
+    path: torch.Tensor
+    score: torch.Tensor
+    nll: torch.Tensor
+
+
+def blank_token_spans(log_probs, targets, input_lengths, target_lengths, blank=0):
+    """One record per target label from the best alignment and the posteriors of the blank-CTC lattice, in one call ->
+    ``BlankTokenSpans(start, end, conf, frame_conf, path, score, nll)``.
+
+    Same inputs as ``blank_best_path``.  For label j < L_b of a sample that has an alignment, ``start[b,j]`` [B,S] int32 is
+    the first frame the best path gives to that label and ``end[b,j]`` one past the last (the frames between are all
+    its own); ``conf[b,j]`` [B,S] fp32 is the mean over those frames of ``frame_conf``.  The class of span j is
+    ``targets[b,j]``.  Padding columns j >= L_b and samples without an alignment have start = end = -1 and conf = 0.
+    ``frame_conf[b,t]`` [B,T] fp32 is the posterior of the best path's state at frame t, ``gamma[b,t,path[b,t]]`` of
+    ``blank_posteriors`` bit for bit (0 where path is -1) -- but gamma [B,T,2S+1] itself is never allocated or written.
+    ``path`` [B,T] int32 and ``score`` [B] are ``blank_best_path``'s, ``nll`` [B] is ``blank_posteriors``', bit for bit.
+    conf is a float32 sum over the span in ascending t followed by one division, so a float32 loop reproduces it.
+    Not differentiable.  S <= 1023 label columns, as the other blank read-outs (CtcAmdError beyond).
+    ``blank_forced_align`` stays the frame-level form (a token and its log-probability per frame).  include/ctc_amd.h.
+    """
+    S = targets.shape[1] if isinstance(targets, torch.Tensor) and targets.dim() == 2 else 0   # (_readout_inputs validates)
+    if S > BLANK_MAX_LABELS:
+        raise _lib.CtcAmdError(
+            "ctc_amd: the blank CTC token spans take targets of at most %d label columns (2S+1 <= %d lattice states), "
+            "got S=%d" % (BLANK_MAX_LABELS, 2 * BLANK_MAX_LABELS + 1, S))
+    xs, tg, il, tl, T, B, C, S, dev = _readout_inputs(log_probs, "log_probs", targets, input_lengths, target_lengths,
+                                                      _lib.BLANK)
+    path = torch.empty((B, T), dtype=torch.int32, device=dev)
+    frame_conf = torch.empty((B, T), dtype=torch.float32, device=dev)
+    start = torch.empty((B, S), dtype=torch.int32, device=dev)
+    end = torch.empty((B, S), dtype=torch.int32, device=dev)
+    conf = torch.empty((B, S), dtype=torch.float32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    nll = torch.empty(B, dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        stream = _stream_handle(dev)
+        ws = _workspace(_lib.BLANK, T, B, C, S, dev, stream)
+        rc = _lib.load().ctc_amd_blank_token_spans(
+            xs.data_ptr(), xs.stride(0), xs.stride(1), tg.data_ptr(), int(tg.dtype is torch.int64), il.data_ptr(),
+            tl.data_ptr(), T, B, C, S, int(blank), path.data_ptr(), score.data_ptr(), nll.data_ptr(),
+            frame_conf.data_ptr(), start.data_ptr(), end.data_ptr(), conf.data_ptr(), ws.data_ptr(), stream)
+    _lib.check(rc, "ctc_amd_blank_token_spans")
+    if _VALIDATE:
+        check_status(dev)
+    return BlankTokenSpans(start, end, conf, frame_conf, path, score, nll)
 
 
 def noblank_posteriors(logits, targets, input_lengths, target_lengths):

@@ -316,6 +316,42 @@ int ctc_amd_blank_posteriors_wide(const float *log_probs, int64_t stride_t, int6
                                   int T, int B, int C, int S, int blank,
                                   float *nll, float *gamma, void *workspace, void *stream);
 
+/* Token spans on the blank-CTC lattice: one record per target label -- where the best alignment puts it and how sure
+ * the model is -- from ctc_amd_blank_best_path's path and ctc_amd_blank_posteriors' gamma in ONE call, without gamma
+ * [B,T,2S+1] ever being written.  Inputs: the same layout and contract as ctc_amd_blank_best_path (log_probs used as
+ * given; stride over classes 1; 0 <= L_b <= S, 1 <= T_b <= T).  1 <= S <= 1023: up to 255 label columns run the narrow
+ * kernels, 256..1023 the wide ones, chosen here.  Every element of every output is written.
+ *   path       [B,T] int32, score [B]: what ctc_amd_blank_best_path / _wide write for the same inputs, bit for bit
+ *   nll        [B]: what ctc_amd_blank_posteriors / _wide write, bit for bit
+ *   frame_conf [B,T] fp32: gamma[b, t, path[b,t]] -- the very value the posteriors entry stores at that position (the
+ *              same z * inv of the same row maximum and row sum); 0 where path[b,t] = -1
+ *   start, end [B,S] int32: for label j < L_b of a sample with an alignment, start = the first frame t with
+ *              path[b,t] = 2j+1 and end = one past the last (the path is monotone: those frames are contiguous and there
+ *              is at least one); -1 / -1 for j >= L_b and for every j of a sample with no alignment or with lengths out
+ *              of contract
+ *   conf       [B,S] fp32: the sum of frame_conf[b,t] over t = start .. end-1 -- from 0.0f, in ascending t, in fp32 --
+ *              followed by one correctly rounded fp32 division by float(end - start); 0 where start is -1.  The order is
+ *              part of the contract: a float32 loop in that order reproduces the bits.
+ * The class of span j is targets[b,j].  Samples with no alignment or with lengths out of contract get in path, score,
+ * nll and frame_conf what the two entries above leave there (path -1, score -inf, nll +inf or NaN, frame_conf 0).
+ * Null pointers, T, B, C, S < 1 and a blank outside [0, C) return CTC_AMD_ERR_BAD_ARGUMENT before anything is
+ * dereferenced or launched, and before S is looked at; S > 1023, or a lattice that does not fit the workspace,
+ * CTC_AMD_ERR_UNSUPPORTED_SHAPE.
+ * Launches, all on `stream`: the best path's (gather, scan + walk back), the posteriors' chains on the lattice areas the
+ * back-pointers have left (S <= 255: on the best path's own table, one gather for both; wider: behind a gather of
+ * their own), one launch that forms each gamma row as ctc_amd_blank_posteriors does and stores the one selected value,
+ * one launch that turns path and frame_conf into the spans.  No workgroup waits on another in the two new launches; the
+ * narrow best path and chains may raise their status bits 8 and 16 as in their own entries, the wide stages raise none.
+ * workspace: at least ctc_amd_workspace_bytes(CTC_AMD_BLANK, T, B, C, S) bytes; only the lattice areas behind the
+ * 256-byte header are written.  Any T.  Deterministic. */
+int ctc_amd_blank_token_spans(const float *log_probs, int64_t stride_t, int64_t stride_b,
+                              const void *targets, int targets_i64,
+                              const int64_t *in_len, const int64_t *tgt_len,
+                              int T, int B, int C, int S, int blank,
+                              int32_t *path, float *score, float *nll, float *frame_conf,
+                              int32_t *start, int32_t *end, float *conf,
+                              void *workspace, void *stream);
+
 /* Target construction: the dedup step of the reference's dataset preparation,
  * datasets/charades_ctc_next_pred.py:646-651,663-678 (same code at :503-505,523-531) -- out[b] = the rows of
  * rows[b] whose code is new, in order of first appearance, remaining rows filled with -1 (:676-678);

@@ -6,7 +6,7 @@
 OLD / NEW: two hipcc -c objects of the same source, or two directories of them (e.g. ctc_amd/lib/obj, obj_diag, obj_fault
 of two checkouts: every *.o of either directory is compared with the one of the same name).  The gfx950 code object is
 unbundled from each, disassembled with llvm-objdump, and every function's instructions are compared with branch targets,
-encodings and the zero fill between functions left out.  fp32 instantiations of noblank_r16_kernel that gained the
+encodings and the fill between functions (zeros, trailing s_nop 0) left out.  fp32 instantiations of noblank_r16_kernel that gained the
 element-type template argument (`...EfEEvNS...`) are matched with their old names.  Exit status 1 if any function (or
 object) is missing, added or differs."""
 import os
@@ -44,6 +44,9 @@ def functions(funcs, text):
         ins = re.sub(r"^(s_c?branch\S*)\s+\S+$", r"\1 <>", ins)       # (a target printed as a bare label)
         if cur is not None and ins and ins != "...":
             cur.append(ins)
+    for body in out.values():                                        # the s_nop fill behind a function's last instruction
+        while body and body[-1] == "s_nop 0":                        # (its length depends on what follows in .text)
+            body.pop()
     return out
 
 
