@@ -114,95 +114,140 @@ struct LstmSeriesParams {
     float *h_out, *c_out;                                    // optional final state [B][H]
 };
 
+// What a thread of the recurrence owns, and where the workgroup's staging lies in LDS (lstm_series_kernel and
+// lstm_forward_kernel: one layout, one prologue, one frame body -- the same fma chains in both, bit for bit).
+struct SeriesLane {
+    float *xh, *pre, *cst;                                   // [kSeriesSamples][4 * K4]: [x_t | h_{t-1} | zeros]; [kSeriesSamples][G]; [kSeriesSamples][H]
+    int K4, G, tid, b0, ns;
+    int xs, xk, cs, cj;                                      // this thread's element of the next frame's inputs; its (sample, unit) of the cell update
+    bool xmine, cmine;
+};
+
+__host__ __device__ inline size_t series_smem_floats(int I, int H)
+{
+    return (size_t)kSeriesSamples * (4 * (size_t)((I + H + 3) / 4) + 4 * (size_t)H + H);
+}
+
+__device__ __forceinline__ SeriesLane series_lane(const LstmSeriesParams &p, float *smem)
+{
+    SeriesLane L;
+    L.K4 = (p.I + p.H + 3) >> 2; L.G = 4 * p.H;
+    L.xh = smem;
+    L.pre = L.xh + kSeriesSamples * 4 * L.K4;
+    L.cst = L.pre + kSeriesSamples * L.G;
+    L.tid = threadIdx.x; L.b0 = blockIdx.x * kSeriesSamples;
+    L.ns = min(kSeriesSamples, p.B - L.b0);
+    // (kSeriesSamples * I <= 256 and kSeriesSamples * H <= 256 are checked on the host)
+    L.xs = L.tid / p.I; L.xk = L.tid - L.xs * p.I;
+    L.xmine = L.xs < L.ns && L.tid < kSeriesSamples * p.I;
+    L.cs = L.tid / p.H; L.cj = L.tid - L.cs * p.H;
+    L.cmine = L.cs < L.ns && L.tid < kSeriesSamples * p.H;
+    return L;
+}
+
+// gate row `tid` of [W_ih | W_hh] -> registers (zeros behind K: the staged vectors are padded alike)
+__device__ __forceinline__ void series_gate_row(const LstmSeriesParams &p, const SeriesLane &L, float (&wr)[kSeriesK], float &bias)
+{
+    const int K = p.I + p.H;
+    bias = 0.f;
+    if (L.tid < L.G) {
+#pragma unroll
+        for (int k = 0; k < kSeriesK; ++k)
+            wr[k] = k < p.I ? p.w_ih[(size_t)L.tid * p.I + k] : k < K ? p.w_hh[(size_t)L.tid * p.H + (k - p.I)] : 0.f;
+        bias = p.b_ih[L.tid] + p.b_hh[L.tid];
+    }
+}
+
+// [x_0 | h_0 | zeros] and c_0 of the workgroup's samples -> LDS; x0(s, k): element k of sample s's input of frame 0
+template <typename X0>
+__device__ __forceinline__ void series_stage(const LstmSeriesParams &p, const SeriesLane &L, X0 x0)
+{
+    const int K = p.I + p.H, K4 = L.K4;
+    for (int i = L.tid; i < kSeriesSamples * 4 * K4; i += kLstmThreads) {
+        const int s = i / (4 * K4), k = i - s * 4 * K4;
+        float v = 0.f;
+        if (s < L.ns && k < p.I) v = x0(s, k);
+        else if (s < L.ns && k < K) v = p.h0[(size_t)(L.b0 + s) * p.H + (k - p.I)];
+        L.xh[i] = v;
+    }
+    for (int i = L.tid; i < kSeriesSamples * p.H; i += kLstmThreads) {
+        const int s = i / p.H, j = i - s * p.H;
+        const float c = s < L.ns ? p.c0[(size_t)(L.b0 + s) * p.H + j] : 0.f;
+        L.cst[i] = c;
+        if (p.cells && s < L.ns) p.cells[(size_t)(L.b0 + s) * p.H + j] = c;
+    }
+}
+
+// Frame t behind its first barrier ([x_t | h_{t-1}] is complete; the caller has x_{t+1} in flight as `xnext`): the gate
+// products, the second barrier, the cell update, h_t into LDS and into v_series[t].
+__device__ __forceinline__ void series_frame(const LstmSeriesParams &p, const SeriesLane &L, const float (&wr)[kSeriesK],
+                                             float bias, int t, float xnext)
+{
+    const int K4 = L.K4, G = L.G, tid = L.tid, cs_ = L.cs, cj = L.cj;
+    float *xh = L.xh, *pre = L.pre, *cst = L.cst;
+    if (tid < G) {
+        float acc[kSeriesSamples];
+#pragma unroll
+        for (int s = 0; s < kSeriesSamples; ++s) acc[s] = 0.f;
+#pragma unroll
+        for (int k4 = 0; k4 < kSeriesK / 4; ++k4) {
+            if (k4 < K4) {                                   // (uniform)
+#pragma unroll
+                for (int s = 0; s < kSeriesSamples; ++s) {
+                    const float4 v = *reinterpret_cast<const float4 *>(xh + (s * K4 + k4) * 4);
+                    acc[s] = __builtin_fmaf(wr[4 * k4], v.x, acc[s]);
+                    acc[s] = __builtin_fmaf(wr[4 * k4 + 1], v.y, acc[s]);
+                    acc[s] = __builtin_fmaf(wr[4 * k4 + 2], v.z, acc[s]);
+                    acc[s] = __builtin_fmaf(wr[4 * k4 + 3], v.w, acc[s]);
+                }
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < kSeriesSamples; ++s) pre[s * G + tid] = acc[s] + bias;
+    }
+    __syncthreads();                                         // the pre-activations are there; the staged vectors are free
+    if (L.xmine) xh[L.xs * 4 * K4 + L.xk] = xnext;
+    if (L.cmine) {
+        const int b = L.b0 + cs_;
+        const float *g4 = pre + cs_ * G;
+        const float gi = sigmoid_f(g4[cj]), gf = sigmoid_f(g4[p.H + cj]), gg = tanhf(g4[2 * p.H + cj]), go = sigmoid_f(g4[3 * p.H + cj]);
+        const float cn = __builtin_fmaf(gf, cst[cs_ * p.H + cj], gi * gg);
+        const float hn = go * tanhf(cn);
+        cst[cs_ * p.H + cj] = cn;
+        xh[cs_ * 4 * K4 + p.I + cj] = hn;                    // h_t: the next frame's recurrent input
+        p.series[t * p.series_stride_t + b * p.series_stride_b + cj] = hn;
+        if (p.gates) {
+            float *q = p.gates + ((size_t)t * p.B + b) * G;
+            q[cj] = gi; q[p.H + cj] = gf; q[2 * p.H + cj] = gg; q[3 * p.H + cj] = go;
+        }
+        if (p.cells) p.cells[((size_t)(t + 1) * p.B + b) * p.H + cj] = cn;
+        if (t == p.T - 1) {
+            if (p.h_out) p.h_out[(size_t)b * p.H + cj] = hn;
+            if (p.c_out) p.c_out[(size_t)b * p.H + cj] = cn;
+        }
+    }
+    if (p.series_cols > p.H) {
+        const int np = p.series_cols - p.H;
+        for (int i = tid; i < L.ns * np; i += kLstmThreads) {
+            const int s = i / np, j = p.H + (i - s * np);
+            p.series[t * p.series_stride_t + (L.b0 + s) * p.series_stride_b + j] = p.pad_value;
+        }
+    }
+}
+
 __global__ __launch_bounds__(kLstmThreads) void lstm_series_kernel(LstmSeriesParams p)
 {
     extern __shared__ float4 series_smem[];
-    const int K = p.I + p.H, G = 4 * p.H, K4 = (K + 3) >> 2;
-    float *xh = reinterpret_cast<float *>(series_smem);      // [kSeriesSamples][4 * K4]: [x_t | h_{t-1} | zeros]
-    float *pre = xh + kSeriesSamples * 4 * K4;               // [kSeriesSamples][G]
-    float *cst = pre + kSeriesSamples * G;                   // [kSeriesSamples][H]
-    const int tid = threadIdx.x, b0 = blockIdx.x * kSeriesSamples;
-    const int ns = min(kSeriesSamples, p.B - b0);
-    // gate row `tid` of [W_ih | W_hh] -> registers (zeros behind K: the staged vectors are padded alike)
+    const SeriesLane L = series_lane(p, reinterpret_cast<float *>(series_smem));
     float wr[kSeriesK];
-    float bias = 0.f;
-    if (tid < G) {
-#pragma unroll
-        for (int k = 0; k < kSeriesK; ++k)
-            wr[k] = k < p.I ? p.w_ih[(size_t)tid * p.I + k] : k < K ? p.w_hh[(size_t)tid * p.H + (k - p.I)] : 0.f;
-        bias = p.b_ih[tid] + p.b_hh[tid];
-    }
-    for (int i = tid; i < kSeriesSamples * 4 * K4; i += kLstmThreads) {
-        const int s = i / (4 * K4), k = i - s * 4 * K4;
-        float v = 0.f;
-        if (s < ns && k < p.I) v = p.x[(size_t)(b0 + s) * p.I + k];                       // x_0
-        else if (s < ns && k < K) v = p.h0[(size_t)(b0 + s) * p.H + (k - p.I)];
-        xh[i] = v;
-    }
-    for (int i = tid; i < kSeriesSamples * p.H; i += kLstmThreads) {
-        const int s = i / p.H, j = i - s * p.H;
-        const float c = s < ns ? p.c0[(size_t)(b0 + s) * p.H + j] : 0.f;
-        cst[i] = c;
-        if (p.cells && s < ns) p.cells[(size_t)(b0 + s) * p.H + j] = c;
-    }
-    // this thread's element of the next frame's inputs (kSeriesSamples * I <= 256 is checked on the host)
-    const int xs = tid / p.I, xk = tid - xs * p.I;
-    const bool xmine = xs < ns && tid < kSeriesSamples * p.I;
-    // this thread's (sample, unit) of the cell update (kSeriesSamples * H <= 256)
-    const int cs_ = tid / p.H, cj = tid - cs_ * p.H;
-    const bool cmine = cs_ < ns && tid < kSeriesSamples * p.H;
+    float bias;
+    series_gate_row(p, L, wr, bias);
+    series_stage(p, L, [&](int s, int k) { return p.x[(size_t)(L.b0 + s) * p.I + k]; });
     for (int t = 0; t < p.T; ++t) {
         __syncthreads();                                     // [x_t | h_{t-1}] is complete
         float xnext = 0.f;
-        if (xmine && t + 1 < p.T) xnext = p.x[((size_t)(t + 1) * p.B + b0 + xs) * p.I + xk];
-        if (tid < G) {
-            float acc[kSeriesSamples];
-#pragma unroll
-            for (int s = 0; s < kSeriesSamples; ++s) acc[s] = 0.f;
-#pragma unroll
-            for (int k4 = 0; k4 < kSeriesK / 4; ++k4) {
-                if (k4 < K4) {                               // (uniform)
-#pragma unroll
-                    for (int s = 0; s < kSeriesSamples; ++s) {
-                        const float4 v = *reinterpret_cast<const float4 *>(xh + (s * K4 + k4) * 4);
-                        acc[s] = __builtin_fmaf(wr[4 * k4], v.x, acc[s]);
-                        acc[s] = __builtin_fmaf(wr[4 * k4 + 1], v.y, acc[s]);
-                        acc[s] = __builtin_fmaf(wr[4 * k4 + 2], v.z, acc[s]);
-                        acc[s] = __builtin_fmaf(wr[4 * k4 + 3], v.w, acc[s]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int s = 0; s < kSeriesSamples; ++s) pre[s * G + tid] = acc[s] + bias;
-        }
-        __syncthreads();                                     // the pre-activations are there; the staged vectors are free
-        if (xmine) xh[xs * 4 * K4 + xk] = xnext;
-        if (cmine) {
-            const int b = b0 + cs_;
-            const float *g4 = pre + cs_ * G;
-            const float gi = sigmoid_f(g4[cj]), gf = sigmoid_f(g4[p.H + cj]), gg = tanhf(g4[2 * p.H + cj]), go = sigmoid_f(g4[3 * p.H + cj]);
-            const float cn = __builtin_fmaf(gf, cst[cs_ * p.H + cj], gi * gg);
-            const float hn = go * tanhf(cn);
-            cst[cs_ * p.H + cj] = cn;
-            xh[cs_ * 4 * K4 + p.I + cj] = hn;                // h_t: the next frame's recurrent input
-            p.series[t * p.series_stride_t + b * p.series_stride_b + cj] = hn;
-            if (p.gates) {
-                float *q = p.gates + ((size_t)t * p.B + b) * G;
-                q[cj] = gi; q[p.H + cj] = gf; q[2 * p.H + cj] = gg; q[3 * p.H + cj] = go;
-            }
-            if (p.cells) p.cells[((size_t)(t + 1) * p.B + b) * p.H + cj] = cn;
-            if (t == p.T - 1) {
-                if (p.h_out) p.h_out[(size_t)b * p.H + cj] = hn;
-                if (p.c_out) p.c_out[(size_t)b * p.H + cj] = cn;
-            }
-        }
-        if (p.series_cols > p.H) {
-            const int np = p.series_cols - p.H;
-            for (int i = tid; i < ns * np; i += kLstmThreads) {
-                const int s = i / np, j = p.H + (i - s * np);
-                p.series[t * p.series_stride_t + (b0 + s) * p.series_stride_b + j] = p.pad_value;
-            }
-        }
+        if (L.xmine && t + 1 < p.T) xnext = p.x[((size_t)(t + 1) * p.B + L.b0 + L.xs) * p.I + L.xk];
+        series_frame(p, L, wr, bias, t, xnext);
     }
 }
 
@@ -314,7 +359,7 @@ extern "C" int ctc_amd_lstm_series(const float *x, const float *h0, const float 
     p.series = series; p.series_stride_t = series_stride_t; p.series_stride_b = series_stride_b;
     p.series_cols = series_cols; p.pad_value = pad_value;
     p.gates = gates_out; p.cells = cells_out; p.h_out = h_out; p.c_out = c_out;
-    const size_t smem = (size_t)kSeriesSamples * (4 * (size_t)((I + H + 3) / 4) + 4 * (size_t)H + H) * sizeof(float);
+    const size_t smem = series_smem_floats(I, H) * sizeof(float);
     return launch<lstm_series_kernel>(dim3((B + kSeriesSamples - 1) / kSeriesSamples), dim3(kLstmThreads), smem,
                                       static_cast<hipStream_t>(stream), p);
 }
@@ -390,6 +435,52 @@ struct HeadParams {
 
 typedef float head_f4 __attribute__((ext_vector_type(4)));
 
+// The Linear product of one tile of 16 rows with N tiles of 16 columns (head_kernel: N = 1; lstm_forward_kernel: every
+// column tile of a row tile).  ap / bp[n]: this lane's feature row / weight rows, already advanced by 4 fq.  Every output
+// element is ONE fmaf chain over k in the order (kb, MFMA i, q) with k = 16 kb + 4 q + i, a zero second batch when the
+// count of 16-blocks is odd: whoever calls this gets the same bits for the same row, column and K.
+template <int N>
+__device__ __forceinline__ void head_dot(const float *ap, const float *const (&bp)[N], int KB, head_f4 (&acc)[N])
+{
+    const head_f4 zero = {0.f, 0.f, 0.f, 0.f};
+    for (int kb = 0; kb < KB; kb += 2) {                     // two batches of four MFMAs in flight (rows are 16-byte aligned: checked by the host)
+        const bool two = kb + 1 < KB;
+        const head_f4 a0 = *reinterpret_cast<const head_f4 *>(ap + 16 * kb);
+        const head_f4 a1 = two ? *reinterpret_cast<const head_f4 *>(ap + 16 * kb + 16) : zero;
+        head_f4 b0[N], b1[N];
+#pragma unroll
+        for (int n = 0; n < N; ++n) {
+            b0[n] = *reinterpret_cast<const head_f4 *>(bp[n] + 16 * kb);
+            b1[n] = two ? *reinterpret_cast<const head_f4 *>(bp[n] + 16 * kb + 16) : zero;
+        }
+#pragma unroll
+        for (int n = 0; n < N; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, b0[n].x, acc[n], 0, 0, 0);
+#pragma unroll
+        for (int n = 0; n < N; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, b0[n].y, acc[n], 0, 0, 0);
+#pragma unroll
+        for (int n = 0; n < N; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, b0[n].z, acc[n], 0, 0, 0);
+#pragma unroll
+        for (int n = 0; n < N; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, b0[n].w, acc[n], 0, 0, 0);
+#pragma unroll
+        for (int n = 0; n < N; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, b1[n].x, acc[n], 0, 0, 0);
+#pragma unroll
+        for (int n = 0; n < N; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, b1[n].y, acc[n], 0, 0, 0);
+#pragma unroll
+        for (int n = 0; n < N; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, b1[n].z, acc[n], 0, 0, 0);
+#pragma unroll
+        for (int n = 0; n < N; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, b1[n].w, acc[n], 0, 0, 0);
+    }
+}
+
+// The head's epilogue, piece by piece (one definition for both kernels: the same roundings in both)
+__device__ __forceinline__ float head_linear(float acc, float bias) { return acc + bias; }
+__device__ __forceinline__ float head_invstd(float var, float eps) { return 1.0f / sqrtf(var + eps); }
+__device__ __forceinline__ float head_bn_relu(float x, float mean, float inv, float g, float be)
+{
+    const float y = (x - mean) * inv * g + be;
+    return y > 0.f ? y : 0.f;
+}
+
 __global__ __launch_bounds__(1024) void head_kernel(HeadParams p)
 {
     __shared__ float red[16][16];                            // [wave][column of the tile]
@@ -400,23 +491,10 @@ __global__ __launch_bounds__(1024) void head_kernel(HeadParams p)
     const int arow = min(16 * w + fr, p.B - 1), bcol = min(16 * n + fr, p.C - 1);
     const float *ap = p.feat + (int64_t)t * p.fst + (int64_t)arow * p.fsb + 4 * fq;
     const float *bp = p.w + (int64_t)bcol * p.K + 4 * fq;
-    head_f4 acc = {0.f, 0.f, 0.f, 0.f};
-    const int KB = p.K >> 4;                                 // K is a multiple of 16 (checked by the host)
-    typedef head_f4 head_f4u;                                // (rows are 16-byte aligned: checked by the host)
-    for (int kb = 0; kb < KB; kb += 2) {                     // two batches of four MFMAs in flight
-        const head_f4 a0 = *reinterpret_cast<const head_f4u *>(ap + 16 * kb), b0 = *reinterpret_cast<const head_f4u *>(bp + 16 * kb);
-        const bool two = kb + 1 < KB;
-        const head_f4 a1 = two ? *reinterpret_cast<const head_f4u *>(ap + 16 * kb + 16) : head_f4{0.f, 0.f, 0.f, 0.f};
-        const head_f4 b1 = two ? *reinterpret_cast<const head_f4u *>(bp + 16 * kb + 16) : head_f4{0.f, 0.f, 0.f, 0.f};
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, b0.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, b0.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, b0.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, b0.w, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, b1.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, b1.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, b1.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, b1.w, acc, 0, 0, 0);
-    }
+    const float *bps[1] = {bp};
+    head_f4 accs[1] = {{0.f, 0.f, 0.f, 0.f}};
+    head_dot<1>(ap, bps, p.K >> 4, accs);                    // K is a multiple of 16 (checked by the host)
+    const head_f4 acc = accs[0];
     // acc[j] = Linear output (without bias) of batch row 16 w + 4 fq + j, column 16 n + fr
     const int col = 16 * n + fr;
     const bool colok = col < p.C;
@@ -426,7 +504,7 @@ __global__ __launch_bounds__(1024) void head_kernel(HeadParams p)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         rowok[j] = 16 * w + 4 * fq + j < p.B;
-        x[j] = acc[j] + bias;
+        x[j] = head_linear(acc[j], bias);
     }
     auto column_total = [&](float v) {                       // sum over the batch rows of the frame, every lane of a column gets it
         v += __shfl_xor(v, 16, 64);
@@ -441,7 +519,7 @@ __global__ __launch_bounds__(1024) void head_kernel(HeadParams p)
     float mean, inv;
     if (p.rmean) {                                           // eval mode
         mean = colok ? p.rmean[col] : 0.f;
-        inv = 1.0f / sqrtf((colok ? p.rvar[col] : 1.f) + p.eps);
+        inv = head_invstd(colok ? p.rvar[col] : 1.f, p.eps);
     } else {
         float s = 0.f;
 #pragma unroll
@@ -451,7 +529,7 @@ __global__ __launch_bounds__(1024) void head_kernel(HeadParams p)
 #pragma unroll
         for (int j = 0; j < 4; ++j) q += rowok[j] ? (x[j] - mean) * (x[j] - mean) : 0.f;
         const float var = column_total(q) / (float)p.B;      // biased, what the normalisation uses
-        inv = 1.0f / sqrtf(var + p.eps);
+        inv = head_invstd(var, p.eps);
         if (w == 0 && fq == 0 && colok) {
             if (p.smean) p.smean[(int64_t)t * p.C + col] = mean;
             if (p.svar) p.svar[(int64_t)t * p.C + col] = var;
@@ -464,8 +542,7 @@ __global__ __launch_bounds__(1024) void head_kernel(HeadParams p)
         const int b = 16 * w + 4 * fq + j;
         if (!rowok[j] || !colok) continue;
         if (p.lin) p.lin[((int64_t)t * p.B + b) * p.C + col] = x[j];
-        float y = (x[j] - mean) * inv * g + be;
-        y = y > 0.f ? y : 0.f;
+        float y = head_bn_relu(x[j], mean, inv, g, be);
         if (p.mask) y *= p.mask[((int64_t)t * p.B + b) * p.C + col];
         p.out[(int64_t)t * p.ost + (int64_t)b * p.osb + col] = y;
     }
@@ -498,4 +575,123 @@ extern "C" int ctc_amd_head_forward(const float *feat, int64_t feat_stride_t, in
     const int NW = (B + 15) / 16;
     hipLaunchKernelGGL(ctc::head_kernel, dim3(T, (C + 15) / 16), dim3(64 * NW), 0, static_cast<hipStream_t>(stream), p);
     return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// EVAL mode: head and recurrence as ONE launch (feat -> v_series).  BatchNorm on its running statistics
+// makes a sample's head rows independent of every other sample, so the workgroup that walks kSeriesSamples samples
+// through the T frames (lstm_series_kernel's split, unchanged) first computes the head of exactly those samples:
+//   phase 1: rows (frame t, sample s) -> 16 x 16 tiles on the matrix cores, A row 4 t + s; wave w takes row tiles
+//            w, w + 4, ... and every column tile of them (the feature rows are loaded once, N = ceil(C / 16) <= 3
+//            independent accumulator chains); bias, BatchNorm, ReLU; the result stays in LDS as [T][4][C];
+//   phase 2: lstm_series_kernel's loop, x_t read from that slice.
+// head_dot / head_linear / head_invstd / head_bn_relu and series_stage / series_frame are the two-launch path's own
+// code: v_series is bit-identical to ctc_amd_head_forward + ctc_amd_lstm_series.
+namespace ctc {
+
+struct LstmForwardParams {
+    HeadParams h;                                            // feat, strides, Linear, BatchNorm, running statistics, eps, T, B, K, C (the rest unused)
+    LstmSeriesParams s;                                      // I = H = C; x unused
+};
+
+template <int N>
+__device__ __forceinline__ void forward_head_phase(const HeadParams &p, float *vall, int b0, int ns)
+{
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, fr = lane & 15, fq = lane >> 4;
+    const int RT = (kSeriesSamples * p.T + 15) >> 4;         // row tiles of the workgroup's [T][4] rows
+    const float *bp[N];
+    float bias[N], mean[N], inv[N], g[N], be[N];
+#pragma unroll
+    for (int n = 0; n < N; ++n) {                            // (columns past C: clamped, never stored)
+        const int col = min(16 * n + fr, p.C - 1);
+        bp[n] = p.w + (int64_t)col * p.K + 4 * fq;
+        bias[n] = p.bias[col];
+        mean[n] = p.rmean[col];
+        inv[n] = head_invstd(p.rvar[col], p.eps);
+        g[n] = p.gamma[col];
+        be[n] = p.beta[col];
+    }
+    for (int rt = w; rt < RT; rt += kLstmThreads / 64) {
+        // A row 16 rt + fr = (frame, sample), clamped like arow / bcol of head_kernel: rows past the count are masked below
+        const int row = 16 * rt + fr;
+        const int t = min(row / kSeriesSamples, p.T - 1), s = min(row % kSeriesSamples, ns - 1);
+        const float *ap = p.feat + (int64_t)t * p.fst + (int64_t)(b0 + s) * p.fsb + 4 * fq;
+        head_f4 acc[N];
+#pragma unroll
+        for (int n = 0; n < N; ++n) acc[n] = head_f4{0.f, 0.f, 0.f, 0.f};
+        head_dot<N>(ap, bp, p.K >> 4, acc);
+        // acc[n][j] = row 16 rt + 4 fq + j = (frame 4 rt + fq, sample j), column 16 n + fr
+        const int to = 4 * rt + fq;
+        if (to >= p.T) continue;
+#pragma unroll
+        for (int n = 0; n < N; ++n) {
+            const int col = 16 * n + fr;
+#pragma unroll
+            for (int j = 0; j < kSeriesSamples; ++j)
+                if (col < p.C && j < ns)
+                    vall[((size_t)to * kSeriesSamples + j) * p.C + col] =
+                        head_bn_relu(head_linear(acc[n][j], bias[n]), mean[n], inv[n], g[n], be[n]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kLstmThreads) void lstm_forward_kernel(LstmForwardParams q)
+{
+    static_assert(kSeriesSamples == 4, "a 16-row tile holds four frames of the workgroup's samples");
+    extern __shared__ float4 forward_smem[];
+    const LstmSeriesParams &p = q.s;
+    float *smem = reinterpret_cast<float *>(forward_smem);
+    const SeriesLane L = series_lane(p, smem);
+    float *vall = smem + series_smem_floats(p.I, p.H);       // [T][kSeriesSamples][C]: this workgroup's slice of the head's output
+    const int C = q.h.C, CT = (C + 15) >> 4;                 // (2 C <= kSeriesK: at most three column tiles)
+    if (CT == 1) forward_head_phase<1>(q.h, vall, L.b0, L.ns);
+    else if (CT == 2) forward_head_phase<2>(q.h, vall, L.b0, L.ns);
+    else forward_head_phase<3>(q.h, vall, L.b0, L.ns);
+    float wr[kSeriesK];
+    float bias;
+    series_gate_row(p, L, wr, bias);
+    __syncthreads();                                         // the slice is complete
+    series_stage(p, L, [&](int s, int k) { return vall[s * C + k]; });
+    for (int t = 0; t < p.T; ++t) {
+        __syncthreads();                                     // [x_t | h_{t-1}] is complete
+        float xnext = 0.f;
+        if (L.xmine && t + 1 < p.T) xnext = vall[((size_t)(t + 1) * kSeriesSamples + L.xs) * C + L.xk];
+        series_frame(p, L, wr, bias, t, xnext);
+    }
+}
+
+}  // namespace ctc
+
+extern "C" int ctc_amd_lstm_forward(const float *feat, int64_t feat_stride_t, int64_t feat_stride_b,
+                                    const float *weight, const float *bias, const float *bn_weight, const float *bn_bias,
+                                    const float *running_mean, const float *running_var, float eps,
+                                    const float *h0, const float *c0,
+                                    const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,
+                                    int T, int B, int K, int C,
+                                    float *series, int64_t series_stride_t, int64_t series_stride_b, int series_cols, float pad_value,
+                                    float *h_out, float *c_out, void *stream)
+{
+    if (!feat || !weight || !bias || !bn_weight || !bn_bias || !running_mean || !running_var) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (!h0 || !c0 || !w_ih || !w_hh || !b_ih || !b_hh || !series) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (T < 1 || B < 1 || K < 1 || C < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (series_cols < C || series_stride_b < series_cols) return CTC_AMD_ERR_BAD_ARGUMENT;
+    // the recurrence's sizes (I = H = C) and the head's 16-byte operand loads
+    if (2 * C > kSeriesK || 4 * C > kLstmThreads || (K & 15) != 0 || (feat_stride_b & 3) != 0 || (feat_stride_t & 3) != 0 ||
+        (reinterpret_cast<uintptr_t>(feat) & 15) != 0 || (reinterpret_cast<uintptr_t>(weight) & 15) != 0)
+        return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
+    // the workgroup's slice of the head's output, [T][4][C], next to the recurrence's staging
+    const size_t smem = (series_smem_floats(C, C) + (size_t)kSeriesSamples * (size_t)T * (size_t)C) * sizeof(float);
+    if (smem > kMaxLds) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
+    ctc::LstmForwardParams q{};
+    q.h.feat = feat; q.h.fst = feat_stride_t; q.h.fsb = feat_stride_b;
+    q.h.w = weight; q.h.bias = bias; q.h.gamma = bn_weight; q.h.beta = bn_bias;
+    q.h.rmean = running_mean; q.h.rvar = running_var; q.h.eps = eps;
+    q.h.T = T; q.h.B = B; q.h.K = K; q.h.C = C;
+    q.s.h0 = h0; q.s.c0 = c0; q.s.w_ih = w_ih; q.s.w_hh = w_hh; q.s.b_ih = b_ih; q.s.b_hh = b_hh;
+    q.s.T = T; q.s.B = B; q.s.I = C; q.s.H = C;
+    q.s.series = series; q.s.series_stride_t = series_stride_t; q.s.series_stride_b = series_stride_b;
+    q.s.series_cols = series_cols; q.s.pad_value = pad_value;
+    q.s.h_out = h_out; q.s.c_out = c_out;
+    return launch<lstm_forward_kernel>(dim3((B + kSeriesSamples - 1) / kSeriesSamples), dim3(kLstmThreads), smem,
+                                       static_cast<hipStream_t>(stream), q);
 }

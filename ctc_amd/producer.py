@@ -10,6 +10,12 @@ written straight into the logits tensor, optionally with one pad column (``pad_c
 as the reference's 33 gets rows of C + 1 floats, the extra logit -1e30 -- softmax gives it exactly 0, so no loss or
 gradient value changes, and the rows become the even, 8-byte aligned rows of the fastest loss kernel).
 
+In eval mode with nothing that needs a gradient (the reference validates under ``eval()`` and ``no_grad``) the two launches
+are ONE (``ctc_amd_lstm_forward`` / ``lstm_forward``): a workgroup computes the head rows of its own four samples into LDS and
+walks the recurrence from there, so ``v_all [T,B,C]`` never goes to memory; the result is bit-identical to the two launches.
+``LSTM_cell.forward`` takes it up to ``FUSED_FORWARD_MAX_WG_ROWS`` head rows per workgroup (4 T <= 64: measured,
+profiles/r13_lstm_forward.md -- 50 us against 70 us per forward at the reference's sizes; at T = 150 the two launches win).
+
 Same attribute names as the reference (``v``, ``v.layers``, ``v_cell``): its checkpoints load unchanged.  The backward
 pass through the cell is plain torch arithmetic on the gate activations the forward launch saved (the recurrence's
 backward is not on the HIP path).  No CPU path: non-HIP tensors raise.
@@ -189,6 +195,41 @@ def lstm_series_backward(d_series, gates, cells, w_hh):
     return dpre, dh0, dc0
 
 
+def lstm_forward(feat, weight, bias, bn_weight, bn_bias, running_mean, running_var, eps, h0, c0, w_ih, w_hh, b_ih, b_hh,
+                 cols=None, pad_value=PAD_LOGIT):
+    """EVAL mode, no gradient: ``head_forward`` (running statistics, no mask) and ``lstm_series`` as ONE launch
+    (``ctc_amd_lstm_forward``; the head's output stays in LDS) -> v_series [T,B,cols], bit-identical to the two launches, or
+    None when the launch does not take the shape (2 C > 80, K not a multiple of 16, unaligned rows, T C beyond the LDS)."""
+    F._require_hip(feat, "feat")
+    T, B, K = feat.shape
+    C = weight.shape[0]
+    cols = C if cols is None else int(cols)
+    dev = feat.device
+    f = feat if (feat.dtype is torch.float32 and feat.stride(2) == 1) else feat.float().contiguous()
+    args = [t if (t.dtype is torch.float32 and t.is_contiguous()) else t.float().contiguous()
+            for t in (weight, bias, bn_weight, bn_bias, running_mean, running_var)]
+    cell = [t if (t.dtype is torch.float32 and t.is_contiguous()) else t.float().contiguous()
+            for t in (h0, c0, w_ih, w_hh, b_ih, b_hh)]
+    series = torch.empty((T, B, cols), dtype=torch.float32, device=dev)
+    with F._on_device(dev):
+        rc = _lib.load().ctc_amd_lstm_forward(f.data_ptr(), f.stride(0), f.stride(1), *(t.data_ptr() for t in args), float(eps),
+                                              *(t.data_ptr() for t in cell), T, B, K, C, series.data_ptr(), series.stride(0),
+                                              series.stride(1), cols, float(pad_value), None, None, F._stream_handle(dev))
+    if rc == _lib.ERR_UNSUPPORTED_SHAPE:
+        return None
+    if rc:
+        _lib.check(rc, "ctc_amd_lstm_forward")
+    return series
+
+
+# LSTM_cell.forward in eval mode takes the one-launch path up to this many head rows per workgroup (4 T: a workgroup does the
+# head of its own four samples for all T frames, B / 4-way parallel where the separate head launch is T * ceil(C / 16)-way
+# parallel, so beyond some T the two launches win -- whatever B is).  Measured, not guessed (profiles/r13_lstm_forward.md):
+# T = 10, 12 and 16 win at B = 10 and at B = 256 (0.72 ... 0.78 and 0.54 ... 0.59 of the two launches' time), T = 20 loses at
+# B = 10 (1.07 x), T = 150 at every B (1.2 - 1.5 x); the bound is the largest measured point that wins at every B measured.
+FUSED_FORWARD_MAX_WG_ROWS = 64
+
+
 class _SeriesFn(torch.autograd.Function):
     """v_all [T,B,I], (h0, c0), LSTMCell parameters -> v_series [T,B,cols]: one launch for the reference's class counts, T
     fused launches otherwise; backward = BPTT in torch."""
@@ -266,14 +307,20 @@ class LSTM_cell(nn.Module):
         self.v = _BaseModule(self.input_size, self.v_class)
         self.v_cell = nn.LSTMCell(self.v_class, self.v_class)
 
-    def _head(self, feat):
-        """self.v applied to every frame (LSTM.py:48): one launch when self.v is the reference's BasicModule and the shape
-        is one the launch takes, the module itself frame by frame otherwise (a custom _BaseModule, B > 256, ...)."""
-        T = self.temporal
+    def _std_layers(self):
+        """self.v's four layers when it is the reference's BasicModule (what the HIP head computes), else None"""
         layers = getattr(self.v, "layers", None)
         std = (isinstance(layers, nn.Sequential) and len(layers) == 4 and isinstance(layers[0], nn.Linear)
                and isinstance(layers[1], nn.BatchNorm1d) and isinstance(layers[2], nn.ReLU) and isinstance(layers[3], nn.Dropout)
                and layers[0].bias is not None and layers[1].affine and layers[1].track_running_stats)
+        return layers if std else None
+
+    def _head(self, feat):
+        """self.v applied to every frame (LSTM.py:48): one launch when self.v is the reference's BasicModule and the shape
+        is one the launch takes, the module itself frame by frame otherwise (a custom _BaseModule, B > 256, ...)."""
+        T = self.temporal
+        layers = self._std_layers()
+        std = layers is not None
         B, K = feat.shape[1], feat.shape[2]
         if not std or feat.shape[0] < T or B > 256 or K % 16 or (self.training and (B < 2 or layers[1].momentum is None)):
             return torch.stack([self.v(feat[time]) for time in range(T)])
@@ -295,10 +342,28 @@ class LSTM_cell(nn.Module):
             bn.num_batches_tracked += T
         return out
 
+    def _forward_one_launch(self, feat, v_hsn, v_csn, cols):
+        """eval mode, the standard head, nothing that needs a gradient, a shape inside the measured gate: feat -> v_series as
+        ONE launch (``lstm_forward``, bit-identical to the two launches).  None: the caller takes the two launches."""
+        T = self.temporal
+        layers = None if self.training else self._std_layers()
+        if layers is None or feat.dim() != 3 or feat.shape[0] < T or 4 * T > FUSED_FORWARD_MAX_WG_ROWS:
+            return None
+        if feat.shape[1] > 256:                              # (the two-launch path leaves such a batch to torch's layers: stay with it)
+            return None
+        if torch.is_grad_enabled() and any(t.requires_grad for t in (feat, v_hsn, v_csn, *self.parameters())):
+            return None
+        lin, bn, cell = layers[0], layers[1], self.v_cell
+        return lstm_forward(feat[:T], lin.weight, lin.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps,
+                            v_hsn, v_csn, cell.weight_ih, cell.weight_hh, cell.bias_ih, cell.bias_hh, cols, PAD_LOGIT)
+
     def forward(self, feat, v_hsn, v_csn):
         F._require_hip(feat, "feat")
-        v_all = self._head(feat)                             # (BatchNorm statistics per frame, as the reference)
         H = self.v_class
         cols = H + 1 if (self.pad_classes and H % 2) else H
         cell = self.v_cell
+        series = self._forward_one_launch(feat, v_hsn, v_csn, cols)
+        if series is not None:
+            return series
+        v_all = self._head(feat)                             # (BatchNorm statistics per frame, as the reference)
         return _SeriesFn.apply(v_all, v_hsn, v_csn, cell.weight_ih, cell.weight_hh, cell.bias_ih, cell.bias_hh, cols, PAD_LOGIT)

@@ -445,6 +445,24 @@ int ctc_amd_head_forward(const float *feat, int64_t feat_stride_t, int64_t feat_
                          float *out, int64_t out_stride_t, int64_t out_stride_b,
                          float *linear_out, float *save_mean, float *save_var, float *save_invstd, void *stream);
 
+/* EVAL mode: ctc_amd_head_forward (running statistics, no mask) and ctc_amd_lstm_series as ONE launch -- feat in, v_series
+ * out; the head's output [T,B,C] never goes to memory (a workgroup keeps the rows of its four samples in LDS).  The LSTM is
+ * nn.LSTMCell(C, C).  Arguments as the two calls take them: feat / weight / bias / bn_weight / bn_bias / running_mean /
+ * running_var / eps as ctc_amd_head_forward (the running statistics are REQUIRED: there is no train mode here -- BatchNorm's
+ * batch statistics would tie the workgroups together);  h0, c0, w_ih, w_hh, b_ih, b_hh, series ..., pad_value, h_out, c_out
+ * as ctc_amd_lstm_series with I = H = C.  No workspace, no host synchronisation: safe under stream capture.
+ * v_series, h_out and c_out are bit-identical to the two calls (the same fmaf chains in the same order).
+ * CTC_AMD_ERR_UNSUPPORTED_SHAPE: 2 C > 80, K not a multiple of 16, feat strides not multiples of 4, feat or weight not
+ * 16-byte aligned, or 4 T C floats + the recurrence's staging beyond the LDS of a compute unit (use the two calls). */
+int ctc_amd_lstm_forward(const float *feat, int64_t feat_stride_t, int64_t feat_stride_b,
+                         const float *weight, const float *bias, const float *bn_weight, const float *bn_bias,
+                         const float *running_mean, const float *running_var, float eps,
+                         const float *h0, const float *c0,
+                         const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,
+                         int T, int B, int K, int C,
+                         float *series, int64_t series_stride_t, int64_t series_stride_b, int series_cols, float pad_value,
+                         float *h_out, float *c_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
