@@ -475,10 +475,27 @@ __device__ __forceinline__ void head_dot(const float *ap, const float *const (&b
 // The head's epilogue, piece by piece (one definition for both kernels: the same roundings in both)
 __device__ __forceinline__ float head_linear(float acc, float bias) { return acc + bias; }
 __device__ __forceinline__ float head_invstd(float var, float eps) { return 1.0f / sqrtf(var + eps); }
+// BatchNorm's output, the value the ReLU tests (head_bn_relu here, the gate of the backward pass in head_bwd_rows_kernel:
+// one expression, so the two agree bit for bit)
+__device__ __forceinline__ float head_bn_y(float x, float mean, float inv, float g, float be) { return (x - mean) * inv * g + be; }
 __device__ __forceinline__ float head_bn_relu(float x, float mean, float inv, float g, float be)
 {
-    const float y = (x - mean) * inv * g + be;
+    const float y = head_bn_y(x, mean, inv, g, be);
     return y > 0.f ? y : 0.f;
+}
+
+// Sum over the batch rows of a frame for the 16 columns of a tile; every lane of a column gets it.  Lane (fr, fq) of wave w
+// brings the partial sum of its four rows; red: [wave][column of the tile].  Fixed order: the lane quarters, then the waves.
+__device__ __forceinline__ float head_column_total(float v, float (*red)[16], int w, int fr, int fq, int NW)
+{
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    __syncthreads();                                         // (the previous total has been read by everybody)
+    if (fq == 0) red[w][fr] = v;
+    __syncthreads();
+    float s = 0.f;
+    for (int i = 0; i < NW; ++i) s += red[i][fr];
+    return s;
 }
 
 __global__ __launch_bounds__(1024) void head_kernel(HeadParams p)
@@ -506,16 +523,7 @@ __global__ __launch_bounds__(1024) void head_kernel(HeadParams p)
         rowok[j] = 16 * w + 4 * fq + j < p.B;
         x[j] = head_linear(acc[j], bias);
     }
-    auto column_total = [&](float v) {                       // sum over the batch rows of the frame, every lane of a column gets it
-        v += __shfl_xor(v, 16, 64);
-        v += __shfl_xor(v, 32, 64);
-        __syncthreads();                                     // (the previous total has been read by everybody)
-        if (fq == 0) red[w][fr] = v;
-        __syncthreads();
-        float s = 0.f;
-        for (int i = 0; i < NW; ++i) s += red[i][fr];
-        return s;
-    };
+    auto column_total = [&](float v) { return head_column_total(v, red, w, fr, fq, NW); };
     float mean, inv;
     if (p.rmean) {                                           // eval mode
         mean = colok ? p.rmean[col] : 0.f;
@@ -694,4 +702,347 @@ extern "C" int ctc_amd_lstm_forward(const float *feat, int64_t feat_stride_t, in
     q.s.h_out = h_out; q.s.c_out = c_out;
     return launch<lstm_forward_kernel>(dim3((B + kSeriesSamples - 1) / kSeriesSamples), dim3(kLstmThreads), smem,
                                        static_cast<hipStream_t>(stream), q);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The BACKWARD of the head: from the upstream gradient of the head's output and what the forward launch saved
+// to the gradients of feat, the Linear layer and BatchNorm's affine parameters.  Two launches (three when the weight
+// gradient splits its row range), data handed on at the kernel boundaries only:
+//   rows      grid (T, ceil(C / 16)), head_kernel's tiling: lane (fr, fq) of wave w owns batch rows 16 w + 4 fq + j of
+//             column 16 n + fr -- dy, xhat, the per-frame column totals (head_column_total), dlin [T B][CP] (CP = C padded
+//             to a multiple of 16, the pad zero) and the per-frame partials dbeta_t, dgamma_t, sum_b dlin [3][T][CP];
+//   products  one wave per task, exact fp32 on the matrix cores (an fmaf chain per output element):
+//               d_weight tile [16 c x 64 k] of one row-range split, contracting over the rows (4-byte operand loads, 64
+//                 contiguous bytes per 16 lanes);
+//               d_feat tile [16 rows x 64 k], contracting over the padded C (16-byte loads of the dlin row);
+//               tail: the [T][CP] partials summed over t ascending;
+//   reduce    (S > 1 only) the S partial weight gradients added in ascending split order.
+// S and the rows per split are functions of T B alone (head_bwd_splits): the same shape sums in the same order.
+namespace ctc {
+
+constexpr int64_t kHeadBwdMaxRows = (int64_t)1 << 22;        // T B beyond this: CTC_AMD_ERR_UNSUPPORTED_SHAPE
+constexpr int64_t kHeadBwdMaxTasks = (int64_t)1 << 28;       // waves of the products launch
+constexpr int kHeadBwdSplitRows = 128, kHeadBwdMaxSplits = 64;
+constexpr size_t kHeadBwdAlign = 256;                        // every piece of the scratch starts on such a boundary
+
+// row-range splits of the weight gradient: S = min(64, ceil(R / 128)) ranges of `chunk` rows (a multiple of 16)
+__host__ __device__ inline void head_bwd_splits(int64_t R, int &S, int &chunk)
+{
+    int64_t s = (R + kHeadBwdSplitRows - 1) / kHeadBwdSplitRows;
+    if (s > kHeadBwdMaxSplits) s = kHeadBwdMaxSplits;
+    if (s < 1) s = 1;
+    const int64_t c = 16 * (((R + s - 1) / s + 15) / 16);
+    S = (int)((R + c - 1) / c);
+    chunk = (int)c;
+}
+
+struct HeadBwdLayout {                                       // byte offsets into the (aligned) scratch
+    size_t dlin, part, wpart, total;
+    int CP, S, chunk;
+};
+
+inline bool head_bwd_shape_ok(int T, int B, int K, int C)
+{
+    if (B > 256 || (K & 15) != 0) return false;
+    const int64_t R = (int64_t)T * B;
+    if (R > kHeadBwdMaxRows) return false;
+    int S, chunk;
+    head_bwd_splits(R, S, chunk);
+    const int64_t CT = (C + 15) / 16, KQ = (K / 16 + 3) / 4;
+    const int64_t tasks = CT * KQ * S + ((R + 15) / 16) * KQ + (3 * 16 * CT + 63) / 64;
+    return CT <= 65535 && tasks <= kHeadBwdMaxTasks;
+}
+
+inline HeadBwdLayout head_bwd_layout(int T, int B, int K, int C)
+{
+    auto up = [](size_t v) { return (v + kHeadBwdAlign - 1) / kHeadBwdAlign * kHeadBwdAlign; };
+    HeadBwdLayout L;
+    const size_t R = (size_t)T * (size_t)B;
+    L.CP = 16 * ((C + 15) / 16);
+    head_bwd_splits((int64_t)R, L.S, L.chunk);
+    L.dlin = 0;
+    L.part = up(R * L.CP * sizeof(float));
+    L.wpart = L.part + up((size_t)3 * T * L.CP * sizeof(float));
+    L.total = L.wpart + (L.S > 1 ? up((size_t)L.S * C * K * sizeof(float)) : 0);
+    return L;
+}
+
+struct HeadBwdRowsParams {
+    const float *dout;                                       // rows of C at (dst, dsb)
+    int64_t dst, dsb;
+    const float *lin, *gamma, *beta;                         // [T][B][C]; [C]
+    const float *smean, *sinv;                               // train: [T][C]
+    const float *rmean, *rvar;                               // eval: [C]
+    const float *mask;                                       // [T][B][C] or NULL
+    float eps;
+    int T, B, C, CP;
+    float *dlin, *part;                                      // [T B][CP]; [3][T][CP]: dbeta_t, dgamma_t, sum_b dlin
+};
+
+__global__ __launch_bounds__(1024) void head_bwd_rows_kernel(HeadBwdRowsParams p)
+{
+    __shared__ float red[16][16];
+    const int t = blockIdx.x, n = blockIdx.y, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    const int fr = lane & 15, fq = lane >> 4;
+    const int NW = blockDim.x >> 6;
+    const int col = 16 * n + fr;                             // (< CP)
+    const bool colok = col < p.C, train = p.smean != nullptr;
+    float mean = 0.f, inv = 0.f, g = 0.f, be = 0.f;
+    if (colok) {
+        mean = train ? p.smean[(int64_t)t * p.C + col] : p.rmean[col];
+        inv = train ? p.sinv[(int64_t)t * p.C + col] : head_invstd(p.rvar[col], p.eps);
+        g = p.gamma[col];
+        be = p.beta[col];
+    }
+    float dy[4], xh[4];
+    bool rowok[4];
+    float sb = 0.f, sg = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int b = 16 * w + 4 * fq + j;
+        rowok[j] = b < p.B;
+        dy[j] = 0.f; xh[j] = 0.f;
+        if (rowok[j] && colok) {
+            const int64_t i = ((int64_t)t * p.B + b) * p.C + col;
+            const float x = p.lin[i];
+            float d = p.dout[(int64_t)t * p.dst + (int64_t)b * p.dsb + col];
+            if (p.mask) d *= p.mask[i];
+            xh[j] = (x - mean) * inv;
+            dy[j] = head_bn_y(x, mean, inv, g, be) > 0.f ? d : 0.f;
+        }
+        sb += dy[j];
+        sg += dy[j] * xh[j];
+    }
+    const float dbeta = head_column_total(sb, red, w, fr, fq, NW);
+    const float dgamma = head_column_total(sg, red, w, fr, fq, NW);
+    const float mb = dbeta / (float)p.B, mg = dgamma / (float)p.B;
+    float sd = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int b = 16 * w + 4 * fq + j;
+        if (!rowok[j]) continue;                             // (uniform per lane quarter; no barrier below depends on it)
+        float dl = 0.f;
+        if (colok) dl = train ? inv * g * (dy[j] - mb - xh[j] * mg) : dy[j] * g * inv;
+        sd += dl;
+        p.dlin[((int64_t)t * p.B + b) * p.CP + col] = dl;    // the pad columns get their zeros here
+    }
+    const float dsum = head_column_total(sd, red, w, fr, fq, NW);
+    if (w == 0 && fq == 0) {
+        const int64_t TC = (int64_t)p.T * p.CP, i = (int64_t)t * p.CP + col;
+        p.part[i] = dbeta;
+        p.part[TC + i] = dgamma;
+        p.part[2 * TC + i] = dsum;
+    }
+}
+
+struct HeadBwdProdParams {
+    const float *dlin, *part;                                // as the rows launch left them
+    const float *feat;
+    int64_t fst, fsb;
+    const float *w;                                          // [C][K]
+    int T, B, K, C, CP;
+    int R, S, chunk;                                         // rows T B; row-range splits of the weight gradient
+    float *dw;                                               // S == 1: d_weight [C][K]; else the partials [S][C][K]
+    float *dfeat;                                            // or NULL
+    int64_t gst, gsb;
+    float *dbias, *dgamma, *dbeta;
+    int64_t nW, nF, nTail;                                   // tasks of the three roles
+};
+
+__global__ __launch_bounds__(256) void head_bwd_products_kernel(HeadBwdProdParams p)
+{
+    const int lane = threadIdx.x & 63, fr = lane & 15, fq = lane >> 4;
+    int64_t task = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int KQ = ((p.K >> 4) + 3) >> 2;
+    head_f4 acc[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) acc[n] = head_f4{0.f, 0.f, 0.f, 0.f};
+    if (task < p.nW) {
+        // d_weight[c][k] = sum_r dlin[r][c] feat[r][k]: A[c][r] = dlin, B[r][k] = feat; MFMA i of a 16-row step takes
+        // rows rb + 4 i + fq.  One chain per element over r ascending within (step, i, fq).
+        const int CT = p.CP >> 4;
+        const int s = (int)(task / ((int64_t)CT * KQ));
+        const int rem = (int)(task - (int64_t)s * CT * KQ);
+        const int ct = rem / KQ, kq = rem - ct * KQ;
+        const int col = 16 * ct + fr;                        // (< CP: the pad columns of dlin hold zeros)
+        int kc[4];
+#pragma unroll
+        for (int n = 0; n < 4; ++n) kc[n] = min(64 * kq + 16 * n + fr, p.K - 1);
+        const int r0 = s * p.chunk, rend = min(p.R, r0 + p.chunk);
+        for (int rb = r0; rb < rend; rb += 16) {
+            float a[4], b[4][4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int r = rb + 4 * i + fq;
+                const bool ok = r < rend;
+                const int rc = ok ? r : rend - 1;            // (an address inside the range; the value is dropped)
+                const int tt = rc / p.B, bb = rc - tt * p.B;
+                const float av = p.dlin[(int64_t)rc * p.CP + col];
+                const float *fp = p.feat + (int64_t)tt * p.fst + (int64_t)bb * p.fsb;
+                a[i] = ok ? av : 0.f;
+#pragma unroll
+                for (int n = 0; n < 4; ++n) {
+                    const float bv = fp[kc[n]];
+                    b[n][i] = ok ? bv : 0.f;
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int n = 0; n < 4; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[n][i], acc[n], 0, 0, 0);
+        }
+        // acc[n][j] = (c = 16 ct + 4 fq + j, k = 64 kq + 16 n + fr)
+        float *out = p.dw + (int64_t)s * p.C * p.K;
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            const int k = 64 * kq + 16 * n + fr;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int c = 16 * ct + 4 * fq + j;
+                if (c < p.C && k < p.K) out[(int64_t)c * p.K + k] = acc[n][j];
+            }
+        }
+        return;
+    }
+    task -= p.nW;
+    if (task < p.nF) {
+        // d_feat[r][k] = sum_c dlin[r][c] W[c][k]: A[r][c] = dlin (16 bytes of the row per lane: MFMA i of a 16-column
+        // block takes c = 16 cb + 4 fq + i on both operands), B[c][k] = W.
+        const int rt = (int)(task / KQ), kq = (int)(task - (int64_t)rt * KQ);
+        const int ra = min(16 * rt + fr, p.R - 1);
+        const float *ap = p.dlin + (int64_t)ra * p.CP + 4 * fq;
+        int kc[4];
+#pragma unroll
+        for (int n = 0; n < 4; ++n) kc[n] = min(64 * kq + 16 * n + fr, p.K - 1);
+        for (int cb = 0; cb < (p.CP >> 4); ++cb) {
+            const head_f4 a = *reinterpret_cast<const head_f4 *>(ap + 16 * cb);
+            float b[4][4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int c = 16 * cb + 4 * fq + i;
+                const bool ok = c < p.C;
+                const float *wp = p.w + (int64_t)(ok ? c : p.C - 1) * p.K;
+#pragma unroll
+                for (int n = 0; n < 4; ++n) {
+                    const float bv = wp[kc[n]];
+                    b[n][i] = ok ? bv : 0.f;
+                }
+            }
+#pragma unroll
+            for (int n = 0; n < 4; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b[n][0], acc[n], 0, 0, 0);
+#pragma unroll
+            for (int n = 0; n < 4; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b[n][1], acc[n], 0, 0, 0);
+#pragma unroll
+            for (int n = 0; n < 4; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b[n][2], acc[n], 0, 0, 0);
+#pragma unroll
+            for (int n = 0; n < 4; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b[n][3], acc[n], 0, 0, 0);
+        }
+        // acc[n][j] = (r = 16 rt + 4 fq + j, k = 64 kq + 16 n + fr)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int r = 16 * rt + 4 * fq + j;
+            if (r >= p.R) continue;
+            const int tt = r / p.B, bb = r - tt * p.B;
+            float *out = p.dfeat + (int64_t)tt * p.gst + (int64_t)bb * p.gsb;
+#pragma unroll
+            for (int n = 0; n < 4; ++n) {
+                const int k = 64 * kq + 16 * n + fr;
+                if (k < p.K) out[k] = acc[n][j];
+            }
+        }
+        return;
+    }
+    task -= p.nF;
+    if (task < p.nTail) {
+        // the per-frame partials summed over the frames, t ascending
+        const int64_t i = task * 64 + lane;
+        const int which = (int)(i / p.CP), c = (int)(i - (int64_t)which * p.CP);
+        if (which < 3 && c < p.C) {
+            const float *q = p.part + (int64_t)which * p.T * p.CP + c;
+            float s = 0.f;
+            for (int t = 0; t < p.T; ++t) s += q[(int64_t)t * p.CP];
+            (which == 0 ? p.dbeta : which == 1 ? p.dgamma : p.dbias)[c] = s;
+        }
+    }
+}
+
+// d_weight = the S partial tiles added in ascending split order
+__global__ __launch_bounds__(256) void head_bwd_reduce_kernel(const float *wpart, float *dw, int64_t n, int S)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float s = 0.f;
+    for (int k = 0; k < S; ++k) s += wpart[(int64_t)k * n + i];
+    dw[i] = s;
+}
+
+}  // namespace ctc
+
+extern "C" size_t ctc_amd_head_backward_scratch_bytes(int T, int B, int K, int C)
+{
+    if (T < 1 || B < 1 || K < 1 || C < 1 || !ctc::head_bwd_shape_ok(T, B, K, C)) return 0;
+    return ctc::head_bwd_layout(T, B, K, C).total + ctc::kHeadBwdAlign;           // (the entry aligns the pointer itself)
+}
+
+extern "C" int ctc_amd_head_backward(const float *d_out, int64_t dout_stride_t, int64_t dout_stride_b,
+                                     const float *feat, int64_t feat_stride_t, int64_t feat_stride_b,
+                                     const float *weight, const float *bn_weight, const float *bn_bias,
+                                     const float *linear_out,
+                                     const float *save_mean, const float *save_invstd,
+                                     const float *running_mean, const float *running_var, float eps,
+                                     const float *mask,
+                                     int T, int B, int K, int C,
+                                     float *d_feat, int64_t dfeat_stride_t, int64_t dfeat_stride_b,
+                                     float *d_weight, float *d_bias, float *d_bn_weight, float *d_bn_bias,
+                                     void *scratch, size_t scratch_bytes, void *stream)
+{
+    if (!d_out || !feat || !weight || !bn_weight || !bn_bias || !linear_out) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (!d_weight || !d_bias || !d_bn_weight || !d_bn_bias || !scratch) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (T < 1 || B < 1 || K < 1 || C < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
+    const bool train = save_mean && save_invstd && !running_mean && !running_var;
+    const bool eval = running_mean && running_var && !save_mean && !save_invstd;
+    if (!train && !eval) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (train && B < 2) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (dout_stride_b < C) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (d_feat && dfeat_stride_b < K) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (scratch_bytes < ctc_amd_head_backward_scratch_bytes(T, B, K, C)) return CTC_AMD_ERR_BAD_ARGUMENT;
+    // what ctc_amd_head_forward refuses, and row counts beyond the launches' index range
+    if (!ctc::head_bwd_shape_ok(T, B, K, C) || (feat_stride_b & 3) != 0 || (feat_stride_t & 3) != 0 ||
+        (reinterpret_cast<uintptr_t>(feat) & 15) != 0 || (reinterpret_cast<uintptr_t>(weight) & 15) != 0)
+        return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
+    const ctc::HeadBwdLayout L = ctc::head_bwd_layout(T, B, K, C);
+    char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(scratch) + ctc::kHeadBwdAlign - 1) /
+                                          ctc::kHeadBwdAlign * ctc::kHeadBwdAlign);
+    float *dlin = reinterpret_cast<float *>(base + L.dlin), *part = reinterpret_cast<float *>(base + L.part);
+    float *wpart = reinterpret_cast<float *>(base + L.wpart);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+
+    ctc::HeadBwdRowsParams r;
+    r.dout = d_out; r.dst = dout_stride_t; r.dsb = dout_stride_b;
+    r.lin = linear_out; r.gamma = bn_weight; r.beta = bn_bias;
+    r.smean = save_mean; r.sinv = save_invstd; r.rmean = running_mean; r.rvar = running_var;
+    r.mask = mask; r.eps = eps;
+    r.T = T; r.B = B; r.C = C; r.CP = L.CP;
+    r.dlin = dlin; r.part = part;
+    int rc = launch<ctc::head_bwd_rows_kernel>(dim3(T, L.CP / 16), dim3(64 * ((B + 15) / 16)), 0, st, r);
+    if (rc) return rc;
+
+    ctc::HeadBwdProdParams q;
+    q.dlin = dlin; q.part = part;
+    q.feat = feat; q.fst = feat_stride_t; q.fsb = feat_stride_b; q.w = weight;
+    q.T = T; q.B = B; q.K = K; q.C = C; q.CP = L.CP;
+    q.R = T * B; q.S = L.S; q.chunk = L.chunk;
+    q.dw = L.S > 1 ? wpart : d_weight;
+    q.dfeat = d_feat; q.gst = dfeat_stride_t; q.gsb = dfeat_stride_b;
+    q.dbias = d_bias; q.dgamma = d_bn_weight; q.dbeta = d_bn_bias;
+    const int64_t KQ = (K / 16 + 3) / 4;
+    q.nW = (int64_t)(L.CP / 16) * KQ * L.S;
+    q.nF = d_feat ? (((int64_t)q.R + 15) / 16) * KQ : 0;
+    q.nTail = (3 * (int64_t)L.CP + 63) / 64;
+    const int64_t tasks = q.nW + q.nF + q.nTail;
+    rc = launch<ctc::head_bwd_products_kernel>(dim3((unsigned)((tasks + 3) / 4)), dim3(256), 0, st, q);
+    if (rc || L.S == 1) return rc;
+    const int64_t n = (int64_t)C * K;
+    return launch<ctc::head_bwd_reduce_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                                               (const float *)wpart, d_weight, n, L.S);
 }

@@ -17,8 +17,12 @@ walks the recurrence from there, so ``v_all [T,B,C]`` never goes to memory; the 
 profiles/r13_lstm_forward.md -- 50 us against 70 us per forward at the reference's sizes; at T = 150 the two launches win).
 
 Same attribute names as the reference (``v``, ``v.layers``, ``v_cell``): its checkpoints load unchanged.  The backward
-pass through the cell is plain torch arithmetic on the gate activations the forward launch saved (the recurrence's
-backward is not on the HIP path).  No CPU path: non-HIP tensors raise.
+pass: the recurrence is one launch (``ctc_amd_lstm_series_backward``) plus three GEMMs on its result (rocBLAS through torch);
+the head's backward is HIP as well (``ctc_amd_head_backward`` / ``head_backward``: the BatchNorm / ReLU / Dropout row pass,
+then both products, the column sums and the sums over the frames on the matrix cores -- two launches, three when the weight
+gradient splits its rows) for T B <= ``HEAD_BACKWARD_MAX_ROWS`` rows (measured, profiles/r14_head_backward.md).  Beyond that
+gate, and for the shapes the entry does not take (B > 256, K not a multiple of 16, unaligned rows), the head's backward is
+torch arithmetic (``_head_backward_torch``: elementwise kernels and two rocBLAS GEMMs).  No CPU path: non-HIP tensors raise.
 """
 import torch
 import torch.nn as nn
@@ -75,10 +79,77 @@ def head_forward(feat, weight, bias, bn_weight, bn_bias, running_mean=None, runn
     return out, lin, mean, var, inv
 
 
+def head_backward(d_out, feat, weight, bn_weight, bn_bias, lin, mean=None, invstd=None, running_mean=None, running_var=None,
+                  eps=1e-5, mask=None, need_dfeat=True):
+    """The backward of ``head_forward`` on the HIP path (``ctc_amd_head_backward``: two launches, three when T B > 128) ->
+    (d_feat [T,B,K] | None, d_weight [C,K], d_bias [C], d_bn_weight [C], d_bn_bias [C]), or None when the entry does not take
+    the shape (what ``head_forward`` refuses, or T B > 2^22 rows).  ``lin``: the forward's Linear output [T,B,C];
+    train mode: ``mean`` / ``invstd`` [T,C] as the forward saved them; eval mode: ``running_mean`` / ``running_var`` [C] and
+    ``eps``; ``mask`` as the forward took it.  Deterministic (no atomics, fixed sum orders).
+
+    The scratch (dlin [T B, C padded to 16], the per-frame partial sums, the partial weight gradients) is one ``torch.empty``
+    per call, not a cached buffer: torch's caching allocator hands the same block back without a device call once the shape has
+    been seen, the stream ordering of the block is torch's own business that way, and under ``torch.cuda.graph`` capture the
+    block comes from the graph's private pool, which a buffer cached outside the capture could not promise."""
+    F._require_hip(d_out, "d_out")
+    F._require_hip(feat, "feat")
+    T, B, K = feat.shape
+    C = weight.shape[0]
+    dev = feat.device
+    f32 = torch.float32
+    do = d_out if (d_out.dtype is f32 and d_out.stride(2) == 1) else d_out.float().contiguous()
+    f = feat if (feat.dtype is f32 and feat.stride(2) == 1) else feat.float().contiguous()
+    cont = lambda t: None if t is None else (t if (t.dtype is f32 and t.is_contiguous()) else t.float().contiguous())   # noqa: E731
+    w, g, be, ln, mn, iv, rm, rv, mk = (cont(t) for t in (weight, bn_weight, bn_bias, lin, mean, invstd, running_mean,
+                                                           running_var, mask))
+    lib = _lib.load()
+    nbytes = lib.ctc_amd_head_backward_scratch_bytes(T, B, K, C)
+    if nbytes == 0 and min(T, B, K, C) >= 1:
+        return None
+    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    d_feat = torch.empty((T, B, K), dtype=f32, device=dev) if need_dfeat else None
+    d_weight = torch.empty((C, K), dtype=f32, device=dev)
+    d_bias, d_gamma, d_beta = (torch.empty(C, dtype=f32, device=dev) for _ in range(3))
+    ptr = lambda t: None if t is None else t.data_ptr()     # noqa: E731
+    with F._on_device(dev):
+        rc = lib.ctc_amd_head_backward(do.data_ptr(), do.stride(0), do.stride(1), f.data_ptr(), f.stride(0), f.stride(1),
+                                       w.data_ptr(), g.data_ptr(), be.data_ptr(), ln.data_ptr(), ptr(mn), ptr(iv), ptr(rm), ptr(rv),
+                                       float(eps), ptr(mk), T, B, K, C, ptr(d_feat), B * K if need_dfeat else 0, K if need_dfeat else 0,
+                                       d_weight.data_ptr(), d_bias.data_ptr(), d_gamma.data_ptr(), d_beta.data_ptr(),
+                                       scratch.data_ptr(), nbytes, F._stream_handle(dev))
+    if rc == _lib.ERR_UNSUPPORTED_SHAPE:
+        return None
+    if rc:
+        _lib.check(rc, "ctc_amd_head_backward")
+    return d_feat, d_weight, d_bias, d_gamma, d_beta
+
+
+def _head_backward_torch(d_out, feat, weight, gamma, beta, lin, mean, inv, mask, train, need_dfeat):
+    """the head's backward as torch arithmetic (BatchNorm's own formulas on the saved Linear output and statistics, two
+    GEMMs over all frames at once): what runs outside the gate.  mean / inv: [T,C] (train) or [1,C] (eval)."""
+    T, B, C = lin.shape
+    xhat = (lin - mean.unsqueeze(1)) * inv.unsqueeze(1)
+    dy = d_out.float()
+    if mask is not None:
+        dy = dy * mask
+    dy = dy * ((xhat * gamma + beta) > 0)
+    dbeta = dy.sum((0, 1))
+    dgamma = (dy * xhat).sum((0, 1))
+    dxh = dy * gamma
+    if train:                                            # BatchNorm over the B rows of each frame
+        dlin = inv.unsqueeze(1) * (dxh - dxh.mean(1, keepdim=True) - xhat * (dxh * xhat).mean(1, keepdim=True))
+    else:
+        dlin = dxh * inv.unsqueeze(1)
+    flat = dlin.reshape(T * B, C)
+    dW = flat.t() @ feat.reshape(T * B, -1).float()
+    dfeat = (flat @ weight.float()).reshape(feat.shape) if need_dfeat else None
+    return dfeat, dW, flat.sum(0), dgamma, dbeta
+
+
 class _HeadFn(torch.autograd.Function):
     """feat [T,B,K], Linear and BatchNorm parameters, running statistics (eval) or None (train), mask -> the head's output
-    [T,B,C] (+ the batch statistics, non-differentiable).  Forward: one HIP launch.  Backward: elementwise torch arithmetic on
-    the saved Linear output and statistics (BatchNorm's own formulas) and two GEMMs over all frames at once."""
+    [T,B,C] (+ the batch statistics, non-differentiable).  Forward: one HIP launch.  Backward: ``head_backward`` (HIP) for
+    T B <= ``HEAD_BACKWARD_MAX_ROWS`` rows; ``_head_backward_torch`` beyond the gate and for shapes the entry does not take."""
 
     @staticmethod
     def forward(ctx, feat, weight, bias, bn_weight, bn_bias, running_mean, running_var, eps, mask):
@@ -92,7 +163,7 @@ class _HeadFn(torch.autograd.Function):
         if need:
             if not ctx.train:
                 mean, inv = running_mean.float().unsqueeze(0), torch.rsqrt(running_var.float() + float(eps)).unsqueeze(0)
-            ctx.save_for_backward(feat, weight, bn_weight, bn_bias, lin, mean, inv, mask)
+            ctx.save_for_backward(feat, weight, bn_weight, bn_bias, lin, mean, inv, mask, running_mean, running_var)
         stats = (mean, var) if ctx.train else (None, None)
         if ctx.train:
             ctx.mark_non_differentiable(mean, var)
@@ -101,24 +172,18 @@ class _HeadFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_out, _dm=None, _dv=None):
-        feat, weight, gamma, beta, lin, mean, inv, mask = ctx.saved_tensors
-        T, B, C = lin.shape
-        xhat = (lin - mean.unsqueeze(1)) * inv.unsqueeze(1)
-        dy = d_out.float()
-        if mask is not None:
-            dy = dy * mask
-        dy = dy * ((xhat * gamma + beta) > 0)
-        dbeta = dy.sum((0, 1))
-        dgamma = (dy * xhat).sum((0, 1))
-        dxh = dy * gamma
-        if ctx.train:                                        # BatchNorm over the B rows of each frame
-            dlin = inv.unsqueeze(1) * (dxh - dxh.mean(1, keepdim=True) - xhat * (dxh * xhat).mean(1, keepdim=True))
-        else:
-            dlin = dxh * inv.unsqueeze(1)
-        flat = dlin.reshape(T * B, C)
-        dW = flat.t() @ feat.reshape(T * B, -1).float()
-        dfeat = (flat @ weight.float()).reshape(feat.shape) if ctx.needs_input_grad[0] else None
-        return dfeat, dW, flat.sum(0), dgamma, dbeta, None, None, None, None
+        feat, weight, gamma, beta, lin, mean, inv, mask, rmean, rvar = ctx.saved_tensors
+        T, B, _ = lin.shape
+        need_dfeat = ctx.needs_input_grad[0]
+        res = None
+        if T * B <= HEAD_BACKWARD_MAX_ROWS:
+            if ctx.train:
+                res = head_backward(d_out, feat, weight, gamma, beta, lin, mean, inv, None, None, ctx.eps, mask, need_dfeat)
+            else:
+                res = head_backward(d_out, feat, weight, gamma, beta, lin, None, None, rmean, rvar, ctx.eps, mask, need_dfeat)
+        if res is None:
+            res = _head_backward_torch(d_out, feat, weight, gamma, beta, lin, mean, inv, mask, ctx.train, need_dfeat)
+        return tuple(res) + (None, None, None, None)
 
 
 def lstm_cell_step(x, h, c, w_ih, w_hh, b_ih, b_hh, series_row=None, pad_value=PAD_LOGIT, want_gates=False):
@@ -228,6 +293,15 @@ def lstm_forward(feat, weight, bias, bn_weight, bn_bias, running_mean, running_v
 # T = 10, 12 and 16 win at B = 10 and at B = 256 (0.72 ... 0.78 and 0.54 ... 0.59 of the two launches' time), T = 20 loses at
 # B = 10 (1.07 x), T = 150 at every B (1.2 - 1.5 x); the bound is the largest measured point that wins at every B measured.
 FUSED_FORWARD_MAX_WG_ROWS = 64
+
+# _HeadFn.backward takes the HIP path (head_backward) up to this many head rows T B; 0 closes the gate.  The scalar is T B
+# because the measurements are ordered by it: the row pass and both products are T B rows of work, the torch arithmetic is
+# launch-bound (110 - 150 us) up to a few thousand rows and a pair of rocBLAS GEMMs beyond, and at equal T B the ratio moves
+# little with how T B splits into T and B.  Measured, not guessed (profiles/r14_head_backward.md, K = 1024, with and without
+# d_feat): at T B = 100 ... 10240 the new call's median is 0.15 ... 0.79 of the torch arithmetic's and below the minimum of
+# its rounds at every B in {10, 64, 256} and C in {33, 158}; at T B = 38400 it wins at C = 33 (0.24 - 0.35 x) and loses at
+# C = 158 (1.02 - 1.09 x).  The bound is the largest measured point that wins at every B and C measured (r13's rule).
+HEAD_BACKWARD_MAX_ROWS = 10240
 
 
 class _SeriesFn(torch.autograd.Function):

@@ -463,6 +463,42 @@ int ctc_amd_lstm_forward(const float *feat, int64_t feat_stride_t, int64_t feat_
                          float *series, int64_t series_stride_t, int64_t series_stride_b, int series_cols, float pad_value,
                          float *h_out, float *c_out, void *stream);
 
+/* The BACKWARD of ctc_amd_head_forward on the same launch path: from d_out, the upstream gradient of the head's output (row
+ * (t, b) of C floats at d_out + t * dout_stride_t + b * dout_stride_b), and what the forward call took and saved to the
+ * gradients of feat (d_feat, rows of K floats at (dfeat_stride_t, dfeat_stride_b); NULL: not wanted), of the Linear layer
+ * (d_weight [C,K], d_bias [C]) and of BatchNorm's affine parameters (d_bn_weight, d_bn_bias [C]).  All fp32.
+ *   linear_out [T,B,C]: the forward's linear_out;  TRAIN mode: save_mean / save_invstd [T,C] as the forward saved them
+ *   (running_mean, running_var NULL);  EVAL mode: running_mean / running_var [C] and eps (save_mean, save_invstd NULL);
+ *   mask [T,B,C] or NULL as the forward took it.  With mean, inv the statistics the forward normalised with:
+ *     xhat = (lin - mean) inv;   dy = d_out mask [y > 0], y being the forward's own BatchNorm output (same operations, same
+ *     order: the gate agrees with the forward's ReLU bit for bit);   dbeta_t = sum_b dy, dgamma_t = sum_b dy xhat per frame;
+ *     train: dlin = inv g (dy - dbeta_t / B - xhat dgamma_t / B) (BatchNorm over each frame's B rows);  eval: dlin = dy g inv;
+ *     d_bn_bias = sum_t dbeta_t, d_bn_weight = sum_t dgamma_t, d_bias = sum_tb dlin, d_weight = sum_tb dlin^T feat,
+ *     d_feat = dlin W.
+ * The products are exact fp32 on the matrix cores (an fmaf chain per output element).  Deterministic: no atomics, every sum
+ * in an order fixed by the shape (rows of a frame: lane quarters, then waves; frames ascending; d_weight: rows ascending
+ * inside one of S = min(64, ceil(T B / 128)) row ranges, the ranges added ascending).  Two launches on `stream` (three when
+ * S > 1), no allocation, no host synchronisation: safe under stream capture.  Every element of every output that is not NULL
+ * is written; d_feat rows only in columns [0,K).  scratch: at least ctc_amd_head_backward_scratch_bytes(T, B, K, C) bytes of
+ * device memory, any alignment, contents irrelevant (nothing is read from it that the same call has not written).
+ * CTC_AMD_ERR_BAD_ARGUMENT (decided first): a NULL among the required pointers, a size < 1, statistics that are not exactly
+ * one complete pair, train mode with B < 2, dout_stride_b < C, dfeat_stride_b < K, scratch_bytes below the query.
+ * CTC_AMD_ERR_UNSUPPORTED_SHAPE: what ctc_amd_head_forward refuses (B > 256, K not a multiple of 16, feat strides not
+ * multiples of 4, feat or weight not 16-byte aligned) and T B > 2^22 rows.  d_feat needs no alignment beyond a float's (it
+ * is written with 4-byte stores).  The query answers 0 for sizes < 1 and for shapes the entry does not take. */
+size_t ctc_amd_head_backward_scratch_bytes(int T, int B, int K, int C);
+int ctc_amd_head_backward(const float *d_out, int64_t dout_stride_t, int64_t dout_stride_b,
+                          const float *feat, int64_t feat_stride_t, int64_t feat_stride_b,
+                          const float *weight, const float *bn_weight, const float *bn_bias,
+                          const float *linear_out,
+                          const float *save_mean, const float *save_invstd,
+                          const float *running_mean, const float *running_var, float eps,
+                          const float *mask,
+                          int T, int B, int K, int C,
+                          float *d_feat, int64_t dfeat_stride_t, int64_t dfeat_stride_b,
+                          float *d_weight, float *d_bias, float *d_bn_weight, float *d_bn_bias,
+                          void *scratch, size_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
