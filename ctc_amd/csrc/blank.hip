@@ -1019,6 +1019,13 @@ __device__ __forceinline__ void blank_row_emit(const BlankParams &p, int t, int 
         m = fmaxf(m, v[k]);
     }
     m = wave_max(m);
+    // On every live row m is the sample's log-likelihood to within log2(n).  A sample whose every path crosses a -inf
+    // emission (kNegB in the lattice) has none: blank_publish's threshold, nll = +inf, and a zero row here -- the
+    // softmax below would normalise a row of -k 1e30 into a distribution.  Wave-uniform; a NaN (poisoned) row goes on.
+    if (m < -1.0e29f) {
+        blank_row_fill<VEC4>(p, t, b, 0.f);
+        return;
+    }
     float ssum = 0.f, blank_part = 0.f;
 #pragma unroll
     for (int k = 0; k < K; ++k) {

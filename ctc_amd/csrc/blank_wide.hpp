@@ -266,6 +266,10 @@ __global__ __launch_bounds__(kGradWaves * kWave) void blank_wide_grad_kernel(Bla
 #pragma unroll
             for (int k = 0; k < K; ++k) m = fmaxf(m, v[q][k]);
         m = wave_max(m);
+        if (m < -1.0e29f) {                                  // no alignment through the emissions: as blank_row_emit
+            blank_row_fill<VEC4>(p, t, b, 0.f);
+            continue;
+        }
         float ssum = 0.f, blank_part = 0.f;
 #pragma unroll
         for (int q = 0; q < W; ++q) {

@@ -490,7 +490,12 @@ def blank_ctc_loss(log_probs, targets, input_lengths, target_lengths, blank=0, b
     semantics (models/layers/AsyncTFCriterion.py:198): log_probs are normalised
     log-probabilities, loss = mean_b(nll_b / max(L_b,1)).  ``targets`` [B,S] with S <= 1023 label columns
     (CtcAmdError beyond); more than 255 columns take the wide lattice path of the library (several waves per chain).
-    ``blank_best_path`` / ``blank_forced_align`` and ``blank_posteriors`` take the same widths."""
+    ``blank_best_path`` / ``blank_forced_align`` and ``blank_posteriors`` take the same widths.
+
+    ``-inf`` log-probs are allowed (a masked vocabulary); the gradient at a ``-inf`` entry is exactly 0.  A sample with
+    no alignment -- through its lengths (``T_b < L_b + adjacent repeats``) or through its emissions (every path crosses
+    a ``-inf`` entry) -- has ``nll = +inf`` like torch and an all-zero gradient where torch gives NaN; ``loss`` is then
+    ``+inf`` and the gradients of the other samples are what they would be without it."""
     return _LossFn.apply(log_probs, targets, input_lengths, target_lengths, _lib.BLANK, batch_total, blank)
 
 

@@ -74,6 +74,21 @@ def test_exact_parity(dev, shape, ragged):
         assert (score == -np.inf).any() and np.isfinite(score).any() and (np_(L) == 0).any()
 
 
+def test_masked_classes(dev):
+    """-inf log-probs (tests/blank_grad_ref.py's mask): holes in the blank and in sample 0's first label, and samples
+    with no alignment through their EMISSIONS alone -- path -1 and score -inf exactly where the loss has nll = +inf"""
+    import ctc_amd
+    from tests.blank_grad_ref import feasible_by_length, make_case
+    lp, tgt, Tb, L = make_case("k2", "masked")
+    path, score = _run(dev, lp, tgt, Tb, L)
+    rp, rs = _check(path, score, lp, tgt, Tb, L)
+    none = rs == -np.inf
+    assert list(none) == [False, False, True, False, False, True] and feasible_by_length(tgt, Tb, L).all()
+    assert (rp[none] == -1).all() and not np.isnan(rs).any()
+    _, nll = ctc_amd.blank_ctc_loss(lp.to(dev), tgt.to(dev), Tb.to(dev), L.to(dev))
+    assert np.array_equal(np_(nll) == np.inf, none)
+
+
 @pytest.mark.parametrize("T,B,C,S", [(50, 8, 20, 6), (300, 6, 1000, 100)])
 def test_blank_last_class(dev, T, B, C, S):
     lp, tgt, Tb, L = _case(3, T, B, C, S, ragged=T < 100, blank=C - 1)

@@ -96,6 +96,20 @@ def test_final_state_at_a_wave_seam(dev, form):
         assert rp[2, 599] == 1023
 
 
+def test_masked_classes(dev):
+    """-inf log-probs (tests/blank_grad_ref.py's mask): holes in the blank and in sample 0's first label, and a sample
+    with no alignment through its EMISSIONS alone -- path -1 and score -inf exactly where the loss has nll = +inf"""
+    from tests.blank_grad_ref import feasible_by_length, make_case
+    lp, tgt, Tb, L = make_case("w2", "masked")
+    path, score = _run(dev, lp, tgt, Tb, L)
+    rp, rs = _check(path, score, lp, tgt, Tb, L)
+    none = rs == -np.inf
+    assert list(none) == [False, False, True] and feasible_by_length(tgt, Tb, L).all()
+    assert (rp[none] == -1).all() and not np.isnan(rs).any()
+    nll = run_loss(dev, lp, tgt, Tb, L, grad=False)["nll"]
+    assert np.array_equal(np_(nll) == np.inf, none)
+
+
 def test_ties_quantised_inputs(dev):
     T, B, C, S = 700, 2, 12, 300
     lp, tgt, Tb, _ = synth_blank(6, T, B, C, S)
