@@ -256,7 +256,8 @@ __global__ __launch_bounds__(kLstmThreads) void lstm_series_kernel(LstmSeriesPar
 // pre-activation gradients of its unit (written out: [T][B][4H]), and takes dh_{t-1}(s, j) = sum_r W_hh[r][j] dpre(s, r) with
 // column j of W_hh in registers and the pre-activation gradients of the sample's 4H gate rows read from LDS (16-byte
 // broadcasts, double-buffered: one barrier per frame).  Everything that is not a recurrence -- dx_t = dpre_t W_ih, the three
-// parameter gradients -- is a plain GEMM over all frames at once on the result (the caller: rocBLAS through torch).
+// parameter gradients -- runs over all frames at once on the result: lstm_bwd_products_kernel behind this launch in
+// ctc_amd_lstm_backward (below), or GEMMs of the caller's (ctc_amd_lstm_series_backward alone: rocBLAS through torch).
 constexpr int kSeriesG = 4 * 64;
 
 struct LstmSeriesBwdParams {
@@ -386,9 +387,24 @@ extern "C" int ctc_amd_lstm_cell_step(const float *x, const float *h, const floa
 }
 
 
+// The enqueue of lstm_series_bwd_kernel, shared by ctc_amd_lstm_series_backward and ctc_amd_lstm_backward (the callers have
+// checked the arguments): one launch on `stream`.
+static int enqueue_series_backward(const float *d_series, int64_t ds_stride_t, int64_t ds_stride_b,
+                                   const float *gates, const float *cells, const float *w_hh,
+                                   int T, int B, int H, float *dpre_out, float *dh0_out, float *dc0_out, hipStream_t stream)
+{
+    LstmSeriesBwdParams p;
+    p.d_series = d_series; p.ds_stride_t = ds_stride_t; p.ds_stride_b = ds_stride_b;
+    p.gates = gates; p.cells = cells; p.w_hh = w_hh;
+    p.T = T; p.B = B; p.H = H;
+    p.dpre = dpre_out; p.dh0 = dh0_out; p.dc0 = dc0_out;
+    const size_t smem = (size_t)2 * kSeriesSamples * 4 * H * sizeof(float);
+    return launch<lstm_series_bwd_kernel>(dim3((B + kSeriesSamples - 1) / kSeriesSamples), dim3(kLstmThreads), smem, stream, p);
+}
+
 // The backward recurrence of ctc_amd_lstm_series (same sizes): from the upstream gradient of v_series and the state the
 // forward launch saved to the pre-activation gradients of every frame and the gradients of (h0, c0).  The rest of the
-// backward pass is three GEMMs on dpre (ctc_amd/producer.py).
+// backward pass has no recurrence in it: ctc_amd_lstm_backward (below) runs this launch and the products behind it.
 extern "C" int ctc_amd_lstm_series_backward(const float *d_series, int64_t ds_stride_t, int64_t ds_stride_b,
                                             const float *gates, const float *cells, const float *w_hh,
                                             int T, int B, int H, float *dpre_out, float *dh0_out, float *dc0_out, void *stream)
@@ -396,14 +412,8 @@ extern "C" int ctc_amd_lstm_series_backward(const float *d_series, int64_t ds_st
     if (!d_series || !gates || !cells || !w_hh || !dpre_out || !dh0_out || !dc0_out) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (T < 1 || B < 1 || H < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (4 * H > kSeriesG || kSeriesSamples * H > kLstmThreads) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
-    LstmSeriesBwdParams p;
-    p.d_series = d_series; p.ds_stride_t = ds_stride_t; p.ds_stride_b = ds_stride_b;
-    p.gates = gates; p.cells = cells; p.w_hh = w_hh;
-    p.T = T; p.B = B; p.H = H;
-    p.dpre = dpre_out; p.dh0 = dh0_out; p.dc0 = dc0_out;
-    const size_t smem = (size_t)2 * kSeriesSamples * 4 * H * sizeof(float);
-    return launch<lstm_series_bwd_kernel>(dim3((B + kSeriesSamples - 1) / kSeriesSamples), dim3(kLstmThreads), smem,
-                                          static_cast<hipStream_t>(stream), p);
+    return enqueue_series_backward(d_series, ds_stride_t, ds_stride_b, gates, cells, w_hh, T, B, H, dpre_out, dh0_out, dc0_out,
+                                   static_cast<hipStream_t>(stream));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1045,4 +1055,272 @@ extern "C" int ctc_amd_head_backward(const float *d_out, int64_t dout_stride_t, 
     const int64_t n = (int64_t)C * K;
     return launch<ctc::head_bwd_reduce_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
                                                (const float *)wpart, d_weight, n, L.S);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The BACKWARD of ctc_amd_lstm_series, whole: the recurrence launch above writes dpre [T B][4H] into the scratch,
+// and everything that is not a recurrence follows as HIP launches on the same stream, head_bwd_products_kernel's scheme:
+//   products  one wave per task, exact fp32 on the matrix cores (an fmaf chain per output element):
+//               d^T x tile [16 gate rows x (I or H)] of one row-range split, contracting over the rows (4-byte operand loads);
+//                 the role runs twice -- against x (d_w_ih) and against h_{t-1} (d_w_hh), which is read IN PLACE: h0 for
+//                 t = 0, row t - 1 of the forward's v_series at its own pitch otherwise;
+//               d W tile [16 rows x I] (d_x), contracting over the 4H gate rows (16-byte loads of the dpre row);
+//               column sums: 64 gate columns of one row-range split, rows ascending (the biases);
+//   reduce    (S > 1 only) the S partial [d_w_ih | d_w_hh | d_b] added in ascending split order; writes d_b_ih and d_b_hh.
+// S and the rows per split are the head's rule (head_bwd_splits), with R = T B: chunk = 16 ceil(ceil(R / min(64, ceil(R / 128))) / 16)
+// rows per range, S = ceil(R / chunk) ranges (9600 rows: 60 ranges of 160) -- a function of T B alone: the same shape sums
+// in the same order.
+namespace ctc {
+
+struct LstmBwdLayout {                                       // byte offsets into the (aligned) scratch
+    size_t dpre, wpart, total;
+    int S, chunk;
+    int64_t ntot;                                            // floats of one split's partials: 4H (I + H + 1)
+};
+
+inline bool lstm_bwd_shape_ok(int T, int B, int I, int H)
+{
+    // ctc_amd_lstm_series's own bounds, compared without arithmetic on the sizes (no int overflow for any I, H)
+    if (I > kLstmThreads / kSeriesSamples || H > kLstmThreads / kSeriesSamples || H > kSeriesG / 4 || I > kSeriesK - H) return false;
+    return (int64_t)T * B <= kHeadBwdMaxRows;
+}
+
+inline LstmBwdLayout lstm_bwd_layout(int T, int B, int I, int H)
+{
+    auto up = [](size_t v) { return (v + kHeadBwdAlign - 1) / kHeadBwdAlign * kHeadBwdAlign; };
+    LstmBwdLayout L;
+    const size_t R = (size_t)T * (size_t)B;
+    head_bwd_splits((int64_t)R, L.S, L.chunk);
+    L.ntot = (int64_t)4 * H * (I + H + 1);
+    L.dpre = 0;
+    L.wpart = up(R * 4 * H * sizeof(float));
+    L.total = L.wpart + (L.S > 1 ? up((size_t)L.S * (size_t)L.ntot * sizeof(float)) : 0);
+    return L;
+}
+
+struct LstmBwdProdParams {
+    const float *dpre;                                       // [R][G] as the recurrence launch left it
+    const float *x;                                          // rows of I at (xst, xsb)
+    int64_t xst, xsb;
+    const float *h0, *series;                                // h_{t-1}: h0 [B][H] for t = 0, row (t - 1, b) of series otherwise
+    int64_t sst, ssb;
+    const float *w_ih;                                       // [G][I]
+    int B, I, H, G;
+    int R, S, chunk;                                         // rows T B; row-range splits
+    float *dwi, *dwh, *db0, *db1;                            // S == 1: the outputs; else split 0 of the partials (db1 NULL)
+    int64_t pstride;                                         // floats between two splits' partials
+    float *dx;                                               // or NULL
+    int64_t dxst, dxsb;
+    int64_t nW, nX, nB;                                      // tasks of the three roles
+};
+
+__global__ __launch_bounds__(256) void lstm_bwd_products_kernel(LstmBwdProdParams p)
+{
+    const int lane = threadIdx.x & 63, fr = lane & 15, fq = lane >> 4;
+    int64_t task = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int G = p.G, GT = (G + 15) >> 4;
+    head_f4 acc[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) acc[n] = head_f4{0.f, 0.f, 0.f, 0.f};
+    if (task < p.nW) {
+        // d_w[g][k] = sum_r dpre[r][g] v[r][k] (v = x or h_{t-1}): A[g][r] = dpre, B[r][k] = v; MFMA i of a 16-row step takes
+        // rows rb + 4 i + fq.  One chain per element over r ascending within (step, i, fq).
+        const int s = (int)(task / (2 * GT));
+        const int rem = (int)(task - (int64_t)s * 2 * GT);
+        const int which = rem / GT, gt = rem - which * GT;   // 0: x, 1: h_{t-1}
+        const int K = which ? p.H : p.I, NT = (K + 15) >> 4;
+        const int col = 16 * gt + fr;
+        const bool colok = col < G;
+        const int colc = colok ? col : G - 1;
+        int kc[4];
+#pragma unroll
+        for (int n = 0; n < 4; ++n) kc[n] = min(16 * n + fr, K - 1);
+        const int r0 = s * p.chunk, rend = min(p.R, r0 + p.chunk);
+        for (int rb = r0; rb < rend; rb += 16) {
+            float a[4], b[4][4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int r = rb + 4 * i + fq;
+                const bool ok = r < rend;
+                const int rc = ok ? r : rend - 1;            // (an address inside the range; the value is dropped)
+                const int tt = rc / p.B, bb = rc - tt * p.B;
+                const float av = p.dpre[(int64_t)rc * G + colc];
+                const float *vp = which == 0 ? p.x + (int64_t)tt * p.xst + (int64_t)bb * p.xsb
+                                  : tt == 0  ? p.h0 + (int64_t)bb * p.H
+                                             : p.series + (int64_t)(tt - 1) * p.sst + (int64_t)bb * p.ssb;
+                a[i] = (ok && colok) ? av : 0.f;
+#pragma unroll
+                for (int n = 0; n < 4; ++n) {
+                    float bv = 0.f;
+                    if (n < NT) bv = vp[kc[n]];              // (uniform)
+                    b[n][i] = ok ? bv : 0.f;
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int n = 0; n < 4; ++n)
+                    if (n < NT) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[n][i], acc[n], 0, 0, 0);
+        }
+        // acc[n][j] = (g = 16 gt + 4 fq + j, k = 16 n + fr)
+        float *out = (which ? p.dwh : p.dwi) + (int64_t)s * p.pstride;
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            const int k = 16 * n + fr;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int g = 16 * gt + 4 * fq + j;
+                if (g < G && k < K) out[(int64_t)g * K + k] = acc[n][j];
+            }
+        }
+        return;
+    }
+    task -= p.nW;
+    if (task < p.nX) {
+        // d_x[r][k] = sum_g dpre[r][g] W_ih[g][k]: A[r][g] = dpre (16 bytes of the row per lane: MFMA i of a 16-column block
+        // takes g = 16 gb + 4 fq + i on both operands; G is a multiple of 4, so a lane's four are inside G or all outside).
+        const int rt = (int)task, NT = (p.I + 15) >> 4;
+        const int ra = min(16 * rt + fr, p.R - 1);
+        const float *ap = p.dpre + (int64_t)ra * G + 4 * fq;
+        int kc[4];
+#pragma unroll
+        for (int n = 0; n < 4; ++n) kc[n] = min(16 * n + fr, p.I - 1);
+        for (int gb = 0; gb < GT; ++gb) {
+            const int g0 = 16 * gb + 4 * fq;
+            const bool ok = g0 < G;
+            head_f4 a = {0.f, 0.f, 0.f, 0.f};
+            if (ok) a = *reinterpret_cast<const head_f4 *>(ap + 16 * gb);
+            const float *wp = p.w_ih + (int64_t)(ok ? g0 : 0) * p.I;
+            float b[4][4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int n = 0; n < 4; ++n) {
+                    float bv = 0.f;
+                    if (n < NT) bv = wp[(int64_t)i * p.I + kc[n]];      // (uniform)
+                    b[n][i] = ok ? bv : 0.f;
+                }
+#pragma unroll
+            for (int n = 0; n < 4; ++n) if (n < NT) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b[n][0], acc[n], 0, 0, 0);
+#pragma unroll
+            for (int n = 0; n < 4; ++n) if (n < NT) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b[n][1], acc[n], 0, 0, 0);
+#pragma unroll
+            for (int n = 0; n < 4; ++n) if (n < NT) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b[n][2], acc[n], 0, 0, 0);
+#pragma unroll
+            for (int n = 0; n < 4; ++n) if (n < NT) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b[n][3], acc[n], 0, 0, 0);
+        }
+        // acc[n][j] = (r = 16 rt + 4 fq + j, k = 16 n + fr)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int r = 16 * rt + 4 * fq + j;
+            if (r >= p.R) continue;
+            const int tt = r / p.B, bb = r - tt * p.B;
+            float *out = p.dx + (int64_t)tt * p.dxst + (int64_t)bb * p.dxsb;
+#pragma unroll
+            for (int n = 0; n < 4; ++n) {
+                const int k = 16 * n + fr;
+                if (k < p.I) out[k] = acc[n][j];
+            }
+        }
+        return;
+    }
+    task -= p.nX;
+    if (task < p.nB) {
+        // the column sums of one row range, rows ascending (sixteen loads in flight, added in row order)
+        const int CG = (G + 63) >> 6;
+        const int s = (int)(task / CG), c = 64 * (int)(task - (int64_t)s * CG) + lane;
+        if (c >= G) return;
+        const int r0 = s * p.chunk, rend = min(p.R, r0 + p.chunk);
+        const float *q = p.dpre + c;
+        float sum = 0.f;
+        int r = r0;
+        for (; r + 16 <= rend; r += 16) {
+            float v[16];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) v[u] = q[(int64_t)(r + u) * G];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) sum += v[u];
+        }
+        for (; r < rend; ++r) sum += q[(int64_t)r * G];
+        p.db0[(int64_t)s * p.pstride + c] = sum;
+        if (p.db1) p.db1[c] = sum;
+    }
+}
+
+// [d_w_ih | d_w_hh | d_b] = the S partials added in ascending split order; the bias sums go to both bias gradients
+__global__ __launch_bounds__(256) void lstm_bwd_reduce_kernel(const float *part, int64_t ntot, int S, int64_t nwi, int64_t nwh,
+                                                              float *dwi, float *dwh, float *db0, float *db1)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= ntot) return;
+    float s = 0.f;
+    for (int k = 0; k < S; ++k) s += part[(int64_t)k * ntot + i];
+    if (i < nwi) dwi[i] = s;
+    else if (i < nwi + nwh) dwh[i - nwi] = s;
+    else {
+        db0[i - nwi - nwh] = s;
+        db1[i - nwi - nwh] = s;
+    }
+}
+
+}  // namespace ctc
+
+extern "C" size_t ctc_amd_lstm_backward_scratch_bytes(int T, int B, int I, int H)
+{
+    if (T < 1 || B < 1 || I < 1 || H < 1 || !ctc::lstm_bwd_shape_ok(T, B, I, H)) return 0;
+    return ctc::lstm_bwd_layout(T, B, I, H).total + ctc::kHeadBwdAlign;           // (the entry aligns the pointer itself)
+}
+
+extern "C" int ctc_amd_lstm_backward(const float *d_series, int64_t ds_stride_t, int64_t ds_stride_b,
+                                     const float *gates, const float *cells,
+                                     const float *x, int64_t x_stride_t, int64_t x_stride_b,
+                                     const float *h0,
+                                     const float *series, int64_t series_stride_t, int64_t series_stride_b,
+                                     const float *w_ih, const float *w_hh,
+                                     int T, int B, int I, int H,
+                                     float *d_x, int64_t dx_stride_t, int64_t dx_stride_b,
+                                     float *dh0, float *dc0,
+                                     float *d_w_ih, float *d_w_hh, float *d_b_ih, float *d_b_hh,
+                                     void *scratch, size_t scratch_bytes, void *stream)
+{
+    if (!d_series || !gates || !cells || !x || !h0 || !series || !w_ih || !w_hh) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (!dh0 || !dc0 || !d_w_ih || !d_w_hh || !d_b_ih || !d_b_hh || !scratch) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (T < 1 || B < 1 || I < 1 || H < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (ds_stride_b < H || series_stride_b < H || x_stride_b < I) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (d_x && dx_stride_b < I) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (scratch_bytes < ctc_amd_lstm_backward_scratch_bytes(T, B, I, H)) return CTC_AMD_ERR_BAD_ARGUMENT;
+    // what ctc_amd_lstm_series refuses (the saved gates and cells can only come from it), and row counts beyond the index range
+    if (!ctc::lstm_bwd_shape_ok(T, B, I, H)) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
+    const ctc::LstmBwdLayout L = ctc::lstm_bwd_layout(T, B, I, H);
+    char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(scratch) + ctc::kHeadBwdAlign - 1) /
+                                          ctc::kHeadBwdAlign * ctc::kHeadBwdAlign);
+    float *dpre = reinterpret_cast<float *>(base + L.dpre), *wpart = reinterpret_cast<float *>(base + L.wpart);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+
+    int rc = enqueue_series_backward(d_series, ds_stride_t, ds_stride_b, gates, cells, w_hh, T, B, H, dpre, dh0, dc0, st);
+    if (rc) return rc;
+
+    const int G = 4 * H;
+    const int64_t nwi = (int64_t)G * I, nwh = (int64_t)G * H;
+    ctc::LstmBwdProdParams q;
+    q.dpre = dpre;
+    q.x = x; q.xst = x_stride_t; q.xsb = x_stride_b;
+    q.h0 = h0; q.series = series; q.sst = series_stride_t; q.ssb = series_stride_b;
+    q.w_ih = w_ih;
+    q.B = B; q.I = I; q.H = H; q.G = G;
+    q.R = T * B; q.S = L.S; q.chunk = L.chunk;
+    if (L.S > 1) {
+        q.dwi = wpart; q.dwh = wpart + nwi; q.db0 = wpart + nwi + nwh; q.db1 = nullptr; q.pstride = L.ntot;
+    } else {
+        q.dwi = d_w_ih; q.dwh = d_w_hh; q.db0 = d_b_ih; q.db1 = d_b_hh; q.pstride = 0;
+    }
+    q.dx = d_x; q.dxst = dx_stride_t; q.dxsb = dx_stride_b;
+    q.nW = (int64_t)2 * ((G + 15) / 16) * L.S;
+    q.nX = d_x ? ((int64_t)q.R + 15) / 16 : 0;
+    q.nB = (int64_t)((G + 63) / 64) * L.S;
+    const int64_t tasks = q.nW + q.nX + q.nB;
+    rc = launch<ctc::lstm_bwd_products_kernel>(dim3((unsigned)((tasks + 3) / 4)), dim3(256), 0, st, q);
+    if (rc || L.S == 1) return rc;
+    return launch<ctc::lstm_bwd_reduce_kernel>(dim3((unsigned)((L.ntot + 255) / 256)), dim3(256), 0, st,
+                                               (const float *)wpart, L.ntot, L.S, nwi, nwh, d_w_ih, d_w_hh, d_b_ih, d_b_hh);
 }

@@ -17,7 +17,11 @@ walks the recurrence from there, so ``v_all [T,B,C]`` never goes to memory; the 
 profiles/r13_lstm_forward.md -- 50 us against 70 us per forward at the reference's sizes; at T = 150 the two launches win).
 
 Same attribute names as the reference (``v``, ``v.layers``, ``v_cell``): its checkpoints load unchanged.  The backward
-pass: the recurrence is one launch (``ctc_amd_lstm_series_backward``) plus three GEMMs on its result (rocBLAS through torch);
+pass: the recurrence's is HIP whole (``ctc_amd_lstm_backward`` / ``lstm_backward``: the recurrence launch, then d_x, both weight
+gradients and the bias gradients as one products launch on the matrix cores, h_{t-1} read in place from v_series -- two launches,
+three when the sums split their rows) for T B <= ``SERIES_BACKWARD_MAX_ROWS`` rows (measured, profiles/r15_lstm_backward.md);
+beyond that gate it is the recurrence launch (``ctc_amd_lstm_series_backward``) plus torch arithmetic on its result
+(``_series_backward_torch``: three rocBLAS GEMMs and a column sum);
 the head's backward is HIP as well (``ctc_amd_head_backward`` / ``head_backward``: the BatchNorm / ReLU / Dropout row pass,
 then both products, the column sums and the sums over the frames on the matrix cores -- two launches, three when the weight
 gradient splits its rows) for T B <= ``HEAD_BACKWARD_MAX_ROWS`` rows (measured, profiles/r14_head_backward.md).  Beyond that
@@ -260,6 +264,61 @@ def lstm_series_backward(d_series, gates, cells, w_hh):
     return dpre, dh0, dc0
 
 
+def lstm_backward(d_series, gates, cells, v_all, h0, series, w_ih, w_hh, need_dx=True):
+    """The backward of ``lstm_series`` on the HIP path, whole (``ctc_amd_lstm_backward``: the recurrence launch, one products
+    launch, a reduce launch when T B > 128) -> (d_x [T,B,I] | None, dh0 [B,H], dc0 [B,H], d_w_ih [4H,I], d_w_hh [4H,H],
+    d_b_ih [4H], d_b_hh [4H]), or None when the entry does not take the shape (what ``lstm_series`` refuses, or T B > 2^22
+    rows).  ``gates`` / ``cells``: as ``lstm_series`` saved them; ``v_all`` [T,B,I]: the cell inputs; ``series`` [T,B,>=H]: the
+    forward's v_series, whose rows are read in place as h_{t-1} (``h0`` for t = 0).  ``d_b_ih`` and ``d_b_hh`` are two tensors
+    with the same values.  ``d_series`` / ``v_all`` / ``series`` are passed as they lie when their rows have unit stride and a
+    pitch of at least their width; anything else (an expanded gradient with pitch 0) is copied first.  Deterministic (no atomics, fixed sum orders).  The scratch (dpre [T B, 4H], the partial sums) is one
+    ``torch.empty`` per call, for ``head_backward``'s reasons."""
+    F._require_hip(d_series, "d_series")
+    F._require_hip(v_all, "v_all")
+    T, B, I = v_all.shape
+    H = h0.shape[1]
+    dev = v_all.device
+    f32 = torch.float32
+    # rows the entry can address: unit stride over the columns and a row pitch of at least the width (autograd hands a
+    # broadcast upstream gradient over with pitch 0, e.g. behind series.sum(1): that one is copied)
+    rows = lambda t: t if (t.dtype is f32 and t.stride(2) == 1 and t.stride(1) >= t.shape[2]) else t.float().contiguous()   # noqa: E731
+    cont = lambda t: t if (t.dtype is f32 and t.is_contiguous()) else t.float().contiguous()          # noqa: E731
+    ds, x, sr = rows(d_series), rows(v_all), rows(series)
+    g, c, h, wi, wh = (cont(t) for t in (gates, cells, h0, w_ih, w_hh))
+    lib = _lib.load()
+    nbytes = lib.ctc_amd_lstm_backward_scratch_bytes(T, B, I, H)
+    if nbytes == 0 and min(T, B, I, H) >= 1:
+        return None
+    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    d_x = torch.empty((T, B, I), dtype=f32, device=dev) if need_dx else None
+    dh0, dc0 = (torch.empty((B, H), dtype=f32, device=dev) for _ in range(2))
+    d_w_ih = torch.empty((4 * H, I), dtype=f32, device=dev)
+    d_w_hh = torch.empty((4 * H, H), dtype=f32, device=dev)
+    d_b_ih, d_b_hh = (torch.empty(4 * H, dtype=f32, device=dev) for _ in range(2))
+    with F._on_device(dev):
+        rc = lib.ctc_amd_lstm_backward(ds.data_ptr(), ds.stride(0), ds.stride(1), g.data_ptr(), c.data_ptr(),
+                                       x.data_ptr(), x.stride(0), x.stride(1), h.data_ptr(),
+                                       sr.data_ptr(), sr.stride(0), sr.stride(1), wi.data_ptr(), wh.data_ptr(), T, B, I, H,
+                                       d_x.data_ptr() if need_dx else None, B * I if need_dx else 0, I if need_dx else 0,
+                                       dh0.data_ptr(), dc0.data_ptr(), d_w_ih.data_ptr(), d_w_hh.data_ptr(),
+                                       d_b_ih.data_ptr(), d_b_hh.data_ptr(), scratch.data_ptr(), nbytes, F._stream_handle(dev))
+    if rc == _lib.ERR_UNSUPPORTED_SHAPE:
+        return None
+    if rc:
+        _lib.check(rc, "ctc_amd_lstm_backward")
+    return d_x, dh0, dc0, d_w_ih, d_w_hh, d_b_ih, d_b_hh
+
+
+def _series_backward_torch(d_series, v_all, w_ih, w_hh, hs, cs, gs, H):
+    """the backward of the one-launch recurrence with torch arithmetic behind the recurrence launch (three rocBLAS GEMMs over
+    all frames at once, a column sum, a clone): what runs outside the gate.  hs [T+1,B,H]: h0 and the hidden states."""
+    dpre, dh0, dc0 = lstm_series_backward(d_series, gs, cs, w_hh)
+    flat = dpre.reshape(-1, 4 * H)
+    db = flat.sum(0)
+    return (dpre @ w_ih.float(), dh0, dc0, flat.t() @ v_all.reshape(-1, v_all.shape[2]).float(),
+            flat.t() @ hs[:-1].reshape(-1, H), db, db.clone(), None, None)
+
+
 def lstm_forward(feat, weight, bias, bn_weight, bn_bias, running_mean, running_var, eps, h0, c0, w_ih, w_hh, b_ih, b_hh,
                  cols=None, pad_value=PAD_LOGIT):
     """EVAL mode, no gradient: ``head_forward`` (running statistics, no mask) and ``lstm_series`` as ONE launch
@@ -303,10 +362,22 @@ FUSED_FORWARD_MAX_WG_ROWS = 64
 # C = 158 (1.02 - 1.09 x).  The bound is the largest measured point that wins at every B and C measured (r13's rule).
 HEAD_BACKWARD_MAX_ROWS = 10240
 
+# _SeriesFn.backward takes the HIP path whole (lstm_backward) up to this many rows T B; 0 closes the gate.  T B for
+# HEAD_BACKWARD_MAX_ROWS's reason: the products and the column sums are T B rows of work, the torch arithmetic behind the
+# recurrence launch is launch-bound at small T B and three rocBLAS GEMMs beyond.  Measured, not guessed
+# (profiles/r15_lstm_backward.md, both bodies captured into graphs, (I, H) in {(33, 33), (38, 38)}, with and without d_x): at
+# every measured T B = 100 ... 38400 the new call's median is 0.49 ... 0.97 of the closed gate's and below the minimum of its
+# rounds at every B in {10, 64, 256} -- behind the recurrence launch both start with, 17 us against 39 us at T B = 100 and
+# 130 us against 249 us at T B = 38400.  The bound is the largest measured point that wins at every B and (I, H) measured
+# (r13's rule); no measured point loses, so it is the largest measured point.
+SERIES_BACKWARD_MAX_ROWS = 38400
+
 
 class _SeriesFn(torch.autograd.Function):
     """v_all [T,B,I], (h0, c0), LSTMCell parameters -> v_series [T,B,cols]: one launch for the reference's class counts, T
-    fused launches otherwise; backward = BPTT in torch."""
+    fused launches otherwise.  Backward of the one launch: ``lstm_backward`` (HIP, whole) for T B <=
+    ``SERIES_BACKWARD_MAX_ROWS`` rows; beyond the gate, and when the entry does not take the shape, the recurrence launch and
+    ``_series_backward_torch``.  Backward of the T launches: BPTT in torch."""
 
     @staticmethod
     def forward(ctx, v_all, h0, c0, w_ih, w_hh, b_ih, b_hh, cols, pad_value):
@@ -318,10 +389,14 @@ class _SeriesFn(torch.autograd.Function):
         if whole is not None:
             series, gates, cells = whole
             ctx.one_launch = need
-            if need:
+            ctx.in_place = need and T * B <= SERIES_BACKWARD_MAX_ROWS
+            if ctx.in_place:                                 # h_{t-1} is read from v_series itself: no concatenated copy
+                ctx.save_for_backward(v_all, w_ih, w_hh, h0.detach(), cells, gates, series)
+            elif need:
                 hs = torch.cat([h0.detach().float().unsqueeze(0), series[:, :, :H]])
                 ctx.save_for_backward(v_all, w_ih, w_hh, hs, cells, gates)
             return series
+        ctx.in_place = False
         ctx.one_launch = False
         series = torch.empty((T, B, cols), dtype=torch.float32, device=v_all.device)
         hs, cs, gs = [h0], [c0], []
@@ -337,14 +412,20 @@ class _SeriesFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_series):
+        H = ctx.H
+        if ctx.in_place:                                     # the gate was open in forward: (h0, series) saved, not their concatenation
+            v_all, w_ih, w_hh, h0, cs, gs, series = ctx.saved_tensors
+            res = None
+            if v_all.shape[0] * v_all.shape[1] <= SERIES_BACKWARD_MAX_ROWS:
+                res = lstm_backward(d_series, gs, cs, v_all, h0, series, w_ih, w_hh, ctx.needs_input_grad[0])
+            if res is not None:
+                return tuple(res) + (None, None)
+            hs = torch.cat([h0.float().unsqueeze(0), series[:, :, :H]])
+            return _series_backward_torch(d_series, v_all, w_ih, w_hh, hs, cs, gs, H)
         v_all, w_ih, w_hh, hs, cs, gs = ctx.saved_tensors
-        T, H = v_all.shape[0], ctx.H
+        T = v_all.shape[0]
         if ctx.one_launch:                                   # the recurrence in one launch, the rest as GEMMs over all frames
-            dpre, dh0, dc0 = lstm_series_backward(d_series, gs, cs, w_hh)
-            flat = dpre.reshape(-1, 4 * H)
-            db = flat.sum(0)
-            return (dpre @ w_ih.float(), dh0, dc0, flat.t() @ v_all.reshape(-1, v_all.shape[2]).float(),
-                    flat.t() @ hs[:-1].reshape(-1, H), db, db.clone(), None, None)
+            return _series_backward_torch(d_series, v_all, w_ih, w_hh, hs, cs, gs, H)
         dh = torch.zeros_like(hs[0])
         dc = torch.zeros_like(cs[0])
         dv = torch.empty_like(v_all)

@@ -429,7 +429,8 @@ int ctc_amd_lstm_series(const float *x, const float *h0, const float *c0,
  * (row (t, b) at d_series + t * ds_stride_t + b * ds_stride_b, unit stride over the classes, columns [0,H) read) and the
  * gates_out / cells_out of the forward launch to dpre_out [T,B,4H] -- the gradient of every frame's gate pre-activations --
  * and the gradients of the initial state dh0_out, dc0_out [B,H].  What is left of the backward pass has no recurrence in
- * it: dx = dpre W_ih, dW_ih = sum_tb dpre^T x, dW_hh = sum_tb dpre^T h_{t-1}, db = sum_tb dpre (plain GEMMs). */
+ * it: dx = dpre W_ih, dW_ih = sum_tb dpre^T x, dW_hh = sum_tb dpre^T h_{t-1}, db = sum_tb dpre -- ctc_amd_lstm_backward
+ * (below) runs this launch and those products behind it. */
 int ctc_amd_lstm_series_backward(const float *d_series, int64_t ds_stride_t, int64_t ds_stride_b,
                                  const float *gates, const float *cells, const float *w_hh,
                                  int T, int B, int H, float *dpre_out, float *dh0_out, float *dc0_out, void *stream);
@@ -506,6 +507,43 @@ int ctc_amd_head_backward(const float *d_out, int64_t dout_stride_t, int64_t dou
                           int T, int B, int K, int C,
                           float *d_feat, int64_t dfeat_stride_t, int64_t dfeat_stride_b,
                           float *d_weight, float *d_bias, float *d_bn_weight, float *d_bn_bias,
+                          void *scratch, size_t scratch_bytes, void *stream);
+
+/* The BACKWARD of ctc_amd_lstm_series, whole: from d_series, the upstream gradient of v_series (as ctc_amd_lstm_series_backward
+ * takes it), and what the forward call took and saved to the gradients of the cell inputs, the initial state and nn.LSTMCell's
+ * four parameters.  All fp32.
+ *   gates [T,B,4H], cells [T+1,B,H]: gates_out / cells_out of the forward call;  x: the cell inputs, row (t, b) of I floats at
+ *   x + t * x_stride_t + b * x_stride_b;  h0 [B,H];  series: the forward's v_series, row (t, b) at series + t * series_stride_t
+ *   + b * series_stride_b -- columns [0,H) of row (t - 1, b) are h_{t-1}, read in place (h_{-1} = h0: no concatenated copy);
+ *   w_ih [4H,I], w_hh [4H,H].  With dpre [T,B,4H] the pre-activation gradients of ctc_amd_lstm_series_backward:
+ *     d_x[t,b,:] = dpre[t,b,:] W_ih (rows of I floats at (dx_stride_t, dx_stride_b); NULL: not wanted),
+ *     d_w_ih [4H,I] = sum_tb dpre[t,b,:]^T x[t,b,:],   d_w_hh [4H,H] = sum_tb dpre[t,b,:]^T h_{t-1}[b,:],
+ *     d_b_ih = d_b_hh [4H] = sum_tb dpre[t,b,:] (two arrays, the same values),   dh0, dc0 [B,H] as that call writes them.
+ * Launches, all on `stream`: lstm_series_bwd_kernel (the launch of ctc_amd_lstm_series_backward, the same bits: dpre goes to the
+ * scratch, dh0 and dc0 to the caller); one products launch -- d^T x against x and against h_{t-1}, d W, the column sums -- exact
+ * fp32 on the matrix cores (v_mfma_f32_16x16x4_f32, one fmaf chain per output element); and, when the row range splits, one
+ * reduce launch.  Row-range splits (the head's rule): with R = T B, the weight and bias gradients sum their rows in ranges of
+ * chunk = 16 ceil(ceil(R / min(64, ceil(R / 128))) / 16) rows, S = ceil(R / chunk) of them (R <= 128: one; 140: two of 80;
+ * 9600: 60 of 160), rows ascending inside a range, the ranges added ascending -- a function of T B alone, no atomics: the same
+ * inputs give the same bits.  No allocation, no host synchronisation:
+ * safe under stream capture.  Every element of every output that is not NULL is written; d_x rows only in columns [0,I).
+ * scratch: at least ctc_amd_lstm_backward_scratch_bytes(T, B, I, H) bytes of device memory, any alignment, contents irrelevant
+ * (nothing is read from it that the same call has not written).
+ * CTC_AMD_ERR_BAD_ARGUMENT (decided first, before any HIP call): a NULL among the required pointers (all but d_x), a size < 1,
+ * ds_stride_b < H, series_stride_b < H, x_stride_b < I, dx_stride_b < I (with d_x), scratch_bytes below the query.
+ * CTC_AMD_ERR_UNSUPPORTED_SHAPE: what ctc_amd_lstm_series refuses (I + H > 80, I > 64, H > 64) and T B > 2^22 rows.
+ * The query answers 0 for sizes < 1 and for shapes the entry does not take. */
+size_t ctc_amd_lstm_backward_scratch_bytes(int T, int B, int I, int H);
+int ctc_amd_lstm_backward(const float *d_series, int64_t ds_stride_t, int64_t ds_stride_b,
+                          const float *gates, const float *cells,
+                          const float *x, int64_t x_stride_t, int64_t x_stride_b,
+                          const float *h0,
+                          const float *series, int64_t series_stride_t, int64_t series_stride_b,
+                          const float *w_ih, const float *w_hh,
+                          int T, int B, int I, int H,
+                          float *d_x, int64_t dx_stride_t, int64_t dx_stride_b,
+                          float *dh0, float *dc0,
+                          float *d_w_ih, float *d_w_hh, float *d_b_ih, float *d_b_hh,
                           void *scratch, size_t scratch_bytes, void *stream);
 
 #ifdef __cplusplus
