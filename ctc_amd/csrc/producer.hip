@@ -342,7 +342,8 @@ __global__ __launch_bounds__(kLstmThreads) void lstm_series_bwd_kernel(LstmSerie
 using namespace ctc;
 
 // The T steps of ctc_amd_lstm_cell_step as one launch, for the reference's class counts (I + H <= 80, H <= 64, I <= 64).
-// Other sizes: CTC_AMD_ERR_UNSUPPORTED_SHAPE (the caller steps frame by frame).
+// Other sizes: CTC_AMD_ERR_UNSUPPORTED_SHAPE (ctc_amd_lstm_series_wide takes up to 160 classes, lstm_wide.hpp; beyond, the caller steps
+// frame by frame).
 extern "C" int ctc_amd_lstm_series(const float *x, const float *h0, const float *c0,
                                    const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,
                                    int T, int B, int I, int H,
@@ -1324,3 +1325,5 @@ extern "C" int ctc_amd_lstm_backward(const float *d_series, int64_t ds_stride_t,
     return launch<ctc::lstm_bwd_reduce_kernel>(dim3((unsigned)((L.ntot + 255) / 256)), dim3(256), 0, st,
                                                (const float *)wpart, L.ntot, L.S, nwi, nwh, d_w_ih, d_w_hh, d_b_ih, d_b_hh);
 }
+
+#include "lstm_wide.hpp"

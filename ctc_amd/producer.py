@@ -5,7 +5,11 @@ ReLU + Dropout) and one ``nn.LSTMCell`` step whose hidden state is stored as ``v
 tensor the CTC losses read.  Here the head of ALL frames is one HIP launch (``ctc_amd_head_forward``: the 1024 -> C
 product on the matrix cores, BatchNorm with the statistics of each frame's batch in train mode / the running statistics
 in eval mode, ReLU, and the dropout mask torch drew), and the LSTMCell steps and stores are one more
-(``ctc_amd_lstm_series``; one launch per frame, ``ctc_amd_lstm_cell_step``, at other sizes): gate products, cell update, and the hidden state
+(``ctc_amd_lstm_series`` at the reference's class counts, I + H <= 80; ``ctc_amd_lstm_series_wide`` / ``lstm_series_wide`` up to
+160 classes, the benchmark's 158 among them: the weights no longer fit a workgroup's registers and are streamed from L2, from a
+transposed copy, the x part of every row computed ahead of the recurrence -- bit for bit the frame-by-frame result, taken for
+T B <= ``SERIES_WIDE_MAX_ROWS`` rows (measured, profiles/r16_lstm_wide.md: forward + backward 5.4 ms against 57.2 ms at T = 150,
+B = 256, C = 158); one launch per frame, ``ctc_amd_lstm_cell_step``, beyond that gate and beyond 160): gate products, cell update, and the hidden state
 written straight into the logits tensor, optionally with one pad column (``pad_classes=True``: an odd class count such
 as the reference's 33 gets rows of C + 1 floats, the extra logit -1e30 -- softmax gives it exactly 0, so no loss or
 gradient value changes, and the rows become the even, 8-byte aligned rows of the fastest loss kernel).
@@ -21,7 +25,11 @@ pass: the recurrence's is HIP whole (``ctc_amd_lstm_backward`` / ``lstm_backward
 gradients and the bias gradients as one products launch on the matrix cores, h_{t-1} read in place from v_series -- two launches,
 three when the sums split their rows) for T B <= ``SERIES_BACKWARD_MAX_ROWS`` rows (measured, profiles/r15_lstm_backward.md);
 beyond that gate it is the recurrence launch (``ctc_amd_lstm_series_backward``) plus torch arithmetic on its result
-(``_series_backward_torch``: three rocBLAS GEMMs and a column sum);
+(``_series_backward_torch``: three rocBLAS GEMMs and a column sum); behind the wide forward it is the wide recurrence launch
+(``ctc_amd_lstm_series_backward_wide`` / ``lstm_series_backward_wide``), the bias gradients as a HIP launch of their own
+(``ctc_amd_lstm_bias_grad_wide`` / ``lstm_bias_grad_wide``: torch's column sum replayed wrong from a captured graph behind this
+launch at T B = 1500, profiles/r16_lstm_wide.md) and the three GEMMs of the same torch arithmetic, and behind the
+frame-by-frame forward a BPTT loop of torch kernels;
 the head's backward is HIP as well (``ctc_amd_head_backward`` / ``head_backward``: the BatchNorm / ReLU / Dropout row pass,
 then both products, the column sums and the sums over the frames on the matrix cores -- two launches, three when the weight
 gradient splits its rows) for T B <= ``HEAD_BACKWARD_MAX_ROWS`` rows (measured, profiles/r14_head_backward.md).  Beyond that
@@ -264,6 +272,81 @@ def lstm_series_backward(d_series, gates, cells, w_hh):
     return dpre, dh0, dc0
 
 
+def lstm_series_wide(v_all, h0, c0, w_ih, w_hh, b_ih, b_hh, cols=None, pad_value=PAD_LOGIT, want_backward_state=False):
+    """``lstm_series`` for every 1 <= I, H <= 160 (``ctc_amd_lstm_series_wide``: the benchmark's C = 158, and the narrow shapes
+    too) -> (v_series [T,B,cols], gates [T,B,4H] | None, cells [T+1,B,H] | None), bit for bit what T calls of
+    ``lstm_cell_step`` give, or None when the entry does not take the shape (I or H > 160, T B > 2^22 rows).  The scratch (the
+    transposed weights, the x part of every row's pre-activations [T B, 4H]) is one ``torch.empty`` per call, for
+    ``head_backward``'s reasons."""
+    F._require_hip(v_all, "v_all")
+    T, B, I = v_all.shape
+    H = h0.shape[1]
+    cols = H if cols is None else int(cols)
+    dev = v_all.device
+    args = [t if (t.dtype is torch.float32 and t.is_contiguous()) else t.float().contiguous()
+            for t in (v_all, h0, c0, w_ih, w_hh, b_ih, b_hh)]
+    lib = _lib.load()
+    nbytes = lib.ctc_amd_lstm_series_wide_scratch_bytes(T, B, I, H)
+    if nbytes == 0 and min(T, B, I, H) >= 1:
+        return None
+    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    series = torch.empty((T, B, cols), dtype=torch.float32, device=dev)
+    gates = torch.empty((T, B, 4 * H), dtype=torch.float32, device=dev) if want_backward_state else None
+    cells = torch.empty((T + 1, B, H), dtype=torch.float32, device=dev) if want_backward_state else None
+    with F._on_device(dev):
+        rc = lib.ctc_amd_lstm_series_wide(*(t.data_ptr() for t in args), T, B, I, H, series.data_ptr(), series.stride(0),
+                                          series.stride(1), cols, float(pad_value),
+                                          gates.data_ptr() if want_backward_state else None,
+                                          cells.data_ptr() if want_backward_state else None, None, None,
+                                          scratch.data_ptr(), nbytes, F._stream_handle(dev))
+    if rc == _lib.ERR_UNSUPPORTED_SHAPE:
+        return None
+    if rc:
+        _lib.check(rc, "ctc_amd_lstm_series_wide")
+    return series, gates, cells
+
+
+def lstm_series_backward_wide(d_series, gates, cells, w_hh):
+    """``lstm_series_backward`` for every 1 <= H <= 160 (``ctc_amd_lstm_series_backward_wide``, one launch, deterministic) ->
+    (dpre [T,B,4H], dh0 [B,H], dc0 [B,H]), or None when the entry does not take the shape (H > 160)."""
+    F._require_hip(d_series, "d_series")
+    T, B, G = gates.shape
+    H = G // 4
+    dev = gates.device
+    f32 = torch.float32
+    ds = d_series if (d_series.dtype is f32 and d_series.stride(2) == 1) else d_series.float().contiguous()
+    g, c, w = (t if (t.dtype is f32 and t.is_contiguous()) else t.float().contiguous() for t in (gates, cells, w_hh))
+    dpre = torch.empty((T, B, G), dtype=f32, device=dev)
+    dh0 = torch.empty((B, H), dtype=f32, device=dev)
+    dc0 = torch.empty((B, H), dtype=f32, device=dev)
+    with F._on_device(dev):
+        rc = _lib.load().ctc_amd_lstm_series_backward_wide(ds.data_ptr(), ds.stride(0), ds.stride(1), g.data_ptr(), c.data_ptr(),
+                                                           w.data_ptr(), T, B, H, dpre.data_ptr(), dh0.data_ptr(), dc0.data_ptr(),
+                                                           F._stream_handle(dev))
+    if rc == _lib.ERR_UNSUPPORTED_SHAPE:
+        return None
+    if rc:
+        _lib.check(rc, "ctc_amd_lstm_series_backward_wide")
+    return dpre, dh0, dc0
+
+
+def lstm_bias_grad_wide(dpre):
+    """The bias gradients behind ``lstm_series_backward_wide``: the column sums of ``dpre`` [T,B,4H] as one deterministic HIP launch
+    (``ctc_amd_lstm_bias_grad_wide``: a fixed sum order, no scratch and nothing to clear) -> (d_b_ih [4H], d_b_hh [4H]), two
+    tensors with the same values."""
+    F._require_hip(dpre, "dpre")
+    G = dpre.shape[-1]
+    d = dpre if (dpre.dtype is torch.float32 and dpre.is_contiguous()) else dpre.float().contiguous()
+    rows = d.numel() // G
+    d_b_ih, d_b_hh = (torch.empty(G, dtype=torch.float32, device=d.device) for _ in range(2))
+    with F._on_device(d.device):
+        rc = _lib.load().ctc_amd_lstm_bias_grad_wide(d.data_ptr(), rows, G // 4, d_b_ih.data_ptr(), d_b_hh.data_ptr(),
+                                                     F._stream_handle(d.device))
+    if rc:
+        _lib.check(rc, "ctc_amd_lstm_bias_grad_wide")
+    return d_b_ih, d_b_hh
+
+
 def lstm_backward(d_series, gates, cells, v_all, h0, series, w_ih, w_hh, need_dx=True):
     """The backward of ``lstm_series`` on the HIP path, whole (``ctc_amd_lstm_backward``: the recurrence launch, one products
     launch, a reduce launch when T B > 128) -> (d_x [T,B,I] | None, dh0 [B,H], dc0 [B,H], d_w_ih [4H,I], d_w_hh [4H,H],
@@ -309,14 +392,20 @@ def lstm_backward(d_series, gates, cells, v_all, h0, series, w_ih, w_hh, need_dx
     return d_x, dh0, dc0, d_w_ih, d_w_hh, d_b_ih, d_b_hh
 
 
-def _series_backward_torch(d_series, v_all, w_ih, w_hh, hs, cs, gs, H):
+def _series_backward_torch(d_series, v_all, w_ih, w_hh, hs, cs, gs, H, recurrence=lstm_series_backward, bias_grad=None):
     """the backward of the one-launch recurrence with torch arithmetic behind the recurrence launch (three rocBLAS GEMMs over
-    all frames at once, a column sum, a clone): what runs outside the gate.  hs [T+1,B,H]: h0 and the hidden states."""
-    dpre, dh0, dc0 = lstm_series_backward(d_series, gs, cs, w_hh)
+    all frames at once, a column sum, a clone): what runs outside the gate, and behind the wide recurrence
+    (``recurrence=lstm_series_backward_wide``, where the column sum is a HIP launch too: ``bias_grad=lstm_bias_grad_wide``).
+    hs [T+1,B,H]: h0 and the hidden states."""
+    dpre, dh0, dc0 = recurrence(d_series, gs, cs, w_hh)
     flat = dpre.reshape(-1, 4 * H)
-    db = flat.sum(0)
+    if bias_grad is None:
+        db = flat.sum(0)
+        db_ih, db_hh = db, db.clone()
+    else:
+        db_ih, db_hh = bias_grad(dpre)
     return (dpre @ w_ih.float(), dh0, dc0, flat.t() @ v_all.reshape(-1, v_all.shape[2]).float(),
-            flat.t() @ hs[:-1].reshape(-1, H), db, db.clone(), None, None)
+            flat.t() @ hs[:-1].reshape(-1, H), db_ih, db_hh, None, None)
 
 
 def lstm_forward(feat, weight, bias, bn_weight, bn_bias, running_mean, running_var, eps, h0, c0, w_ih, w_hh, b_ih, b_hh,
@@ -372,12 +461,28 @@ HEAD_BACKWARD_MAX_ROWS = 10240
 # (r13's rule); no measured point loses, so it is the largest measured point.
 SERIES_BACKWARD_MAX_ROWS = 38400
 
+# _SeriesFn takes the wide recurrence (lstm_series_wide forward; lstm_series_backward_wide, lstm_bias_grad_wide and
+# _series_backward_torch's three GEMMs backward)
+# for the shapes lstm_series refuses, I and H up to 160, up to this many rows T B; 0 closes the gate, and the T step launches
+# and the BPTT loop of torch kernels run as before.  T B for the neighbours' reason: the x part, the saved state and the torch
+# arithmetic behind the backward launch are T B rows of work, and the comparator is launch-bound (T step launches, then about
+# two dozen torch kernels per frame).  Measured, not guessed (profiles/r16_lstm_wide.md, forward + backward captured into one
+# graph, I = H in {158, 96}): at every measured T B = 100 ... 38400 the open path's median is 0.09 ... 0.27 of the closed
+# gate's and below the minimum of its rounds at every B in {10, 64, 256} -- 5.40 ms against 57.2 ms at T = 150, B = 256,
+# C = 158, 0.43 ms against 1.63 ms at T = 10, B = 10; forward alone 0.23 ... 0.46, backward alone 0.07 ... 0.23; every graph
+# replay gives the eager bits.  The bound
+# is the largest measured point that wins at every B and H measured (r13's rule); no measured point loses, so it is the
+# largest measured point.
+SERIES_WIDE_MAX_ROWS = 38400
+SERIES_WIDE_MAX_CLASSES = 160                        # kWideMax of csrc/lstm_wide.hpp: the bound of the wide entries on I and H
+
 
 class _SeriesFn(torch.autograd.Function):
-    """v_all [T,B,I], (h0, c0), LSTMCell parameters -> v_series [T,B,cols]: one launch for the reference's class counts, T
-    fused launches otherwise.  Backward of the one launch: ``lstm_backward`` (HIP, whole) for T B <=
+    """v_all [T,B,I], (h0, c0), LSTMCell parameters -> v_series [T,B,cols]: one launch for the reference's class counts, the
+    wide recurrence (``ctx.wide``) up to 160 classes and T B <= ``SERIES_WIDE_MAX_ROWS`` rows, T fused launches otherwise.  Backward of the one launch: ``lstm_backward`` (HIP, whole) for T B <=
     ``SERIES_BACKWARD_MAX_ROWS`` rows; beyond the gate, and when the entry does not take the shape, the recurrence launch and
-    ``_series_backward_torch``.  Backward of the T launches: BPTT in torch."""
+    ``_series_backward_torch``.  Backward of the wide recurrence: its own recurrence launch and ``_series_backward_torch``.
+    Backward of the T launches: BPTT in torch."""
 
     @staticmethod
     def forward(ctx, v_all, h0, c0, w_ih, w_hh, b_ih, b_hh, cols, pad_value):
@@ -385,6 +490,7 @@ class _SeriesFn(torch.autograd.Function):
         H = h0.shape[1]
         need = any(ctx.needs_input_grad[:7])
         ctx.H = H
+        ctx.wide = False
         whole = lstm_series(v_all, h0, c0, w_ih, w_hh, b_ih, b_hh, cols, pad_value, want_backward_state=need)
         if whole is not None:
             series, gates, cells = whole
@@ -398,6 +504,15 @@ class _SeriesFn(torch.autograd.Function):
             return series
         ctx.in_place = False
         ctx.one_launch = False
+        if 0 < T * B <= SERIES_WIDE_MAX_ROWS and max(v_all.shape[2], H) <= SERIES_WIDE_MAX_CLASSES:   # beyond the narrow entry's sizes
+            whole = lstm_series_wide(v_all, h0, c0, w_ih, w_hh, b_ih, b_hh, cols, pad_value, want_backward_state=need)
+            if whole is not None:
+                series, gates, cells = whole
+                ctx.wide = need
+                if need:
+                    hs = torch.cat([h0.detach().float().unsqueeze(0), series[:, :, :H]])
+                    ctx.save_for_backward(v_all, w_ih, w_hh, hs, cells, gates)
+                return series
         series = torch.empty((T, B, cols), dtype=torch.float32, device=v_all.device)
         hs, cs, gs = [h0], [c0], []
         h, c = h0, c0
@@ -426,6 +541,9 @@ class _SeriesFn(torch.autograd.Function):
         T = v_all.shape[0]
         if ctx.one_launch:                                   # the recurrence in one launch, the rest as GEMMs over all frames
             return _series_backward_torch(d_series, v_all, w_ih, w_hh, hs, cs, gs, H)
+        if getattr(ctx, "wide", False):                     # the same behind the wide recurrence launch
+            return _series_backward_torch(d_series, v_all, w_ih, w_hh, hs, cs, gs, H, lstm_series_backward_wide,
+                                          lstm_bias_grad_wide)
         dh = torch.zeros_like(hs[0])
         dc = torch.zeros_like(cs[0])
         dv = torch.empty_like(v_all)

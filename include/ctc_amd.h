@@ -546,6 +546,45 @@ int ctc_amd_lstm_backward(const float *d_series, int64_t ds_stride_t, int64_t ds
                           float *d_w_ih, float *d_w_hh, float *d_b_ih, float *d_b_hh,
                           void *scratch, size_t scratch_bytes, void *stream);
 
+/* ctc_amd_lstm_series beyond the reference's class counts: every 1 <= I <= 160 and 1 <= H <= 160 (the benchmark's C = 158;
+ * the narrow shapes too).  Arguments and outputs are those of ctc_amd_lstm_series -- series at any pitch, pad columns
+ * [H, series_cols) filled with pad_value, gates_out [T,B,4H], cells_out [T+1,B,H] (cells[0] = c0), h_out, c_out, each of the
+ * last four or NULL -- and the arithmetic is, bit for bit, that of T calls of ctc_amd_lstm_cell_step: per (sample, gate row)
+ * one fp32 fmaf chain from 0 over k ascending through the W_ih part, then through the W_hh part, then + (b_ih[r] + b_hh[r]).
+ * The weights (800 KB at 158) fit neither the LDS nor a workgroup's registers: they stay in L2 and are streamed every frame,
+ * from a transposed copy [I + H][4H] so that the reads are coalesced.  Launches, all on `stream`: the transposed copy into the
+ * scratch; the x part of every (t, b) row's pre-activations into the scratch (no recurrence in it: all T B rows at once, the
+ * chain from 0 through the W_ih part); the recurrence, one workgroup per four samples for all T frames, which starts every
+ * W_hh chain from the stored x part (an fp32 store and load is exact).  No allocation, no host synchronisation: safe under
+ * stream capture.
+ * scratch: at least ctc_amd_lstm_series_wide_scratch_bytes(T, B, I, H) bytes of device memory, any alignment, contents
+ * irrelevant.  The query answers 0 for sizes < 1 and for shapes the entry does not take.
+ * CTC_AMD_ERR_BAD_ARGUMENT (decided first, before any HIP call): a NULL among x, h0, c0, the four parameters, series and
+ * scratch; a size < 1; series_cols < H; series_stride_b < series_cols; scratch_bytes below the query.
+ * CTC_AMD_ERR_UNSUPPORTED_SHAPE: I > 160, H > 160, or T B > 2^22 rows. */
+size_t ctc_amd_lstm_series_wide_scratch_bytes(int T, int B, int I, int H);
+int ctc_amd_lstm_series_wide(const float *x, const float *h0, const float *c0,
+                             const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,
+                             int T, int B, int I, int H,
+                             float *series, int64_t series_stride_t, int64_t series_stride_b, int series_cols, float pad_value,
+                             float *gates_out, float *cells_out, float *h_out, float *c_out,
+                             void *scratch, size_t scratch_bytes, void *stream);
+
+/* ctc_amd_lstm_series_backward for every 1 <= H <= 160 (H > 160: CTC_AMD_ERR_UNSUPPORTED_SHAPE): the same arguments, the same
+ * formulas, one launch, no scratch.  W_hh is streamed from L2 as it lies (row-major, lanes over the columns); the sum over the
+ * 4H gate rows runs as four chains of H rows, one per gate chunk, added in ascending chunk order -- no atomics, a fixed order:
+ * two calls give the same bits.  No bitwise tie to ctc_amd_lstm_series_backward, whose sum is one chain. */
+int ctc_amd_lstm_series_backward_wide(const float *d_series, int64_t ds_stride_t, int64_t ds_stride_b,
+                                      const float *gates, const float *cells, const float *w_hh,
+                                      int T, int B, int H, float *dpre_out, float *dh0_out, float *dc0_out, void *stream);
+
+/* The bias gradients behind ctc_amd_lstm_series_backward_wide: d_b_ih[c] = d_b_hh[c] = sum_r dpre[r][c] over the `rows` = T B rows
+ * of dpre [rows][4H] (two arrays, the same values), H <= 160.  One launch: lanes over the columns, sixteen waves over the rows,
+ * the partial sums added in a fixed order -- no atomics, no scratch, nothing that has to be cleared first; two calls give the
+ * same bits.  No allocation, no host synchronisation: safe under stream capture.  CTC_AMD_ERR_BAD_ARGUMENT: a NULL pointer,
+ * rows < 1, H < 1;  CTC_AMD_ERR_UNSUPPORTED_SHAPE: H > 160. */
+int ctc_amd_lstm_bias_grad_wide(const float *dpre, int64_t rows, int H, float *d_b_ih, float *d_b_hh, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
