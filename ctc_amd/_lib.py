@@ -72,6 +72,10 @@ PROTOTYPES = {
                                         _vp, _vp, _vp, _vp]),
     "ctc_amd_blank_posteriors_wide": (_int, [_vp, _i64, _i64, _vp, _int, _vp, _vp, _int, _int, _int, _int, _int,
                                              _vp, _vp, _vp, _vp]),
+    "ctc_amd_noblank_token_spans": (_int, [_vp, _i64, _i64, _vp, _int, _vp, _vp, _int, _int, _int, _int,
+                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ctc_amd_binary_token_spans": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _int, _int, _int, _int,
+                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ctc_amd_blank_token_spans": (_int, [_vp, _i64, _i64, _vp, _int, _vp, _vp, _int, _int, _int, _int, _int,
                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }

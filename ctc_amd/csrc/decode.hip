@@ -10,6 +10,7 @@
 // One 256-thread workgroup per sample: every wave normalises rows (log-softmax statistics,
 // emission gather) into LDS; wave 0 runs the max-scan, one state per lane and K states
 // per lane for S > 64, recording one back-pointer byte per cell; lane 0 walks them back.
+// decode_spans.hpp (token spans) runs the same emission stage and the same max-scan beside the alpha / beta' chains.
 #include "lattice.hpp"
 #include "launch.hpp"
 
@@ -31,7 +32,8 @@ constexpr int kDecWaves = kDecThreads / kWave;
 
 // the max-scan over em[T_b][SP] by ONE wave (one back-pointer byte per cell), the read-out and the walk back
 template <int K>
-__device__ __forceinline__ void viterbi_wave(const float *em, unsigned char *bp, const DecodeParams &p, int b, int Tb, int L, bool ok)
+__device__ __forceinline__ void viterbi_wave(const float *em, unsigned char *bp, const DecodeParams &p, int b, int Tb, int L, bool ok,
+                                             int *lpath = nullptr)          // lpath (LDS, [T]): the path once more, for the workgroup
 {
     const int lane = lane_id();
     {
@@ -70,27 +72,27 @@ __device__ __forceinline__ void viterbi_wave(const float *em, unsigned char *bp,
             int32_t *out = p.path + (int64_t)b * p.T;
             int l = L - 1;
             for (int t = p.T - 1; t >= 0; --t) {
-                if (!feasible || t >= Tb) { out[t] = -1; continue; }
+                if (!feasible || t >= Tb) {
+                    out[t] = -1;
+                    if (lpath) lpath[t] = -1;
+                    continue;
+                }
                 out[t] = l;
+                if (lpath) lpath[t] = l;
                 if (bp[t * p.SP + l]) --l;
             }
         }
     }
 }
 
-template <int K>
-__global__ __launch_bounds__(kDecThreads) void noblank_best_path_kernel(DecodeParams p)
+// The emission stage of the no-blank read-outs, by the NW waves of a workgroup: the sample's label classes into lab[SP]
+// (negative labels wrap), then per row the log-softmax statistics and em[t][l] = lp_t(lab_l) for l < L, the sentinel
+// beyond.  Shared by the best-path and the token-span kernels: the same statements, so the same bits in em.
+template <int NW>
+__device__ __forceinline__ void noblank_emissions(const DecodeParams &p, float *em, int *lab, int b, int Tb, int L)
 {
-    extern __shared__ float4 smem_raw[];
-    float *em = reinterpret_cast<float *>(smem_raw);                       // [T][SP]
-    int *lab = reinterpret_cast<int *>(em + (size_t)p.T * p.SP);            // [SP]
-    unsigned char *bp = reinterpret_cast<unsigned char *>(lab + p.SP);      // [T][SP]: 1 = came from l-1
-    const int b = blockIdx.x, tid = threadIdx.x, w = wave_id(), lane = lane_id();
-    const int64_t Tb64 = p.in_len[b], L64 = p.tgt_len[b];
-    const bool ok = L64 >= 1 && L64 <= p.S && Tb64 >= L64 && Tb64 <= p.T;
-    const int Tb = ok ? (int)Tb64 : 0, L = ok ? (int)L64 : 0;
-
-    for (int l = tid; l < p.SP; l += kDecThreads) {
+    const int tid = threadIdx.x, w = wave_id(), lane = lane_id();
+    for (int l = tid; l < p.SP; l += NW * kWave) {
         int k = 0;
         if (l < L) {
             k = load_label(p.lab, p.lab64, (int64_t)b * p.S + l) % p.C;
@@ -99,7 +101,7 @@ __global__ __launch_bounds__(kDecThreads) void noblank_best_path_kernel(DecodePa
         lab[l] = k;
     }
     __syncthreads();
-    for (int t = w; t < Tb; t += kDecWaves) {                               // rows: any C
+    for (int t = w; t < Tb; t += NW) {                                      // rows: any C
         const float *row = p.x + (int64_t)t * p.st + (int64_t)b * p.sb;
         float m = -__builtin_inff();
         for (int c = lane; c < p.C; c += kWave) m = fmaxf(m, row[c]);
@@ -110,29 +112,19 @@ __global__ __launch_bounds__(kDecThreads) void noblank_best_path_kernel(DecodePa
         const float lsum = fast_log(s);
         for (int l = lane; l < p.SP; l += kWave) em[t * p.SP + l] = (l < L) ? (row[lab[l]] - m) - lsum : kNeg;
     }
-    __syncthreads();
-
-    if (w == 0) viterbi_wave<K>(em, bp, p, b, Tb, L, ok);
 }
 
-// The same read-out on the lattice of the binary (multi-label sigmoid) variant: cell (t, l) costs
-// -nn.BCELoss()(sigmoid(x[t,b,:]), y[b,l,:]) (NoBlankBinaryCTC.py:112,:88,:146) -- per row the two clamped logs, their
-// difference in a wave-private LDS row, one dot product per label row of the targets.
-template <int K>
-__global__ __launch_bounds__(kDecThreads) void binary_best_path_kernel(DecodeParams p, const float *y)
+// The same for the binary lattice: per row the two clamped logs, their difference in the wave's own LDS row
+// (drow [NW][C]), one dot product per label row of the targets y [B,S,C].
+template <int NW>
+__device__ __forceinline__ void binary_emissions(const DecodeParams &p, const float *y, float *em, float *drow, int b, int Tb,
+                                                 int L)
 {
-    extern __shared__ float4 smem_raw[];
-    float *em = reinterpret_cast<float *>(smem_raw);                       // [T][SP]
-    float *drow = em + (size_t)p.T * p.SP;                                 // [kDecWaves][C]
-    unsigned char *bp = reinterpret_cast<unsigned char *>(drow + (size_t)kDecWaves * p.C);   // [T][SP]
-    const int b = blockIdx.x, w = wave_id(), lane = lane_id();
-    const int64_t Tb64 = p.in_len[b], L64 = p.tgt_len[b];
-    const bool ok = L64 >= 1 && L64 <= p.S && Tb64 >= L64 && Tb64 <= p.T;
-    const int Tb = ok ? (int)Tb64 : 0, L = ok ? (int)L64 : 0;
+    const int w = wave_id(), lane = lane_id();
     const float *yb = y + (int64_t)b * p.S * p.C;
     float *d = drow + (size_t)w * p.C;
     const float invC = 1.0f / (float)p.C;
-    for (int t = w; t < Tb; t += kDecWaves) {
+    for (int t = w; t < Tb; t += NW) {
         const float *row = p.x + (int64_t)t * p.st + (int64_t)b * p.sb;
         float q = 0.f;
         for (int c = lane; c < p.C; c += kWave) {
@@ -152,11 +144,48 @@ __global__ __launch_bounds__(kDecThreads) void binary_best_path_kernel(DecodePar
             if (lane == 0) em[t * p.SP + l] = e;
         }
     }
+}
+
+template <int K>
+__global__ __launch_bounds__(kDecThreads) void noblank_best_path_kernel(DecodeParams p)
+{
+    extern __shared__ float4 smem_raw[];
+    float *em = reinterpret_cast<float *>(smem_raw);                       // [T][SP]
+    int *lab = reinterpret_cast<int *>(em + (size_t)p.T * p.SP);            // [SP]
+    unsigned char *bp = reinterpret_cast<unsigned char *>(lab + p.SP);      // [T][SP]: 1 = came from l-1
+    const int b = blockIdx.x, w = wave_id();
+    const int64_t Tb64 = p.in_len[b], L64 = p.tgt_len[b];
+    const bool ok = L64 >= 1 && L64 <= p.S && Tb64 >= L64 && Tb64 <= p.T;
+    const int Tb = ok ? (int)Tb64 : 0, L = ok ? (int)L64 : 0;
+
+    noblank_emissions<kDecWaves>(p, em, lab, b, Tb, L);
+    __syncthreads();
+
+    if (w == 0) viterbi_wave<K>(em, bp, p, b, Tb, L, ok);
+}
+
+// The same read-out on the lattice of the binary (multi-label sigmoid) variant: cell (t, l) costs
+// -nn.BCELoss()(sigmoid(x[t,b,:]), y[b,l,:]) (NoBlankBinaryCTC.py:112,:88,:146) -- per row the two clamped logs, their
+// difference in a wave-private LDS row, one dot product per label row of the targets.
+template <int K>
+__global__ __launch_bounds__(kDecThreads) void binary_best_path_kernel(DecodeParams p, const float *y)
+{
+    extern __shared__ float4 smem_raw[];
+    float *em = reinterpret_cast<float *>(smem_raw);                       // [T][SP]
+    float *drow = em + (size_t)p.T * p.SP;                                 // [kDecWaves][C]
+    unsigned char *bp = reinterpret_cast<unsigned char *>(drow + (size_t)kDecWaves * p.C);   // [T][SP]
+    const int b = blockIdx.x, w = wave_id();
+    const int64_t Tb64 = p.in_len[b], L64 = p.tgt_len[b];
+    const bool ok = L64 >= 1 && L64 <= p.S && Tb64 >= L64 && Tb64 <= p.T;
+    const int Tb = ok ? (int)Tb64 : 0, L = ok ? (int)L64 : 0;
+    binary_emissions<kDecWaves>(p, y, em, drow, b, Tb, L);
     __syncthreads();
     if (w == 0) viterbi_wave<K>(em, bp, p, b, Tb, L, ok);
 }
 
 }  // namespace ctc
+
+#include "decode_spans.hpp"
 
 using namespace ctc;
 
@@ -218,4 +247,54 @@ extern "C" int ctc_amd_binary_best_path(const float *x, int64_t stride_t, int64_
         case 2: return launch<binary_best_path_kernel<2>>(grid, block, smem, s, p, y);
         default: return launch<binary_best_path_kernel<4>>(grid, block, smem, s, p, y);
     }
+}
+
+
+// Token spans: one launch of decode_spans.hpp's kernel per call.
+static int token_spans_entry(const float *x, int64_t stride_t, int64_t stride_b, const void *labels, int labels_i64,
+                             const float *y, const int64_t *in_len, const int64_t *tgt_len, int T, int B, int C, int S,
+                             int32_t *path, float *score, float *nll, float *frame_conf, int32_t *start, int32_t *end,
+                             float *conf, void *stream)
+{
+    if (!x || (!labels && !y) || !in_len || !tgt_len || !path || !score || !nll || !frame_conf || !start || !end || !conf)
+        return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (T < 1 || B < 1 || C < 1 || S < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
+    const auto [K, SP] = lane_states(S);
+    if (K > 4) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
+    TokenSpanParams q;
+    DecodeParams &p = q.d;
+    p.x = x; p.st = stride_t; p.sb = stride_b;
+    p.lab = labels; p.lab64 = labels_i64;
+    p.in_len = in_len; p.tgt_len = tgt_len;
+    p.T = T; p.B = B; p.C = C; p.S = S;
+    p.SP = SP;
+    p.path = path; p.score = score;
+    q.nll = nll; q.frame_conf = frame_conf;
+    q.start = start; q.end = end; q.conf = conf;
+    return run_token_spans(q, y, K, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int ctc_amd_noblank_token_spans(const float *x, int64_t stride_t, int64_t stride_b,
+                                           const void *labels, int labels_i64,
+                                           const int64_t *in_len, const int64_t *tgt_len,
+                                           int T, int B, int C, int S,
+                                           int32_t *path, float *score, float *nll, float *frame_conf,
+                                           int32_t *start, int32_t *end, float *conf,
+                                           void *workspace, void *stream)
+{
+    (void)workspace;
+    return token_spans_entry(x, stride_t, stride_b, labels, labels_i64, nullptr, in_len, tgt_len, T, B, C, S, path, score,
+                             nll, frame_conf, start, end, conf, stream);
+}
+
+extern "C" int ctc_amd_binary_token_spans(const float *x, int64_t stride_t, int64_t stride_b, const float *y,
+                                          const int64_t *in_len, const int64_t *tgt_len,
+                                          int T, int B, int C, int S,
+                                          int32_t *path, float *score, float *nll, float *frame_conf,
+                                          int32_t *start, int32_t *end, float *conf,
+                                          void *workspace, void *stream)
+{
+    (void)workspace;
+    return token_spans_entry(x, stride_t, stride_b, nullptr, 0, y, in_len, tgt_len, T, B, C, S, path, score, nll,
+                             frame_conf, start, end, conf, stream);
 }

@@ -691,6 +691,85 @@ def blank_token_spans(log_probs, targets, input_lengths, target_lengths, blank=0
     return BlankTokenSpans(start, end, conf, frame_conf, path, score, nll)
 
 
+class TokenSpans(NamedTuple):
+    """What ``noblank_token_spans`` / ``binary_token_spans`` return (shapes and meanings: their docstrings)."""
+    start: torch.Tensor
+    end: torch.Tensor
+    conf: torch.Tensor
+    frame_conf: torch.Tensor
+    path: torch.Tensor
+    score: torch.Tensor
+    nll: torch.Tensor
+
+
+TOKEN_SPANS_MAX_LABELS = 256       # ctc_amd_noblank_token_spans / ctc_amd_binary_token_spans: S <= 256
+TOKEN_SPANS_LDS_BYTES = 160 * 1024
+
+
+def _token_spans(entry, variant, logits, targets, in_len, tgt_len):
+    xs, tg, il, tl, T, B, C, S, dev = _readout_inputs(logits, "logits", targets, in_len, tgt_len, variant)
+    path = torch.empty((B, T), dtype=torch.int32, device=dev)
+    frame_conf = torch.empty((B, T), dtype=torch.float32, device=dev)
+    start = torch.empty((B, S), dtype=torch.int32, device=dev)
+    end = torch.empty((B, S), dtype=torch.int32, device=dev)
+    conf = torch.empty((B, S), dtype=torch.float32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    nll = torch.empty(B, dtype=torch.float32, device=dev)
+    lab = () if variant == _lib.BINARY else (int(tg.dtype is torch.int64),)
+    with _on_device(dev):
+        rc = getattr(_lib.load(), entry)(
+            xs.data_ptr(), xs.stride(0), xs.stride(1), tg.data_ptr(), *lab, il.data_ptr(), tl.data_ptr(), T, B, C, S,
+            path.data_ptr(), score.data_ptr(), nll.data_ptr(), frame_conf.data_ptr(), start.data_ptr(), end.data_ptr(),
+            conf.data_ptr(), None, _stream_handle(dev))
+    if rc == _lib.ERR_UNSUPPORTED_SHAPE:
+        raise _lib.CtcAmdError(
+            "ctc_amd: %s holds a sample's lattice in LDS: S <= %d label columns and about 13 bytes per cell of T x S "
+            "(emissions, alpha, beta' and a back-pointer byte%s) within %d bytes -- T = 150 at S <= 64; got T=%d, S=%d, "
+            "C=%d" % (entry, TOKEN_SPANS_MAX_LABELS, ", plus 64 C bytes of row buffers" if variant == _lib.BINARY else "",
+                      TOKEN_SPANS_LDS_BYTES, T, S, C))
+    _lib.check(rc, entry)
+    return TokenSpans(start, end, conf, frame_conf, path, score, nll)
+
+
+def noblank_token_spans(logits, targets, input_lengths, target_lengths):
+    """The segmentation of a clip by its transcript on the no-blank lattice, in one launch ->
+    ``TokenSpans(start, end, conf, frame_conf, path, score, nll)``.
+
+    Same inputs as ``noblank_best_path``: float32 logits [T,B,C] on a HIP device (any batch / time strides), ``targets``
+    [B,S] int32 / int64 (negative labels inside L_b wrap as there), lengths on the host or on the device.  For sample b
+    with T_b frames and L_b labels:
+
+    * ``path`` [B,T] int32 and ``score`` [B] are ``noblank_best_path``'s, bit for bit: the label position per frame, -1
+      for ``t >= T_b``; -1 / -inf for a sample without an alignment.
+    * ``nll`` [B] is ``-alpha[T_b-1, L_b-1]`` of the lattice; ``+inf`` for a sample without an alignment (``L_b > T_b``
+      or lengths outside the tensor) -- the loss itself reports the reference's sentinel magnitude (1e13) there.
+    * ``frame_conf`` [B,T] fp32 is the posterior of the state the best path occupies, ``gamma_t(path_t)`` with gamma
+      normalised per row as in ``noblank_posteriors``; 0 where ``path`` is -1.  gamma [B,T,S] itself is never written.
+    * ``start``, ``end`` [B,S] int32: label j owns the frames ``start[b,j] .. end[b,j]-1``.  Every label j < L_b of an
+      aligned sample owns at least one frame and the spans partition ``[0, T_b)``: ``start[b,0] == 0``, ``end[b,j] ==
+      start[b,j+1]``, ``end[b,L_b-1] == T_b``.  Columns j >= L_b and samples without an alignment get -1 / -1.
+    * ``conf`` [B,S] fp32: the float32 sum of ``frame_conf`` over the span, from 0 in ascending t, then one float32
+      division by ``float(end - start)``; 0 where start is -1.  A float32 loop over ``path`` and ``frame_conf`` reproduces
+      it bit for bit (the rule of ``blank_token_spans``).
+
+    The class of span j is ``targets[b,j]``.  Not differentiable; no CPU path.  One workgroup per sample keeps the
+    lattice in LDS: S <= 256, and ``((3T + 8) SP + 2T + 3 SP + 8) * 4 + T * SP + 16`` bytes (SP = S rounded up to a
+    multiple of 1, 2, 4 for S <= 64, 128, 256: 13 bytes per lattice cell) within 160 KB -- T = 150 at every S <= 64;
+    ``CtcAmdError`` beyond.  include/ctc_amd.h, DESIGN.md 3.10.
+    """
+    return _token_spans("ctc_amd_noblank_token_spans", _lib.NOBLANK, logits, targets, input_lengths, target_lengths)
+
+
+def binary_token_spans(logits, targets, input_lengths, target_lengths):
+    """``noblank_token_spans`` on the lattice of the binary variant -> ``TokenSpans``: ``targets`` [B,S,C] float label
+    rows as in ``binary_best_path``, whose ``path`` / ``score`` these are bit for bit; the class of span j is row j of
+    the targets.  ``nll`` is ``+inf`` for a sample without an alignment (the loss itself reports the reference's sentinel
+    magnitude there).  LDS bound: ``((3T + 8) SP + 2T + 2 SP + 16 C + 8) * 4 + T * SP + 16`` bytes within 160 KB (S <=
+    256; T = 150 at every S <= 64 and C <= 256 -- not ``binary_posteriors``' T <= 168, S <= 64, C <= 256);
+    ``CtcAmdError`` beyond."""
+    return _token_spans("ctc_amd_binary_token_spans", _lib.BINARY, logits, targets, input_lengths, target_lengths)
+
+
 def noblank_posteriors(logits, targets, input_lengths, target_lengths):
     """Per-step state posteriors of the no-blank lattice -> (gamma[B,T,S], nll[B]).
 

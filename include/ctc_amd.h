@@ -239,6 +239,49 @@ int ctc_amd_binary_best_path(const float *x, int64_t stride_t, int64_t stride_b,
                              int T, int B, int C, int S,
                              int32_t *path, float *score, void *workspace, void *stream);
 
+/* Token spans on the no-blank lattice: one record per label of the transcript -- the frame where the best alignment
+ * starts it, the frame where it ends, and how sure the model is -- in ONE launch, without gamma [B,T,S] ever being
+ * written.  Inputs: those of ctc_amd_noblank_best_path (float32 logits, stride over classes 1; int32 / int64 labels,
+ * negative ones inside L_b wrap as there).  Every element of every output is written; nothing needs clearing.
+ *   path       [B,T] int32, score [B]: what ctc_amd_noblank_best_path writes for the same inputs, bit for bit (the same
+ *              emission stage and the same max-scan): -1 for t >= T_b, -1 / -inf for a sample without an alignment
+ *   nll        [B]: -alpha[T_b-1, L_b-1], the chain of ctc_amd_noblank_loss_grad; +inf for a sample without an
+ *              alignment (L_b > T_b, lengths outside the tensor) -- the loss itself reports the reference's sentinel
+ *              magnitude (1e13) there
+ *   frame_conf [B,T] fp32: gamma_t(path_t), the row-normalised posterior exp(alpha_t(l) + beta'_t(l) - e_t(l)) /
+ *              sum_l' (same) at the state the best path occupies; 0 where path is -1
+ *   start, end [B,S] int32: label j < L_b of an aligned sample owns the frames start .. end-1, the t < T_b with
+ *              path[b,t] = j; every such label owns at least one frame and the spans partition [0, T_b):
+ *              start[b,0] = 0, end[b,j] = start[b,j+1], end[b,L_b-1] = T_b.  -1 / -1 for j >= L_b and for every j of a
+ *              sample without an alignment
+ *   conf       [B,S] fp32: the sum of frame_conf[b,t] over t = start .. end-1 -- from 0.0f, in ascending t, in fp32 --
+ *              followed by one correctly rounded fp32 division by float(end - start); 0 where start is -1.  The order is
+ *              part of the contract: a float32 loop in that order reproduces the bits (as ctc_amd_blank_token_spans).
+ * The class of span j is labels[b,j].  One 1024-thread workgroup per sample holds the sample's lattice in LDS: S <= 256,
+ * and ((3T + 8) SP + 2T + 3SP + 8) * 4 + T * SP + 16 bytes <= 160 KB, SP = S rounded up to the states per lane (1, 2, 4
+ * for S <= 64, 128, 256) -- 13 bytes per lattice cell, T = 150 at every S <= 64; CTC_AMD_ERR_UNSUPPORTED_SHAPE beyond.
+ * Null pointers and T, B, C, S < 1 return CTC_AMD_ERR_BAD_ARGUMENT before anything is dereferenced or launched.
+ * `workspace` is ignored and may be NULL.  No atomics, no waiting between workgroups: deterministic. */
+int ctc_amd_noblank_token_spans(const float *x, int64_t stride_t, int64_t stride_b,
+                                const void *labels, int labels_i64,
+                                const int64_t *in_len, const int64_t *tgt_len,
+                                int T, int B, int C, int S,
+                                int32_t *path, float *score, float *nll, float *frame_conf,
+                                int32_t *start, int32_t *end, float *conf,
+                                void *workspace, void *stream);
+
+/* The same on the lattice of the binary variant: y [B,S,C] float label rows, path / score those of
+ * ctc_amd_binary_best_path bit for bit, nll the chain of ctc_amd_binary_loss_grad; the class of span j is row j of y.
+ * LDS: the bound above with the label table replaced by the waves' row buffers,
+ * ((3T + 8) SP + 2T + 2SP + 16 C + 8) * 4 + T * SP + 16 bytes <= 160 KB (T = 150 at every S <= 64 and C <= 256; no
+ * T <= 168 limit as in ctc_amd_binary_posteriors). */
+int ctc_amd_binary_token_spans(const float *x, int64_t stride_t, int64_t stride_b, const float *y,
+                               const int64_t *in_len, const int64_t *tgt_len,
+                               int T, int B, int C, int S,
+                               int32_t *path, float *score, float *nll, float *frame_conf,
+                               int32_t *start, int32_t *end, float *conf,
+                               void *workspace, void *stream);
+
 /* Best-path (Viterbi) forced alignment on the blank-CTC lattice (torch.nn.CTCLoss semantics, as
  * ctc_amd_blank_loss_grad): which frame belongs to which label of a KNOWN target sequence, and the score of that
  * alignment.  Inputs: the same layout and contract as ctc_amd_blank_loss_grad (log_probs used as given, no

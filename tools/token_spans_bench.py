@@ -1,10 +1,18 @@
-"""Blank-CTC token spans in one call against the route a caller composes from the best path and the posteriors, on the
-same inputs, in the same process.
+"""Token spans in one call against the route a caller composes from the best path and the posteriors, on the same
+inputs, in the same process; --family chooses the lattice (blank, the default; noblank; binary).
 
-    python tools/token_spans_bench.py [--shapes 2000x64x1000x100 150x256x158x20 1250x16x64x1023] [--reps 9]
-                                      [--per-graph 5] [--eager] [--routes spans composed_b1 composed_b2] [--out FILE]
+    python tools/token_spans_bench.py [--family blank] [--shapes 2000x64x1000x100 150x256x158x20 1250x16x64x1023]
+                                      [--reps 9] [--per-graph 5] [--eager] [--routes spans composed_b1 composed_b2]
+                                      [--out FILE]
 
-Routes, per shape T x B x C x S (synth_blank inputs, full-length samples):
+Routes of --family noblank / binary, per shape T x B x C x S (synth_noblank / synth_binary inputs, full-length samples;
+default shapes 10x10x33x5 and 150x256x158x20):
+    spans        (a)  ctc_amd.noblank_token_spans / binary_token_spans: ONE launch
+    composed_b1  (b1) *_best_path + *_posteriors: path, score, gamma [B,T,S], nll (two launches)
+    composed_b2  (b2) b1, then torch.gather(gamma, 2, path) and the mask of the frames behind T_b: the composition that
+                      yields frame_conf.  The float32 per-label loop that a caller would run on the host for start / end /
+                      conf is in NEITHER timed region.
+Routes of --family blank, per shape T x B x C x S (synth_blank inputs, full-length samples):
     spans        (a)  ctc_amd.blank_token_spans: start, end, conf [B,S], frame_conf, path [B,T], score, nll [B]
     composed_b1  (b1) ctc_amd.blank_best_path + ctc_amd.blank_posteriors: path, score, gamma [B,T,2S+1], nll
     composed_b2  (b2) b1, then torch.gather(gamma, 2, path) and a merge of equal states in torch without a host loop
@@ -27,7 +35,7 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 import ctc_amd  # noqa: E402
-from tests.helpers import synth_blank  # noqa: E402
+from tests.helpers import synth_binary, synth_blank, synth_noblank  # noqa: E402
 
 
 def torch_merge(path, gamma, S):
@@ -49,7 +57,36 @@ def torch_merge(path, gamma, S):
     return start, end, conf, fc
 
 
-def routes(T, B, C, S, dev):
+def lattice_routes(family, T, B, C, S, dev):
+    """the no-blank / binary lattice: the new call and what a caller composes today, on the same device tensors"""
+    if family == "noblank":
+        x, tgt, Tb, L = synth_noblank(0, T, B, C, S)
+        spans_fn, path_fn, post_fn = ctc_amd.noblank_token_spans, ctc_amd.noblank_best_path, ctc_amd.noblank_posteriors
+    else:
+        x, tgt, Tb, L = synth_binary(0, T, B, C, S, density=0.2)
+        spans_fn, path_fn, post_fn = ctc_amd.binary_token_spans, ctc_amd.binary_best_path, ctc_amd.binary_posteriors
+    args = (x.to(dev), tgt.to(dev), Tb.to(dev), L.to(dev))
+
+    def spans():
+        return spans_fn(*args)
+
+    def composed_b1():
+        path, score = path_fn(*args)
+        gamma, nll = post_fn(*args)
+        return path, score, gamma, nll
+
+    def composed_b2():
+        path, score, gamma, nll = composed_b1()
+        fc = torch.gather(gamma, 2, path.clamp(min=0).long().unsqueeze(2)).squeeze(2)
+        fc = torch.where(path >= 0, fc, torch.zeros_like(fc))
+        return fc, path, score, nll
+
+    return {"spans": spans, "composed_b1": composed_b1, "composed_b2": composed_b2}
+
+
+def routes(T, B, C, S, dev, family="blank"):
+    if family != "blank":
+        return lattice_routes(family, T, B, C, S, dev)
     lp, tgt, Tb, L = synth_blank(0, T, B, C, S)
     args = (lp.to(dev), tgt.to(dev), Tb.to(dev), L.to(dev))
 
@@ -122,20 +159,24 @@ def time_graphs(graphs, reps, per_graph):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--shapes", nargs="+", default=["2000x64x1000x100", "150x256x158x20", "1250x16x64x1023"])
+    ap.add_argument("--family", choices=["blank", "noblank", "binary"], default="blank")
+    ap.add_argument("--shapes", nargs="+")
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--per-graph", type=int, default=5)
     ap.add_argument("--eager", action="store_true")
     ap.add_argument("--routes", nargs="+", default=["spans", "composed_b1", "composed_b2"])
     ap.add_argument("--out")
     a = ap.parse_args()
+    if not a.shapes:
+        a.shapes = (["2000x64x1000x100", "150x256x158x20", "1250x16x64x1023"] if a.family == "blank"
+                    else ["10x10x33x5", "150x256x158x20"])
     dev = torch.device("cuda:0")
     lines = ["| T x B x C x S | route | median us | min | max | vs composed_b1 | peak MB of one call |",
              "|---|---|---|---|---|---|---|"]
     for shape in a.shapes:
         T, B, C, S = (int(v) for v in shape.split("x"))
         res, peak, graphs = {}, {}, {}
-        fns = {name: fn for name, fn in routes(T, B, C, S, dev).items() if name in a.routes}
+        fns = {name: fn for name, fn in routes(T, B, C, S, dev, a.family).items() if name in a.routes}
         for name, fn in fns.items():
             g = capture(fn, a.reps, a.per_graph, a.eager)
             if g is not None:
