@@ -1327,3 +1327,4 @@ extern "C" int ctc_amd_lstm_backward(const float *d_series, int64_t ds_stride_t,
 }
 
 #include "lstm_wide.hpp"
+#include "head_wide.hpp"

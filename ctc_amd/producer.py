@@ -34,7 +34,14 @@ the head's backward is HIP as well (``ctc_amd_head_backward`` / ``head_backward`
 then both products, the column sums and the sums over the frames on the matrix cores -- two launches, three when the weight
 gradient splits its rows) for T B <= ``HEAD_BACKWARD_MAX_ROWS`` rows (measured, profiles/r14_head_backward.md).  Beyond that
 gate, and for the shapes the entry does not take (B > 256, K not a multiple of 16, unaligned rows), the head's backward is
-torch arithmetic (``_head_backward_torch``: elementwise kernels and two rocBLAS GEMMs).  No CPU path: non-HIP tensors raise.
+torch arithmetic (``_head_backward_torch``: elementwise kernels and two rocBLAS GEMMs).  Batches beyond 256 samples stay on the
+HIP path as well (``ctc_amd_head_forward_wide`` / ``head_forward_wide``: a frame's rows no longer fit one workgroup, so BatchNorm's
+batch statistics cross workgroups at a kernel boundary -- one launch in eval mode, two in train mode, the Linear output and all of
+eval mode bit for bit the narrow launch's; ``ctc_amd_head_backward_wide`` / ``head_backward_wide``: the row pass walks the frame's
+blocks of 256 rows, the products are the narrow entry's) for T B <= ``HEAD_WIDE_MAX_ROWS`` and T B <=
+``HEAD_WIDE_BACKWARD_MAX_ROWS`` rows (measured, profiles/r18_head_wide.md: 0.70 ms against 6.41 ms for the train-mode head at
+T = 150, B = 2048, C = 33); beyond the first gate torch's layers run frame by frame, beyond the second ``_head_backward_torch``.
+No CPU path: non-HIP tensors raise.
 """
 import torch
 import torch.nn as nn
@@ -136,6 +143,87 @@ def head_backward(d_out, feat, weight, bn_weight, bn_bias, lin, mean=None, invst
     return d_feat, d_weight, d_bias, d_gamma, d_beta
 
 
+def head_forward_wide(feat, weight, bias, bn_weight, bn_bias, running_mean=None, running_var=None, eps=1e-5, mask=None,
+                      want_backward_state=False):
+    """``head_forward`` for batches beyond 256 samples (``ctc_amd_head_forward_wide``: B up to 65536, the B <= 256 of the narrow
+    entry too; one launch in eval mode, two in train mode -- a frame's rows no longer fit one workgroup, so BatchNorm's batch
+    statistics cross workgroups at a kernel boundary): the same arguments, the same return value, or None when the entry does
+    not take the shape (K not a multiple of 16, unaligned rows, T B > 2^22 rows, B > 65536).  The Linear output and all of eval
+    mode are bit for bit the narrow entry's.  The scratch is one ``torch.empty`` per call, as ``head_backward`` explains."""
+    F._require_hip(feat, "feat")
+    T, B, K = feat.shape
+    C = weight.shape[0]
+    dev = feat.device
+    f = feat if (feat.dtype is torch.float32 and feat.stride(2) == 1) else feat.float().contiguous()
+    prm = [t if (t.dtype is torch.float32 and t.is_contiguous()) else t.float().contiguous()
+           for t in (weight, bias, bn_weight, bn_bias)]
+    rm = rv = None
+    if running_mean is not None:
+        rm, rv = running_mean.float().contiguous(), running_var.float().contiguous()
+    mk = None if mask is None else (mask if (mask.dtype is torch.float32 and mask.is_contiguous()) else mask.float().contiguous())
+    lib = _lib.load()
+    nbytes = lib.ctc_amd_head_forward_wide_scratch_bytes(T, B, K, C)
+    if nbytes == 0 and min(T, B, K, C) >= 1:
+        return None
+    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    out = torch.empty((T, B, C), dtype=torch.float32, device=dev)
+    train = rm is None
+    lin = torch.empty((T, B, C), dtype=torch.float32, device=dev) if want_backward_state else None
+    mean = torch.empty((T, C), dtype=torch.float32, device=dev) if train else None
+    var = torch.empty((T, C), dtype=torch.float32, device=dev) if train else None
+    inv = torch.empty((T, C), dtype=torch.float32, device=dev) if train else None
+    ptr = lambda t: None if t is None else t.data_ptr()     # noqa: E731
+    with F._on_device(dev):
+        rc = lib.ctc_amd_head_forward_wide(f.data_ptr(), f.stride(0), f.stride(1), *(t.data_ptr() for t in prm), ptr(rm), ptr(rv),
+                                           float(eps), ptr(mk), T, B, K, C, out.data_ptr(), out.stride(0), out.stride(1),
+                                           ptr(lin), ptr(mean), ptr(var), ptr(inv), scratch.data_ptr(), nbytes,
+                                           F._stream_handle(dev))
+    if rc == _lib.ERR_UNSUPPORTED_SHAPE:
+        return None
+    if rc:
+        _lib.check(rc, "ctc_amd_head_forward_wide")
+    return out, lin, mean, var, inv
+
+
+def head_backward_wide(d_out, feat, weight, bn_weight, bn_bias, lin, mean=None, invstd=None, running_mean=None, running_var=None,
+                       eps=1e-5, mask=None, need_dfeat=True):
+    """``head_backward`` for batches beyond 256 samples (``ctc_amd_head_backward_wide``: B up to 65536; the row pass walks a
+    frame's blocks of 256 rows, the products and the reduce launch are the narrow entry's -- two launches, three when
+    T B > 128): the same arguments, the same return value, or None when the entry does not take the shape (what
+    ``head_forward_wide`` refuses).  Deterministic.  The scratch is one ``torch.empty`` per call, as ``head_backward`` explains."""
+    F._require_hip(d_out, "d_out")
+    F._require_hip(feat, "feat")
+    T, B, K = feat.shape
+    C = weight.shape[0]
+    dev = feat.device
+    f32 = torch.float32
+    do = d_out if (d_out.dtype is f32 and d_out.stride(2) == 1) else d_out.float().contiguous()
+    f = feat if (feat.dtype is f32 and feat.stride(2) == 1) else feat.float().contiguous()
+    cont = lambda t: None if t is None else (t if (t.dtype is f32 and t.is_contiguous()) else t.float().contiguous())   # noqa: E731
+    w, g, be, ln, mn, iv, rm, rv, mk = (cont(t) for t in (weight, bn_weight, bn_bias, lin, mean, invstd, running_mean,
+                                                           running_var, mask))
+    lib = _lib.load()
+    nbytes = lib.ctc_amd_head_backward_wide_scratch_bytes(T, B, K, C)
+    if nbytes == 0 and min(T, B, K, C) >= 1:
+        return None
+    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    d_feat = torch.empty((T, B, K), dtype=f32, device=dev) if need_dfeat else None
+    d_weight = torch.empty((C, K), dtype=f32, device=dev)
+    d_bias, d_gamma, d_beta = (torch.empty(C, dtype=f32, device=dev) for _ in range(3))
+    ptr = lambda t: None if t is None else t.data_ptr()     # noqa: E731
+    with F._on_device(dev):
+        rc = lib.ctc_amd_head_backward_wide(do.data_ptr(), do.stride(0), do.stride(1), f.data_ptr(), f.stride(0), f.stride(1),
+                                            w.data_ptr(), g.data_ptr(), be.data_ptr(), ln.data_ptr(), ptr(mn), ptr(iv), ptr(rm),
+                                            ptr(rv), float(eps), ptr(mk), T, B, K, C, ptr(d_feat), B * K if need_dfeat else 0,
+                                            K if need_dfeat else 0, d_weight.data_ptr(), d_bias.data_ptr(), d_gamma.data_ptr(),
+                                            d_beta.data_ptr(), scratch.data_ptr(), nbytes, F._stream_handle(dev))
+    if rc == _lib.ERR_UNSUPPORTED_SHAPE:
+        return None
+    if rc:
+        _lib.check(rc, "ctc_amd_head_backward_wide")
+    return d_feat, d_weight, d_bias, d_gamma, d_beta
+
+
 def _head_backward_torch(d_out, feat, weight, gamma, beta, lin, mean, inv, mask, train, need_dfeat):
     """the head's backward as torch arithmetic (BatchNorm's own formulas on the saved Linear output and statistics, two
     GEMMs over all frames at once): what runs outside the gate.  mean / inv: [T,C] (train) or [1,C] (eval)."""
@@ -161,14 +249,20 @@ def _head_backward_torch(d_out, feat, weight, gamma, beta, lin, mean, inv, mask,
 class _HeadFn(torch.autograd.Function):
     """feat [T,B,K], Linear and BatchNorm parameters, running statistics (eval) or None (train), mask -> the head's output
     [T,B,C] (+ the batch statistics, non-differentiable).  Forward: one HIP launch.  Backward: ``head_backward`` (HIP) for
-    T B <= ``HEAD_BACKWARD_MAX_ROWS`` rows; ``_head_backward_torch`` beyond the gate and for shapes the entry does not take."""
+    T B <= ``HEAD_BACKWARD_MAX_ROWS`` rows; ``_head_backward_torch`` beyond the gate and for shapes the entry does not take.
+    B > 256 (``ctx.wide``): ``head_forward_wide`` (one launch in eval mode, two in train mode) and, for T B <=
+    ``HEAD_WIDE_BACKWARD_MAX_ROWS`` rows, ``head_backward_wide``; the caller (``LSTM_cell._head``) holds the forward's gate."""
 
     @staticmethod
     def forward(ctx, feat, weight, bias, bn_weight, bn_bias, running_mean, running_var, eps, mask):
         need = any(ctx.needs_input_grad[:5])
-        res = head_forward(feat, weight, bias, bn_weight, bn_bias, running_mean, running_var, eps, mask, want_backward_state=need)
+        ctx.wide = feat.shape[1] > 256
+        fwd = head_forward_wide if ctx.wide else head_forward
+        res = fwd(feat, weight, bias, bn_weight, bn_bias, running_mean, running_var, eps, mask, want_backward_state=need)
         if res is None:
-            raise _lib.CtcAmdError("ctc_amd: the fused head does not take this shape (B <= 256, feature dimension a multiple of 16)")
+            raise _lib.CtcAmdError("ctc_amd: the fused head does not take this shape (feature dimension a multiple of 16, "
+                                   "16-byte aligned rows, T B <= 2^22)" if ctx.wide else
+                                   "ctc_amd: the fused head does not take this shape (B <= 256, feature dimension a multiple of 16)")
         out, lin, mean, var, inv = res
         ctx.train = running_mean is None
         ctx.eps = float(eps)
@@ -188,7 +282,11 @@ class _HeadFn(torch.autograd.Function):
         T, B, _ = lin.shape
         need_dfeat = ctx.needs_input_grad[0]
         res = None
-        if T * B <= HEAD_BACKWARD_MAX_ROWS:
+        if ctx.wide:
+            if T * B <= HEAD_WIDE_BACKWARD_MAX_ROWS:
+                stats = (mean, inv, None, None) if ctx.train else (None, None, rmean, rvar)
+                res = head_backward_wide(d_out, feat, weight, gamma, beta, lin, *stats, ctx.eps, mask, need_dfeat)
+        elif T * B <= HEAD_BACKWARD_MAX_ROWS:
             if ctx.train:
                 res = head_backward(d_out, feat, weight, gamma, beta, lin, mean, inv, None, None, ctx.eps, mask, need_dfeat)
             else:
@@ -451,6 +549,26 @@ FUSED_FORWARD_MAX_WG_ROWS = 64
 # C = 158 (1.02 - 1.09 x).  The bound is the largest measured point that wins at every B and C measured (r13's rule).
 HEAD_BACKWARD_MAX_ROWS = 10240
 
+# LSTM_cell._head takes the wide head (head_forward_wide: one launch in eval mode, two in train mode) for B > 256 up to this many
+# head rows T B; 0 closes the gate, and such a batch goes through torch's four layers frame by frame as before.  T B for the
+# neighbours' reason: the product, the statistics and the epilogue are T B rows of work, the comparator is 4 T torch kernels.
+# Measured, not guessed (profiles/r18_head_wide.md, LSTM_cell._head with the gate open and closed, both captured into graphs,
+# K = 1024, B in {512, 1024, 2048}, C in {33, 158}, train mode with p = 0.3 and eval mode): at every measured T B = 5120 ...
+# 307200 the wide path's median is 0.07 ... 0.83 of the closed gate's and below the minimum of its rounds -- 0.70 ms against
+# 6.41 ms in train mode at T = 150, B = 2048, C = 33, 2.82 ms against 6.88 ms at C = 158, 158 us against 286 us at T = 10, B = 512,
+# C = 33; the narrowest win is eval mode at T = 10, B = 2048, C = 158 (228 us against 273 us).  The bound is the largest measured
+# point that wins at every B and C measured (r13's rule); no measured point loses, so it is the largest measured point.
+HEAD_WIDE_MAX_ROWS = 307200
+
+# _HeadFn.backward behind the wide head takes the HIP path (head_backward_wide) up to this many head rows T B; 0 closes the gate,
+# and _head_backward_torch runs on the saved state, as it does beyond the gate.  Measured, not guessed (profiles/r18_head_wide.md,
+# the same shapes, train mode, with and without d_feat, both bodies captured into graphs): at T B = 5120, 10240 and 20480 the new
+# call's median is 0.27 ... 0.85 of the torch arithmetic's and below the minimum of its rounds at every B and C; at T B = 76800,
+# 153600 and 307200 it wins at C = 33 (0.29 ... 0.33 x: 2.03 ms against 6.81 ms at T = 150, B = 2048) and loses at C = 158
+# (1.16 ... 1.29 x: the products launch, ctc_amd_head_backward's own, against two rocBLAS GEMMs -- what closes
+# HEAD_BACKWARD_MAX_ROWS at 10240 too).  The bound is the largest measured point that wins at every B and C measured (r13's rule).
+HEAD_WIDE_BACKWARD_MAX_ROWS = 20480
+
 # _SeriesFn.backward takes the HIP path whole (lstm_backward) up to this many rows T B; 0 closes the gate.  T B for
 # HEAD_BACKWARD_MAX_ROWS's reason: the products and the column sums are T B rows of work, the torch arithmetic behind the
 # recurrence launch is launch-bound at small T B and three rocBLAS GEMMs beyond.  Measured, not guessed
@@ -590,12 +708,14 @@ class LSTM_cell(nn.Module):
 
     def _head(self, feat):
         """self.v applied to every frame (LSTM.py:48): one launch when self.v is the reference's BasicModule and the shape
-        is one the launch takes, the module itself frame by frame otherwise (a custom _BaseModule, B > 256, ...)."""
+        is one the launch takes, the module itself frame by frame otherwise (a custom _BaseModule, ...).  B > 256: the wide
+        launches (``head_forward_wide``) for T B <= ``HEAD_WIDE_MAX_ROWS`` rows, the module frame by frame beyond that gate."""
         T = self.temporal
         layers = self._std_layers()
         std = layers is not None
         B, K = feat.shape[1], feat.shape[2]
-        if not std or feat.shape[0] < T or B > 256 or K % 16 or (self.training and (B < 2 or layers[1].momentum is None)):
+        wide_closed = B > 256 and T * B > HEAD_WIDE_MAX_ROWS
+        if not std or feat.shape[0] < T or wide_closed or K % 16 or (self.training and (B < 2 or layers[1].momentum is None)):
             return torch.stack([self.v(feat[time]) for time in range(T)])
         lin, bn, drop = layers[0], layers[1], layers[3]
         x = feat[:T]
@@ -622,7 +742,9 @@ class LSTM_cell(nn.Module):
         layers = None if self.training else self._std_layers()
         if layers is None or feat.dim() != 3 or feat.shape[0] < T or 4 * T > FUSED_FORWARD_MAX_WG_ROWS:
             return None
-        if feat.shape[1] > 256:                              # (the two-launch path leaves such a batch to torch's layers: stay with it)
+        # B > 256 stays closed here: the head of such a batch is head_forward_wide's launch, followed by the recurrence's; whether
+        # one launch from feat to v_series pays at these batches has not been measured (a measurement of its own).
+        if feat.shape[1] > 256:
             return None
         if torch.is_grad_enabled() and any(t.requires_grad for t in (feat, v_hsn, v_csn, *self.parameters())):
             return None

@@ -628,6 +628,52 @@ int ctc_amd_lstm_series_backward_wide(const float *d_series, int64_t ds_stride_t
  * rows < 1, H < 1;  CTC_AMD_ERR_UNSUPPORTED_SHAPE: H > 160. */
 int ctc_amd_lstm_bias_grad_wide(const float *dpre, int64_t rows, int H, float *d_b_ih, float *d_b_hh, void *stream);
 
+/* ctc_amd_head_forward for batches beyond one workgroup's 256 rows: every 1 <= B <= 65536 (the B <= 256 it already takes too).
+ * Arguments, outputs and formulas are ctc_amd_head_forward's, followed by the scratch.  Every Linear output is the same fmaf chain
+ * as the narrow entry's (bit for bit, and so is all of eval mode: no value there depends on another row).  Train mode: the
+ * statistics of each frame's B rows in two passes -- the mean, then the centred second moment; biased variance, eps inside the
+ * root -- with the sums over a frame's rows crossing workgroups at a kernel boundary:
+ *   eval   ONE launch: grid (frame, block of 256 rows, group of <= 3 column tiles); a wave takes 16 rows and every column tile
+ *          of its group, so feat is read ceil(ceil(C / 16) / 3) times, not ceil(C / 16) times;
+ *   train  TWO launches: the same grid writes the Linear output (to linear_out, or to the scratch when that is NULL) and the
+ *          column sums of its 256 rows (lane quarters, then waves) to the scratch; then one workgroup per (frame, column tile)
+ *          adds those sums in ascending block order (mean), walks the Linear output for the centred moment (per lane: row blocks
+ *          ascending, then its four rows; then lane quarters, then waves), and applies BatchNorm, ReLU and the mask.
+ * No atomics, every order fixed by the shape: two calls give the same bits.  No allocation, no host synchronisation: safe under
+ * stream capture.  Every element of every output that is not NULL is written (save_* in train mode only, as the narrow entry).
+ * scratch: at least ctc_amd_head_forward_wide_scratch_bytes(T, B, K, C) bytes of device memory, any alignment, contents
+ * irrelevant.  CTC_AMD_ERR_BAD_ARGUMENT (decided first, before any HIP call): a NULL among feat, the four parameters, out and
+ * scratch; a size < 1; one running statistic without the other; out_stride_b < C; train mode with B < 2; scratch_bytes below
+ * the query.  CTC_AMD_ERR_UNSUPPORTED_SHAPE: K not a multiple of 16, feat strides not multiples of 4, feat or weight not
+ * 16-byte aligned, T B > 2^22 rows, B > 65536.  The query answers 0 for sizes < 1 and for shapes the entry does not take. */
+size_t ctc_amd_head_forward_wide_scratch_bytes(int T, int B, int K, int C);
+int ctc_amd_head_forward_wide(const float *feat, int64_t feat_stride_t, int64_t feat_stride_b,
+                              const float *weight, const float *bias, const float *bn_weight, const float *bn_bias,
+                              const float *running_mean, const float *running_var, float eps, const float *mask,
+                              int T, int B, int K, int C,
+                              float *out, int64_t out_stride_t, int64_t out_stride_b,
+                              float *linear_out, float *save_mean, float *save_var, float *save_invstd,
+                              void *scratch, size_t scratch_bytes, void *stream);
+
+/* ctc_amd_head_backward for every 1 <= B <= 65536: the same arguments, the same formulas, the same errors (with the batch bound
+ * at 65536) and the same scratch layout.  Only the row pass differs: one workgroup per (frame, column tile) walks the frame's
+ * blocks of 256 rows -- dbeta_t and dgamma_t per lane over the row blocks ascending, then lane quarters, then waves; in train
+ * mode a second walk writes dlin and sums it (eval mode has no cross-row term and writes dlin in the first walk).  The products
+ * launch and the reduce launch are ctc_amd_head_backward's own.  Two launches on `stream`, three when T B > 128; no atomics, no
+ * allocation, no host synchronisation: safe under stream capture, and two calls give the same bits. */
+size_t ctc_amd_head_backward_wide_scratch_bytes(int T, int B, int K, int C);
+int ctc_amd_head_backward_wide(const float *d_out, int64_t dout_stride_t, int64_t dout_stride_b,
+                               const float *feat, int64_t feat_stride_t, int64_t feat_stride_b,
+                               const float *weight, const float *bn_weight, const float *bn_bias,
+                               const float *linear_out,
+                               const float *save_mean, const float *save_invstd,
+                               const float *running_mean, const float *running_var, float eps,
+                               const float *mask,
+                               int T, int B, int K, int C,
+                               float *d_feat, int64_t dfeat_stride_t, int64_t dfeat_stride_b,
+                               float *d_weight, float *d_bias, float *d_bn_weight, float *d_bn_bias,
+                               void *scratch, size_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
