@@ -62,6 +62,18 @@ PROTOTYPES = {
     "ctc_amd_head_backward_wide_scratch_bytes": (_sz, [_int, _int, _int, _int]),
     "ctc_amd_head_backward_wide": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp,
                                           _int, _int, _int, _int, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # the head entries on a typed feat: the sibling's list with `int feat_dtype` behind the feat pointer
+    "ctc_amd_head_forward_typed": (_int, [_vp, _int, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _int, _int, _int, _int,
+                                          _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "ctc_amd_head_forward_wide_typed": (_int, [_vp, _int, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _int, _int, _int,
+                                               _int, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ctc_amd_lstm_forward_typed": (_int, [_vp, _int, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _int, _int, _int, _int, _vp, _i64, _i64, _int, _f32, _vp, _vp, _vp]),
+    "ctc_amd_head_backward_typed": (_int, [_vp, _i64, _i64, _vp, _int, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32,
+                                           _vp, _int, _int, _int, _int, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ctc_amd_head_backward_wide_typed": (_int, [_vp, _i64, _i64, _vp, _int, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                _f32, _vp, _int, _int, _int, _int, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _sz,
+                                                _vp]),
     "ctc_amd_dedup_multihot_targets": (_int, [_vp, _int, _int, _int, _int, _vp, _vp, _vp]),
     "ctc_amd_blank_set_schedule": (_int, [_int]),
     "ctc_amd_workspace_status": (_int, [_vp, _int, _vp, ctypes.POINTER(ctypes.c_uint)]),

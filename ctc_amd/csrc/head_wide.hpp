@@ -71,7 +71,7 @@ inline unsigned head_wide_block(int B) { return 64u * (unsigned)((B < kHeadWideR
 
 // The product of one row block with one group of N column tiles.  Eval mode (p.rmean): head_kernel's epilogue, the whole head.
 // Train mode: lin and the block's column sums psum [T][NB][CP] (a pad column gets 0).
-template <int N>
+template <int N, typename E>
 __global__ __launch_bounds__(1024) void head_wide_product_kernel(HeadParams p, float *psum, int CP)
 {
     __shared__ float red[16][16];                            // [wave][column of the tile]
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(1024) void head_wide_product_kernel(HeadParams p, f
     const int NW = blockDim.x >> 6, NB = gridDim.y;
     const int row0 = kHeadWideRows * rb + 16 * w;            // operands clamped like head_kernel's: the padding is masked out below
     const int arow = min(row0 + fr, p.B - 1);
-    const float *ap = p.feat + (int64_t)t * p.fst + (int64_t)arow * p.fsb + 4 * fq;
+    const E *ap = static_cast<const E *>(p.feat) + (int64_t)t * p.fst + (int64_t)arow * p.fsb + 4 * fq;
     const float *bp[N];
     head_f4 acc[N];
 #pragma unroll
@@ -247,10 +247,10 @@ __global__ __launch_bounds__(1024) void head_wide_bwd_rows_kernel(HeadBwdRowsPar
     }
 }
 
-template <int N>
+template <int N, typename E>
 inline int head_wide_launch_product(const HeadParams &p, float *psum, const HeadWideLayout &L, int NG, hipStream_t st)
 {
-    return launch<head_wide_product_kernel<N>>(dim3(p.T, L.NB, NG), dim3(head_wide_block(p.B)), 0, st, p, psum, L.CP);
+    return launch<head_wide_product_kernel<N, E>>(dim3(p.T, L.NB, NG), dim3(head_wide_block(p.B)), 0, st, p, psum, L.CP);
 }
 
 }  // namespace ctc
@@ -261,22 +261,24 @@ extern "C" size_t ctc_amd_head_forward_wide_scratch_bytes(int T, int B, int K, i
     return ctc::head_wide_layout(T, B, C).total + ctc::kHeadBwdAlign;             // (the entry aligns the pointer itself)
 }
 
-// ctc_amd_head_forward for any batch up to kHeadWideMaxBatch: ONE launch in eval mode, TWO in train mode (see the top).
-extern "C" int ctc_amd_head_forward_wide(const float *feat, int64_t feat_stride_t, int64_t feat_stride_b,
-                                         const float *weight, const float *bias, const float *bn_weight, const float *bn_bias,
-                                         const float *running_mean, const float *running_var, float eps, const float *mask,
-                                         int T, int B, int K, int C,
-                                         float *out, int64_t out_stride_t, int64_t out_stride_b,
-                                         float *linear_out, float *save_mean, float *save_var, float *save_invstd,
-                                         void *scratch, size_t scratch_bytes, void *stream)
+// ctc_amd_head_forward(_typed) for any batch up to kHeadWideMaxBatch: ONE launch in eval mode, TWO in train mode (see the top).
+// Only the product launch reads feat: it carries the element type, the statistics launch is one kernel for all three.
+extern "C" int ctc_amd_head_forward_wide_typed(const void *feat, int feat_dtype, int64_t feat_stride_t, int64_t feat_stride_b,
+                                               const float *weight, const float *bias, const float *bn_weight, const float *bn_bias,
+                                               const float *running_mean, const float *running_var, float eps, const float *mask,
+                                               int T, int B, int K, int C,
+                                               float *out, int64_t out_stride_t, int64_t out_stride_b,
+                                               float *linear_out, float *save_mean, float *save_var, float *save_invstd,
+                                               void *scratch, size_t scratch_bytes, void *stream)
 {
+    if (feat_dtype != CTC_AMD_F32 && feat_dtype != CTC_AMD_BF16 && feat_dtype != CTC_AMD_F16) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (!feat || !weight || !bias || !bn_weight || !bn_bias || !out || !scratch) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (T < 1 || B < 1 || K < 1 || C < 1 || (running_mean == nullptr) != (running_var == nullptr)) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (out_stride_b < C) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (running_mean == nullptr && B < 2) return CTC_AMD_ERR_BAD_ARGUMENT;       // (torch raises too: one value per channel)
     if (scratch_bytes < ctc_amd_head_forward_wide_scratch_bytes(T, B, K, C)) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (!ctc::head_wide_shape_ok(T, B, K, C) || (feat_stride_b & 3) != 0 || (feat_stride_t & 3) != 0 ||
-        (reinterpret_cast<uintptr_t>(feat) & 15) != 0 || (reinterpret_cast<uintptr_t>(weight) & 15) != 0)
+    if (!ctc::head_wide_shape_ok(T, B, K, C) || !ctc::head_feat_aligned(feat, feat_dtype, feat_stride_t, feat_stride_b) ||
+        (reinterpret_cast<uintptr_t>(weight) & 15) != 0)
         return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
     const ctc::HeadWideLayout L = ctc::head_wide_layout(T, B, C);
     char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(scratch) + ctc::kHeadBwdAlign - 1) /
@@ -294,12 +296,28 @@ extern "C" int ctc_amd_head_forward_wide(const float *feat, int64_t feat_stride_
     p.smean = save_mean; p.svar = save_var; p.sinv = save_invstd;
     int N, NG;
     ctc::head_wide_groups(C, N, NG);
-    int rc = N == 1   ? ctc::head_wide_launch_product<1>(p, psum, L, NG, st)
-             : N == 2 ? ctc::head_wide_launch_product<2>(p, psum, L, NG, st)
-                      : ctc::head_wide_launch_product<3>(p, psum, L, NG, st);
+    int rc = ctc::head_with_elem(feat_dtype, [&](auto e) {
+        using E = typename decltype(e)::type;
+        return N == 1   ? ctc::head_wide_launch_product<1, E>(p, psum, L, NG, st)
+               : N == 2 ? ctc::head_wide_launch_product<2, E>(p, psum, L, NG, st)
+                        : ctc::head_wide_launch_product<3, E>(p, psum, L, NG, st);
+    });
     if (rc || !train) return rc;
     return launch<ctc::head_wide_stats_kernel>(dim3(T, L.CP / 16), dim3(ctc::head_wide_block(B)), 0, st, p,
                                                (const float *)psum, L.CP, L.NB);
+}
+
+extern "C" int ctc_amd_head_forward_wide(const float *feat, int64_t feat_stride_t, int64_t feat_stride_b,
+                                         const float *weight, const float *bias, const float *bn_weight, const float *bn_bias,
+                                         const float *running_mean, const float *running_var, float eps, const float *mask,
+                                         int T, int B, int K, int C,
+                                         float *out, int64_t out_stride_t, int64_t out_stride_b,
+                                         float *linear_out, float *save_mean, float *save_var, float *save_invstd,
+                                         void *scratch, size_t scratch_bytes, void *stream)
+{
+    return ctc_amd_head_forward_wide_typed(feat, CTC_AMD_F32, feat_stride_t, feat_stride_b, weight, bias, bn_weight, bn_bias,
+                                           running_mean, running_var, eps, mask, T, B, K, C, out, out_stride_t, out_stride_b,
+                                           linear_out, save_mean, save_var, save_invstd, scratch, scratch_bytes, stream);
 }
 
 extern "C" size_t ctc_amd_head_backward_wide_scratch_bytes(int T, int B, int K, int C)
@@ -308,20 +326,21 @@ extern "C" size_t ctc_amd_head_backward_wide_scratch_bytes(int T, int B, int K, 
     return ctc::head_bwd_layout(T, B, K, C).total + ctc::kHeadBwdAlign;           // (the entry aligns the pointer itself)
 }
 
-// ctc_amd_head_backward for any batch up to kHeadWideMaxBatch: the walking row pass, then the narrow entry's products and
+// ctc_amd_head_backward(_typed) for any batch up to kHeadWideMaxBatch: the walking row pass, then the narrow entry's products and
 // reduce launches on the same scratch layout -- two launches, three when T B > 128.
-extern "C" int ctc_amd_head_backward_wide(const float *d_out, int64_t dout_stride_t, int64_t dout_stride_b,
-                                          const float *feat, int64_t feat_stride_t, int64_t feat_stride_b,
-                                          const float *weight, const float *bn_weight, const float *bn_bias,
-                                          const float *linear_out,
-                                          const float *save_mean, const float *save_invstd,
-                                          const float *running_mean, const float *running_var, float eps,
-                                          const float *mask,
-                                          int T, int B, int K, int C,
-                                          float *d_feat, int64_t dfeat_stride_t, int64_t dfeat_stride_b,
-                                          float *d_weight, float *d_bias, float *d_bn_weight, float *d_bn_bias,
-                                          void *scratch, size_t scratch_bytes, void *stream)
+extern "C" int ctc_amd_head_backward_wide_typed(const float *d_out, int64_t dout_stride_t, int64_t dout_stride_b,
+                                                const void *feat, int feat_dtype, int64_t feat_stride_t, int64_t feat_stride_b,
+                                                const float *weight, const float *bn_weight, const float *bn_bias,
+                                                const float *linear_out,
+                                                const float *save_mean, const float *save_invstd,
+                                                const float *running_mean, const float *running_var, float eps,
+                                                const float *mask,
+                                                int T, int B, int K, int C,
+                                                void *d_feat, int64_t dfeat_stride_t, int64_t dfeat_stride_b,
+                                                float *d_weight, float *d_bias, float *d_bn_weight, float *d_bn_bias,
+                                                void *scratch, size_t scratch_bytes, void *stream)
 {
+    if (feat_dtype != CTC_AMD_F32 && feat_dtype != CTC_AMD_BF16 && feat_dtype != CTC_AMD_F16) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (!d_out || !feat || !weight || !bn_weight || !bn_bias || !linear_out) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (!d_weight || !d_bias || !d_bn_weight || !d_bn_bias || !scratch) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (T < 1 || B < 1 || K < 1 || C < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
@@ -332,8 +351,8 @@ extern "C" int ctc_amd_head_backward_wide(const float *d_out, int64_t dout_strid
     if (dout_stride_b < C) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (d_feat && dfeat_stride_b < K) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (scratch_bytes < ctc_amd_head_backward_wide_scratch_bytes(T, B, K, C)) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (!ctc::head_wide_shape_ok(T, B, K, C) || (feat_stride_b & 3) != 0 || (feat_stride_t & 3) != 0 ||
-        (reinterpret_cast<uintptr_t>(feat) & 15) != 0 || (reinterpret_cast<uintptr_t>(weight) & 15) != 0)
+    if (!ctc::head_wide_shape_ok(T, B, K, C) || !ctc::head_feat_aligned(feat, feat_dtype, feat_stride_t, feat_stride_b) ||
+        (reinterpret_cast<uintptr_t>(weight) & 15) != 0 || (d_feat && !ctc::head_dfeat_aligned(d_feat, feat_dtype)))
         return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
     const ctc::HeadBwdLayout L = ctc::head_bwd_layout(T, B, K, C);
     char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(scratch) + ctc::kHeadBwdAlign - 1) /
@@ -365,9 +384,27 @@ extern "C" int ctc_amd_head_backward_wide(const float *d_out, int64_t dout_strid
     q.nF = d_feat ? (((int64_t)q.R + 15) / 16) * KQ : 0;
     q.nTail = (3 * (int64_t)L.CP + 63) / 64;
     const int64_t tasks = q.nW + q.nF + q.nTail;
-    rc = launch<ctc::head_bwd_products_kernel>(dim3((unsigned)((tasks + 3) / 4)), dim3(256), 0, st, q);
+    rc = ctc::head_bwd_launch_products(feat_dtype, tasks, st, q);
     if (rc || L.S == 1) return rc;
     const int64_t n = (int64_t)C * K;
     return launch<ctc::head_bwd_reduce_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
                                                (const float *)wpart, d_weight, n, L.S);
+}
+
+extern "C" int ctc_amd_head_backward_wide(const float *d_out, int64_t dout_stride_t, int64_t dout_stride_b,
+                                          const float *feat, int64_t feat_stride_t, int64_t feat_stride_b,
+                                          const float *weight, const float *bn_weight, const float *bn_bias,
+                                          const float *linear_out,
+                                          const float *save_mean, const float *save_invstd,
+                                          const float *running_mean, const float *running_var, float eps,
+                                          const float *mask,
+                                          int T, int B, int K, int C,
+                                          float *d_feat, int64_t dfeat_stride_t, int64_t dfeat_stride_b,
+                                          float *d_weight, float *d_bias, float *d_bn_weight, float *d_bn_bias,
+                                          void *scratch, size_t scratch_bytes, void *stream)
+{
+    return ctc_amd_head_backward_wide_typed(d_out, dout_stride_t, dout_stride_b, feat, CTC_AMD_F32, feat_stride_t, feat_stride_b,
+                                            weight, bn_weight, bn_bias, linear_out, save_mean, save_invstd, running_mean,
+                                            running_var, eps, mask, T, B, K, C, d_feat, dfeat_stride_t, dfeat_stride_b,
+                                            d_weight, d_bias, d_bn_weight, d_bn_bias, scratch, scratch_bytes, stream);
 }

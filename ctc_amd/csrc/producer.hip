@@ -432,7 +432,7 @@ extern "C" int ctc_amd_lstm_series_backward(const float *d_series, int64_t ds_st
 namespace ctc {
 
 struct HeadParams {
-    const float *feat;                                        // [T][B][K]
+    const void *feat;                                        // [T][B][K] of the kernel's element type E (strides in elements)
     int64_t fst, fsb;
     const float *w, *bias, *gamma, *beta;                    // Linear [C][K], [C]; BatchNorm weight / bias [C]
     const float *rmean, *rvar;                               // eval mode: running statistics; NULL: batch statistics
@@ -446,18 +446,62 @@ struct HeadParams {
 
 typedef float head_f4 __attribute__((ext_vector_type(4)));
 
+// The FEATURE operand's element type E: float, or the 2-byte __bf16 / _Float16 of a backbone under autocast, read as
+// it lies and widened to fp32 in registers -- bf16 by a 16-bit shift, fp16 by v_cvt_f32_f16 (exact, subnormals included: the
+// conversion makes normal fp32 numbers of them).  Everything behind the widening is the fp32 kernel's own code, so a 2-byte
+// launch gives the bits of the fp32 launch on feat.float().  Weights, statistics, the mask and every output stay fp32.
+// head_feat4: four consecutive elements -> fp32 (float: one 16-byte load; 2-byte E: one 8-byte load)
+template <typename E>
+__device__ __forceinline__ head_f4 head_feat4(const E *p)
+{
+    if constexpr (__is_same(E, float)) {
+        return *reinterpret_cast<const head_f4 *>(p);
+    } else {
+        typedef unsigned head_u2 __attribute__((ext_vector_type(2)));
+        const head_u2 u = *reinterpret_cast<const head_u2 *>(p);
+        if constexpr (__is_same(E, __bf16)) {
+            const head_f4 f = {__builtin_bit_cast(float, u.x << 16), __builtin_bit_cast(float, u.x & 0xffff0000u),
+                               __builtin_bit_cast(float, u.y << 16), __builtin_bit_cast(float, u.y & 0xffff0000u)};
+            return f;
+        } else {
+            typedef _Float16 head_h4 __attribute__((ext_vector_type(4)));
+            return __builtin_convertvector(__builtin_bit_cast(head_h4, u), head_f4);
+        }
+    }
+}
+
+// feat_dtype of the typed entries -> E
+template <typename E> struct HeadElem { using type = E; };
+template <typename F>
+inline int head_with_elem(int feat_dtype, F f)
+{
+    switch (feat_dtype) {
+    case CTC_AMD_F32: return f(HeadElem<float>{});
+    case CTC_AMD_BF16: return f(HeadElem<__bf16>{});
+    case CTC_AMD_F16: return f(HeadElem<_Float16>{});
+    default: return CTC_AMD_ERR_BAD_ARGUMENT;
+    }
+}
+
+// what the entries ask of the feature operand: 16-byte loads of fp32 rows, 8-byte loads of 2-byte rows (strides in elements)
+inline bool head_feat_aligned(const void *feat, int feat_dtype, int64_t stride_t, int64_t stride_b)
+{
+    const uintptr_t mask = feat_dtype == CTC_AMD_F32 ? 15 : 7;
+    return (stride_b & 3) == 0 && (stride_t & 3) == 0 && (reinterpret_cast<uintptr_t>(feat) & mask) == 0;
+}
+
 // The Linear product of one tile of 16 rows with N tiles of 16 columns (head_kernel: N = 1; lstm_forward_kernel: every
 // column tile of a row tile).  ap / bp[n]: this lane's feature row / weight rows, already advanced by 4 fq.  Every output
 // element is ONE fmaf chain over k in the order (kb, MFMA i, q) with k = 16 kb + 4 q + i, a zero second batch when the
 // count of 16-blocks is odd: whoever calls this gets the same bits for the same row, column and K.
-template <int N>
-__device__ __forceinline__ void head_dot(const float *ap, const float *const (&bp)[N], int KB, head_f4 (&acc)[N])
+template <int N, typename E>
+__device__ __forceinline__ void head_dot(const E *ap, const float *const (&bp)[N], int KB, head_f4 (&acc)[N])
 {
     const head_f4 zero = {0.f, 0.f, 0.f, 0.f};
-    for (int kb = 0; kb < KB; kb += 2) {                     // two batches of four MFMAs in flight (rows are 16-byte aligned: checked by the host)
+    for (int kb = 0; kb < KB; kb += 2) {                     // two batches of four MFMAs in flight (rows are 16-byte aligned, 8-byte for a 2-byte E: checked by the host)
         const bool two = kb + 1 < KB;
-        const head_f4 a0 = *reinterpret_cast<const head_f4 *>(ap + 16 * kb);
-        const head_f4 a1 = two ? *reinterpret_cast<const head_f4 *>(ap + 16 * kb + 16) : zero;
+        const head_f4 a0 = head_feat4(ap + 16 * kb);
+        const head_f4 a1 = two ? head_feat4(ap + 16 * kb + 16) : zero;
         head_f4 b0[N], b1[N];
 #pragma unroll
         for (int n = 0; n < N; ++n) {
@@ -509,6 +553,7 @@ __device__ __forceinline__ float head_column_total(float v, float (*red)[16], in
     return s;
 }
 
+template <typename E>
 __global__ __launch_bounds__(1024) void head_kernel(HeadParams p)
 {
     __shared__ float red[16][16];                            // [wave][column of the tile]
@@ -517,7 +562,7 @@ __global__ __launch_bounds__(1024) void head_kernel(HeadParams p)
     const int NW = blockDim.x >> 6;
     // operands: A row = batch row 16 w + fr, B row = output column 16 n + fr (clamped: the padding is masked out below)
     const int arow = min(16 * w + fr, p.B - 1), bcol = min(16 * n + fr, p.C - 1);
-    const float *ap = p.feat + (int64_t)t * p.fst + (int64_t)arow * p.fsb + 4 * fq;
+    const E *ap = static_cast<const E *>(p.feat) + (int64_t)t * p.fst + (int64_t)arow * p.fsb + 4 * fq;
     const float *bp = p.w + (int64_t)bcol * p.K + 4 * fq;
     const float *bps[1] = {bp};
     head_f4 accs[1] = {{0.f, 0.f, 0.f, 0.f}};
@@ -569,19 +614,20 @@ __global__ __launch_bounds__(1024) void head_kernel(HeadParams p)
 
 }  // namespace ctc
 
-extern "C" int ctc_amd_head_forward(const float *feat, int64_t feat_stride_t, int64_t feat_stride_b,
-                                    const float *weight, const float *bias, const float *bn_weight, const float *bn_bias,
-                                    const float *running_mean, const float *running_var, float eps, const float *mask,
-                                    int T, int B, int K, int C,
-                                    float *out, int64_t out_stride_t, int64_t out_stride_b,
-                                    float *linear_out, float *save_mean, float *save_var, float *save_invstd, void *stream)
+extern "C" int ctc_amd_head_forward_typed(const void *feat, int feat_dtype, int64_t feat_stride_t, int64_t feat_stride_b,
+                                          const float *weight, const float *bias, const float *bn_weight, const float *bn_bias,
+                                          const float *running_mean, const float *running_var, float eps, const float *mask,
+                                          int T, int B, int K, int C,
+                                          float *out, int64_t out_stride_t, int64_t out_stride_b,
+                                          float *linear_out, float *save_mean, float *save_var, float *save_invstd, void *stream)
 {
+    if (feat_dtype != CTC_AMD_F32 && feat_dtype != CTC_AMD_BF16 && feat_dtype != CTC_AMD_F16) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (!feat || !weight || !bias || !bn_weight || !bn_bias || !out) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (T < 1 || B < 1 || K < 1 || C < 1 || (running_mean == nullptr) != (running_var == nullptr)) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (out_stride_b < C) return CTC_AMD_ERR_BAD_ARGUMENT;
-    // one workgroup holds the B rows of a frame (BatchNorm's statistics); 16-byte operand loads
-    if (B > 256 || (K & 15) != 0 || (feat_stride_b & 3) != 0 || (feat_stride_t & 3) != 0 ||
-        (reinterpret_cast<uintptr_t>(feat) & 15) != 0 || (reinterpret_cast<uintptr_t>(weight) & 15) != 0)
+    // one workgroup holds the B rows of a frame (BatchNorm's statistics); 16-byte operand loads (8-byte: a 2-byte feat)
+    if (B > 256 || (K & 15) != 0 || !ctc::head_feat_aligned(feat, feat_dtype, feat_stride_t, feat_stride_b) ||
+        (reinterpret_cast<uintptr_t>(weight) & 15) != 0)
         return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
     if (running_mean == nullptr && B < 2) return CTC_AMD_ERR_BAD_ARGUMENT;       // (torch raises too: one value per channel)
     ctc::HeadParams p;
@@ -592,8 +638,23 @@ extern "C" int ctc_amd_head_forward(const float *feat, int64_t feat_stride_t, in
     p.out = out; p.ost = out_stride_t; p.osb = out_stride_b;
     p.lin = linear_out; p.smean = save_mean; p.svar = save_var; p.sinv = save_invstd;
     const int NW = (B + 15) / 16;
-    hipLaunchKernelGGL(ctc::head_kernel, dim3(T, (C + 15) / 16), dim3(64 * NW), 0, static_cast<hipStream_t>(stream), p);
-    return (int)hipGetLastError();
+    return ctc::head_with_elem(feat_dtype, [&](auto e) {
+        using E = typename decltype(e)::type;
+        hipLaunchKernelGGL(ctc::head_kernel<E>, dim3(T, (C + 15) / 16), dim3(64 * NW), 0, static_cast<hipStream_t>(stream), p);
+        return (int)hipGetLastError();
+    });
+}
+
+extern "C" int ctc_amd_head_forward(const float *feat, int64_t feat_stride_t, int64_t feat_stride_b,
+                                    const float *weight, const float *bias, const float *bn_weight, const float *bn_bias,
+                                    const float *running_mean, const float *running_var, float eps, const float *mask,
+                                    int T, int B, int K, int C,
+                                    float *out, int64_t out_stride_t, int64_t out_stride_b,
+                                    float *linear_out, float *save_mean, float *save_var, float *save_invstd, void *stream)
+{
+    return ctc_amd_head_forward_typed(feat, CTC_AMD_F32, feat_stride_t, feat_stride_b, weight, bias, bn_weight, bn_bias,
+                                      running_mean, running_var, eps, mask, T, B, K, C, out, out_stride_t, out_stride_b,
+                                      linear_out, save_mean, save_var, save_invstd, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -613,7 +674,7 @@ struct LstmForwardParams {
     LstmSeriesParams s;                                      // I = H = C; x unused
 };
 
-template <int N>
+template <int N, typename E>
 __device__ __forceinline__ void forward_head_phase(const HeadParams &p, float *vall, int b0, int ns)
 {
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, fr = lane & 15, fq = lane >> 4;
@@ -634,7 +695,7 @@ __device__ __forceinline__ void forward_head_phase(const HeadParams &p, float *v
         // A row 16 rt + fr = (frame, sample), clamped like arow / bcol of head_kernel: rows past the count are masked below
         const int row = 16 * rt + fr;
         const int t = min(row / kSeriesSamples, p.T - 1), s = min(row % kSeriesSamples, ns - 1);
-        const float *ap = p.feat + (int64_t)t * p.fst + (int64_t)(b0 + s) * p.fsb + 4 * fq;
+        const E *ap = static_cast<const E *>(p.feat) + (int64_t)t * p.fst + (int64_t)(b0 + s) * p.fsb + 4 * fq;
         head_f4 acc[N];
 #pragma unroll
         for (int n = 0; n < N; ++n) acc[n] = head_f4{0.f, 0.f, 0.f, 0.f};
@@ -654,6 +715,7 @@ __device__ __forceinline__ void forward_head_phase(const HeadParams &p, float *v
     }
 }
 
+template <typename E>
 __global__ __launch_bounds__(kLstmThreads) void lstm_forward_kernel(LstmForwardParams q)
 {
     static_assert(kSeriesSamples == 4, "a 16-row tile holds four frames of the workgroup's samples");
@@ -663,9 +725,9 @@ __global__ __launch_bounds__(kLstmThreads) void lstm_forward_kernel(LstmForwardP
     const SeriesLane L = series_lane(p, smem);
     float *vall = smem + series_smem_floats(p.I, p.H);       // [T][kSeriesSamples][C]: this workgroup's slice of the head's output
     const int C = q.h.C, CT = (C + 15) >> 4;                 // (2 C <= kSeriesK: at most three column tiles)
-    if (CT == 1) forward_head_phase<1>(q.h, vall, L.b0, L.ns);
-    else if (CT == 2) forward_head_phase<2>(q.h, vall, L.b0, L.ns);
-    else forward_head_phase<3>(q.h, vall, L.b0, L.ns);
+    if (CT == 1) forward_head_phase<1, E>(q.h, vall, L.b0, L.ns);
+    else if (CT == 2) forward_head_phase<2, E>(q.h, vall, L.b0, L.ns);
+    else forward_head_phase<3, E>(q.h, vall, L.b0, L.ns);
     float wr[kSeriesK];
     float bias;
     series_gate_row(p, L, wr, bias);
@@ -681,22 +743,23 @@ __global__ __launch_bounds__(kLstmThreads) void lstm_forward_kernel(LstmForwardP
 
 }  // namespace ctc
 
-extern "C" int ctc_amd_lstm_forward(const float *feat, int64_t feat_stride_t, int64_t feat_stride_b,
-                                    const float *weight, const float *bias, const float *bn_weight, const float *bn_bias,
-                                    const float *running_mean, const float *running_var, float eps,
-                                    const float *h0, const float *c0,
-                                    const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,
-                                    int T, int B, int K, int C,
-                                    float *series, int64_t series_stride_t, int64_t series_stride_b, int series_cols, float pad_value,
-                                    float *h_out, float *c_out, void *stream)
+extern "C" int ctc_amd_lstm_forward_typed(const void *feat, int feat_dtype, int64_t feat_stride_t, int64_t feat_stride_b,
+                                          const float *weight, const float *bias, const float *bn_weight, const float *bn_bias,
+                                          const float *running_mean, const float *running_var, float eps,
+                                          const float *h0, const float *c0,
+                                          const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,
+                                          int T, int B, int K, int C,
+                                          float *series, int64_t series_stride_t, int64_t series_stride_b, int series_cols,
+                                          float pad_value, float *h_out, float *c_out, void *stream)
 {
+    if (feat_dtype != CTC_AMD_F32 && feat_dtype != CTC_AMD_BF16 && feat_dtype != CTC_AMD_F16) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (!feat || !weight || !bias || !bn_weight || !bn_bias || !running_mean || !running_var) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (!h0 || !c0 || !w_ih || !w_hh || !b_ih || !b_hh || !series) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (T < 1 || B < 1 || K < 1 || C < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (series_cols < C || series_stride_b < series_cols) return CTC_AMD_ERR_BAD_ARGUMENT;
-    // the recurrence's sizes (I = H = C) and the head's 16-byte operand loads
-    if (2 * C > kSeriesK || 4 * C > kLstmThreads || (K & 15) != 0 || (feat_stride_b & 3) != 0 || (feat_stride_t & 3) != 0 ||
-        (reinterpret_cast<uintptr_t>(feat) & 15) != 0 || (reinterpret_cast<uintptr_t>(weight) & 15) != 0)
+    // the recurrence's sizes (I = H = C) and the head's 16-byte operand loads (8-byte: a 2-byte feat)
+    if (2 * C > kSeriesK || 4 * C > kLstmThreads || (K & 15) != 0 ||
+        !ctc::head_feat_aligned(feat, feat_dtype, feat_stride_t, feat_stride_b) || (reinterpret_cast<uintptr_t>(weight) & 15) != 0)
         return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
     // the workgroup's slice of the head's output, [T][4][C], next to the recurrence's staging
     const size_t smem = (series_smem_floats(C, C) + (size_t)kSeriesSamples * (size_t)T * (size_t)C) * sizeof(float);
@@ -711,8 +774,25 @@ extern "C" int ctc_amd_lstm_forward(const float *feat, int64_t feat_stride_t, in
     q.s.series = series; q.s.series_stride_t = series_stride_t; q.s.series_stride_b = series_stride_b;
     q.s.series_cols = series_cols; q.s.pad_value = pad_value;
     q.s.h_out = h_out; q.s.c_out = c_out;
-    return launch<lstm_forward_kernel>(dim3((B + kSeriesSamples - 1) / kSeriesSamples), dim3(kLstmThreads), smem,
-                                       static_cast<hipStream_t>(stream), q);
+    return ctc::head_with_elem(feat_dtype, [&](auto e) {
+        using E = typename decltype(e)::type;
+        return launch<lstm_forward_kernel<E>>(dim3((B + kSeriesSamples - 1) / kSeriesSamples), dim3(kLstmThreads), smem,
+                                              static_cast<hipStream_t>(stream), q);
+    });
+}
+
+extern "C" int ctc_amd_lstm_forward(const float *feat, int64_t feat_stride_t, int64_t feat_stride_b,
+                                    const float *weight, const float *bias, const float *bn_weight, const float *bn_bias,
+                                    const float *running_mean, const float *running_var, float eps,
+                                    const float *h0, const float *c0,
+                                    const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,
+                                    int T, int B, int K, int C,
+                                    float *series, int64_t series_stride_t, int64_t series_stride_b, int series_cols, float pad_value,
+                                    float *h_out, float *c_out, void *stream)
+{
+    return ctc_amd_lstm_forward_typed(feat, CTC_AMD_F32, feat_stride_t, feat_stride_b, weight, bias, bn_weight, bn_bias,
+                                      running_mean, running_var, eps, h0, c0, w_ih, w_hh, b_ih, b_hh, T, B, K, C,
+                                      series, series_stride_t, series_stride_b, series_cols, pad_value, h_out, c_out, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -848,18 +928,21 @@ __global__ __launch_bounds__(1024) void head_bwd_rows_kernel(HeadBwdRowsParams p
 
 struct HeadBwdProdParams {
     const float *dlin, *part;                                // as the rows launch left them
-    const float *feat;
+    const void *feat;                                        // of the kernel's element type E
     int64_t fst, fsb;
     const float *w;                                          // [C][K]
     int T, B, K, C, CP;
     int R, S, chunk;                                         // rows T B; row-range splits of the weight gradient
     float *dw;                                               // S == 1: d_weight [C][K]; else the partials [S][C][K]
-    float *dfeat;                                            // or NULL
+    void *dfeat;                                             // of E as well, or NULL
     int64_t gst, gsb;
     float *dbias, *dgamma, *dbeta;
     int64_t nW, nF, nTail;                                   // tasks of the three roles
 };
 
+// E: the element type of feat and d_feat.  The d_weight role widens feat exactly (bf16: a shift; fp16: v_cvt_f32_f16); the d_feat
+// role rounds its fp32 accumulator once, to nearest even.  float: the loads and stores as they were.
+template <typename E>
 __global__ __launch_bounds__(256) void head_bwd_products_kernel(HeadBwdProdParams p)
 {
     const int lane = threadIdx.x & 63, fr = lane & 15, fq = lane >> 4;
@@ -889,11 +972,11 @@ __global__ __launch_bounds__(256) void head_bwd_products_kernel(HeadBwdProdParam
                 const int rc = ok ? r : rend - 1;            // (an address inside the range; the value is dropped)
                 const int tt = rc / p.B, bb = rc - tt * p.B;
                 const float av = p.dlin[(int64_t)rc * p.CP + col];
-                const float *fp = p.feat + (int64_t)tt * p.fst + (int64_t)bb * p.fsb;
+                const E *fp = static_cast<const E *>(p.feat) + (int64_t)tt * p.fst + (int64_t)bb * p.fsb;
                 a[i] = ok ? av : 0.f;
 #pragma unroll
                 for (int n = 0; n < 4; ++n) {
-                    const float bv = fp[kc[n]];
+                    const float bv = (float)fp[kc[n]];
                     b[n][i] = ok ? bv : 0.f;
                 }
             }
@@ -954,11 +1037,11 @@ __global__ __launch_bounds__(256) void head_bwd_products_kernel(HeadBwdProdParam
             const int r = 16 * rt + 4 * fq + j;
             if (r >= p.R) continue;
             const int tt = r / p.B, bb = r - tt * p.B;
-            float *out = p.dfeat + (int64_t)tt * p.gst + (int64_t)bb * p.gsb;
+            E *out = static_cast<E *>(p.dfeat) + (int64_t)tt * p.gst + (int64_t)bb * p.gsb;
 #pragma unroll
             for (int n = 0; n < 4; ++n) {
                 const int k = 64 * kq + 16 * n + fr;
-                if (k < p.K) out[k] = acc[n][j];
+                if (k < p.K) out[k] = (E)acc[n][j];
             }
         }
         return;
@@ -995,18 +1078,38 @@ extern "C" size_t ctc_amd_head_backward_scratch_bytes(int T, int B, int K, int C
     return ctc::head_bwd_layout(T, B, K, C).total + ctc::kHeadBwdAlign;           // (the entry aligns the pointer itself)
 }
 
-extern "C" int ctc_amd_head_backward(const float *d_out, int64_t dout_stride_t, int64_t dout_stride_b,
-                                     const float *feat, int64_t feat_stride_t, int64_t feat_stride_b,
-                                     const float *weight, const float *bn_weight, const float *bn_bias,
-                                     const float *linear_out,
-                                     const float *save_mean, const float *save_invstd,
-                                     const float *running_mean, const float *running_var, float eps,
-                                     const float *mask,
-                                     int T, int B, int K, int C,
-                                     float *d_feat, int64_t dfeat_stride_t, int64_t dfeat_stride_b,
-                                     float *d_weight, float *d_bias, float *d_bn_weight, float *d_bn_bias,
-                                     void *scratch, size_t scratch_bytes, void *stream)
+namespace ctc {
+
+// d_feat of a 2-byte element type: 2-byte aligned (written with 2-byte stores); fp32 as the untyped entries take it
+inline bool head_dfeat_aligned(const void *d_feat, int feat_dtype)
 {
+    return feat_dtype == CTC_AMD_F32 || (reinterpret_cast<uintptr_t>(d_feat) & 1) == 0;
+}
+
+// the products launch of the head's backward on the element type of feat and d_feat
+inline int head_bwd_launch_products(int feat_dtype, int64_t tasks, hipStream_t st, const HeadBwdProdParams &q)
+{
+    return head_with_elem(feat_dtype, [&](auto e) {
+        using E = typename decltype(e)::type;
+        return launch<head_bwd_products_kernel<E>>(dim3((unsigned)((tasks + 3) / 4)), dim3(256), 0, st, q);
+    });
+}
+
+}  // namespace ctc
+
+extern "C" int ctc_amd_head_backward_typed(const float *d_out, int64_t dout_stride_t, int64_t dout_stride_b,
+                                           const void *feat, int feat_dtype, int64_t feat_stride_t, int64_t feat_stride_b,
+                                           const float *weight, const float *bn_weight, const float *bn_bias,
+                                           const float *linear_out,
+                                           const float *save_mean, const float *save_invstd,
+                                           const float *running_mean, const float *running_var, float eps,
+                                           const float *mask,
+                                           int T, int B, int K, int C,
+                                           void *d_feat, int64_t dfeat_stride_t, int64_t dfeat_stride_b,
+                                           float *d_weight, float *d_bias, float *d_bn_weight, float *d_bn_bias,
+                                           void *scratch, size_t scratch_bytes, void *stream)
+{
+    if (feat_dtype != CTC_AMD_F32 && feat_dtype != CTC_AMD_BF16 && feat_dtype != CTC_AMD_F16) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (!d_out || !feat || !weight || !bn_weight || !bn_bias || !linear_out) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (!d_weight || !d_bias || !d_bn_weight || !d_bn_bias || !scratch) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (T < 1 || B < 1 || K < 1 || C < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
@@ -1017,9 +1120,9 @@ extern "C" int ctc_amd_head_backward(const float *d_out, int64_t dout_stride_t, 
     if (dout_stride_b < C) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (d_feat && dfeat_stride_b < K) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (scratch_bytes < ctc_amd_head_backward_scratch_bytes(T, B, K, C)) return CTC_AMD_ERR_BAD_ARGUMENT;
-    // what ctc_amd_head_forward refuses, and row counts beyond the launches' index range
-    if (!ctc::head_bwd_shape_ok(T, B, K, C) || (feat_stride_b & 3) != 0 || (feat_stride_t & 3) != 0 ||
-        (reinterpret_cast<uintptr_t>(feat) & 15) != 0 || (reinterpret_cast<uintptr_t>(weight) & 15) != 0)
+    // what ctc_amd_head_forward(_typed) refuses, and row counts beyond the launches' index range
+    if (!ctc::head_bwd_shape_ok(T, B, K, C) || !ctc::head_feat_aligned(feat, feat_dtype, feat_stride_t, feat_stride_b) ||
+        (reinterpret_cast<uintptr_t>(weight) & 15) != 0 || (d_feat && !ctc::head_dfeat_aligned(d_feat, feat_dtype)))
         return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
     const ctc::HeadBwdLayout L = ctc::head_bwd_layout(T, B, K, C);
     char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(scratch) + ctc::kHeadBwdAlign - 1) /
@@ -1051,11 +1154,29 @@ extern "C" int ctc_amd_head_backward(const float *d_out, int64_t dout_stride_t, 
     q.nF = d_feat ? (((int64_t)q.R + 15) / 16) * KQ : 0;
     q.nTail = (3 * (int64_t)L.CP + 63) / 64;
     const int64_t tasks = q.nW + q.nF + q.nTail;
-    rc = launch<ctc::head_bwd_products_kernel>(dim3((unsigned)((tasks + 3) / 4)), dim3(256), 0, st, q);
+    rc = ctc::head_bwd_launch_products(feat_dtype, tasks, st, q);
     if (rc || L.S == 1) return rc;
     const int64_t n = (int64_t)C * K;
     return launch<ctc::head_bwd_reduce_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
                                                (const float *)wpart, d_weight, n, L.S);
+}
+
+extern "C" int ctc_amd_head_backward(const float *d_out, int64_t dout_stride_t, int64_t dout_stride_b,
+                                     const float *feat, int64_t feat_stride_t, int64_t feat_stride_b,
+                                     const float *weight, const float *bn_weight, const float *bn_bias,
+                                     const float *linear_out,
+                                     const float *save_mean, const float *save_invstd,
+                                     const float *running_mean, const float *running_var, float eps,
+                                     const float *mask,
+                                     int T, int B, int K, int C,
+                                     float *d_feat, int64_t dfeat_stride_t, int64_t dfeat_stride_b,
+                                     float *d_weight, float *d_bias, float *d_bn_weight, float *d_bn_bias,
+                                     void *scratch, size_t scratch_bytes, void *stream)
+{
+    return ctc_amd_head_backward_typed(d_out, dout_stride_t, dout_stride_b, feat, CTC_AMD_F32, feat_stride_t, feat_stride_b,
+                                       weight, bn_weight, bn_bias, linear_out, save_mean, save_invstd, running_mean, running_var,
+                                       eps, mask, T, B, K, C, d_feat, dfeat_stride_t, dfeat_stride_b,
+                                       d_weight, d_bias, d_bn_weight, d_bn_bias, scratch, scratch_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -41,6 +41,9 @@ eval mode bit for bit the narrow launch's; ``ctc_amd_head_backward_wide`` / ``he
 blocks of 256 rows, the products are the narrow entry's) for T B <= ``HEAD_WIDE_MAX_ROWS`` and T B <=
 ``HEAD_WIDE_BACKWARD_MAX_ROWS`` rows (measured, profiles/r18_head_wide.md: 0.70 ms against 6.41 ms for the train-mode head at
 T = 150, B = 2048, C = 33); beyond the first gate torch's layers run frame by frame, beyond the second ``_head_backward_torch``.
+A bf16 / fp16 ``feat`` (a backbone under ``torch.autocast``) is read natively by all five head entry points (the ``*_typed``
+entries, ``_feat_call``): no ``.float()``, no fp32 copy, every output fp32 and bit for bit that of ``feat.float()``, ``d_feat`` in
+``feat``'s dtype; no gate of its own (measured, profiles/r19_head_typed.md: below the cast path's minimum at every point).
 No CPU path: non-HIP tensors raise.
 """
 import torch
@@ -63,17 +66,47 @@ class BasicModule(nn.Module):
         return self.layers(x)
 
 
+_LOWP_FEAT = {torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
+
+
+def _feat_call(name, feat, pre, post):
+    """One head entry on ``feat`` [T,B,K] -> (return code, whether the typed entry ran).  ``pre`` / ``post``: the arguments in
+    front of and behind (feat, its strides); ``post`` is a function of that flag (the backward entries write d_feat in feat's
+    element type).  An fp32 ``feat`` goes to the entry ``name`` as before.  A bf16 / fp16 ``feat`` with unit last stride -- what a
+    backbone under ``torch.autocast`` hands over -- goes to ``name + "_typed"`` as it lies: no ``.float()``, no copy (DESIGN
+    3.6c).  When that entry answers UNSUPPORTED_SHAPE (a view that is not 8-byte aligned, a stride that is not a multiple of 4
+    elements; also what the fp32 entry refuses, which the second answer then repeats), and for every other dtype or layout, the
+    cast and the fp32 entry."""
+    lib = _lib.load()
+    code = _LOWP_FEAT.get(feat.dtype)
+    if code is not None and feat.stride(2) == 1:
+        rc = getattr(lib, name + "_typed")(*pre, feat.data_ptr(), code, feat.stride(0), feat.stride(1), *post(True))
+        if rc != _lib.ERR_UNSUPPORTED_SHAPE:
+            return rc, True
+    f = feat if (feat.dtype is torch.float32 and feat.stride(2) == 1) else feat.float().contiguous()
+    return getattr(lib, name)(*pre, f.data_ptr(), f.stride(0), f.stride(1), *post(False)), False
+
+
+def _dfeat_as(d_feat, feat):
+    """d_feat in the element type of a bf16 / fp16 ``feat`` (the typed entry wrote it so; behind the cast path the fp32 result is
+    rounded here, once, as autograd would round it at the module level)"""
+    if d_feat is None or feat.dtype not in _LOWP_FEAT or d_feat.dtype is feat.dtype:
+        return d_feat
+    return d_feat.to(feat.dtype)
+
+
 def head_forward(feat, weight, bias, bn_weight, bn_bias, running_mean=None, running_var=None, eps=1e-5, mask=None,
                  want_backward_state=False):
     """``dropout(relu(batchnorm(feat[t] @ weight.T + bias)))`` for every frame t in ONE launch (``ctc_amd_head_forward``)
     -> (out [T,B,C], lin [T,B,C] | None, mean [T,C] | None, var [T,C] | None, invstd [T,C] | None), or None when the launch
     does not take the shape (B > 256, K not a multiple of 16, unaligned rows).  running_mean / running_var: eval mode;
-    both None: the statistics of each frame's batch.  ``mask``: [T,B,C], already scaled by 1 / (1 - p)."""
+    both None: the statistics of each frame's batch.  ``mask``: [T,B,C], already scaled by 1 / (1 - p).  A bf16 / fp16 ``feat``
+    is read as it lies (``ctc_amd_head_forward_typed``, see ``_feat_call``): every result is fp32 and bit for bit that of
+    ``feat.float()``."""
     F._require_hip(feat, "feat")
     T, B, K = feat.shape
     C = weight.shape[0]
     dev = feat.device
-    f = feat if (feat.dtype is torch.float32 and feat.stride(2) == 1) else feat.float().contiguous()
     prm = [t if (t.dtype is torch.float32 and t.is_contiguous()) else t.float().contiguous()
            for t in (weight, bias, bn_weight, bn_bias)]
     rm = rv = None
@@ -88,9 +121,9 @@ def head_forward(feat, weight, bias, bn_weight, bn_bias, running_mean=None, runn
     inv = torch.empty((T, C), dtype=torch.float32, device=dev) if train else None
     ptr = lambda t: None if t is None else t.data_ptr()
     with F._on_device(dev):
-        rc = _lib.load().ctc_amd_head_forward(f.data_ptr(), f.stride(0), f.stride(1), *(t.data_ptr() for t in prm), ptr(rm), ptr(rv),
-                                              float(eps), ptr(mk), T, B, K, C, out.data_ptr(), out.stride(0), out.stride(1),
-                                              ptr(lin), ptr(mean), ptr(var), ptr(inv), F._stream_handle(dev))
+        rc, _ = _feat_call("ctc_amd_head_forward", feat, (), lambda typed: (
+            *(t.data_ptr() for t in prm), ptr(rm), ptr(rv), float(eps), ptr(mk), T, B, K, C, out.data_ptr(), out.stride(0),
+            out.stride(1), ptr(lin), ptr(mean), ptr(var), ptr(inv), F._stream_handle(dev)))
     if rc == _lib.ERR_UNSUPPORTED_SHAPE:
         return None
     if rc:
@@ -106,6 +139,10 @@ def head_backward(d_out, feat, weight, bn_weight, bn_bias, lin, mean=None, invst
     train mode: ``mean`` / ``invstd`` [T,C] as the forward saved them; eval mode: ``running_mean`` / ``running_var`` [C] and
     ``eps``; ``mask`` as the forward took it.  Deterministic (no atomics, fixed sum orders).
 
+    A bf16 / fp16 ``feat`` is read as it lies (``ctc_amd_head_backward_typed``, see ``_feat_call``) and ``d_feat`` comes back in
+    ``feat``'s dtype: the fp32 value rounded once to nearest even, which is what autograd makes of an fp32 gradient at the module
+    level anyway.  The four parameter gradients stay fp32, bit for bit those of ``feat.float()``.
+
     The scratch (dlin [T B, C padded to 16], the per-frame partial sums, the partial weight gradients) is one ``torch.empty``
     per call, not a cached buffer: torch's caching allocator hands the same block back without a device call once the shape has
     been seen, the stream ordering of the block is torch's own business that way, and under ``torch.cuda.graph`` capture the
@@ -117,7 +154,6 @@ def head_backward(d_out, feat, weight, bn_weight, bn_bias, lin, mean=None, invst
     dev = feat.device
     f32 = torch.float32
     do = d_out if (d_out.dtype is f32 and d_out.stride(2) == 1) else d_out.float().contiguous()
-    f = feat if (feat.dtype is f32 and feat.stride(2) == 1) else feat.float().contiguous()
     cont = lambda t: None if t is None else (t if (t.dtype is f32 and t.is_contiguous()) else t.float().contiguous())   # noqa: E731
     w, g, be, ln, mn, iv, rm, rv, mk = (cont(t) for t in (weight, bn_weight, bn_bias, lin, mean, invstd, running_mean,
                                                            running_var, mask))
@@ -126,21 +162,24 @@ def head_backward(d_out, feat, weight, bn_weight, bn_bias, lin, mean=None, invst
     if nbytes == 0 and min(T, B, K, C) >= 1:
         return None
     scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    d_feat = torch.empty((T, B, K), dtype=f32, device=dev) if need_dfeat else None
     d_weight = torch.empty((C, K), dtype=f32, device=dev)
     d_bias, d_gamma, d_beta = (torch.empty(C, dtype=f32, device=dev) for _ in range(3))
     ptr = lambda t: None if t is None else t.data_ptr()     # noqa: E731
+    d_feat = [None]
+
+    def behind_feat(typed):                                  # d_feat: feat's element type from the typed entry, fp32 from the other
+        if need_dfeat:
+            d_feat[0] = torch.empty((T, B, K), dtype=feat.dtype if typed else f32, device=dev)
+        return (w.data_ptr(), g.data_ptr(), be.data_ptr(), ln.data_ptr(), ptr(mn), ptr(iv), ptr(rm), ptr(rv), float(eps), ptr(mk),
+                T, B, K, C, ptr(d_feat[0]), B * K if need_dfeat else 0, K if need_dfeat else 0, d_weight.data_ptr(),
+                d_bias.data_ptr(), d_gamma.data_ptr(), d_beta.data_ptr(), scratch.data_ptr(), nbytes, F._stream_handle(dev))
     with F._on_device(dev):
-        rc = lib.ctc_amd_head_backward(do.data_ptr(), do.stride(0), do.stride(1), f.data_ptr(), f.stride(0), f.stride(1),
-                                       w.data_ptr(), g.data_ptr(), be.data_ptr(), ln.data_ptr(), ptr(mn), ptr(iv), ptr(rm), ptr(rv),
-                                       float(eps), ptr(mk), T, B, K, C, ptr(d_feat), B * K if need_dfeat else 0, K if need_dfeat else 0,
-                                       d_weight.data_ptr(), d_bias.data_ptr(), d_gamma.data_ptr(), d_beta.data_ptr(),
-                                       scratch.data_ptr(), nbytes, F._stream_handle(dev))
+        rc, _ = _feat_call("ctc_amd_head_backward", feat, (do.data_ptr(), do.stride(0), do.stride(1)), behind_feat)
     if rc == _lib.ERR_UNSUPPORTED_SHAPE:
         return None
     if rc:
         _lib.check(rc, "ctc_amd_head_backward")
-    return d_feat, d_weight, d_bias, d_gamma, d_beta
+    return _dfeat_as(d_feat[0], feat), d_weight, d_bias, d_gamma, d_beta
 
 
 def head_forward_wide(feat, weight, bias, bn_weight, bn_bias, running_mean=None, running_var=None, eps=1e-5, mask=None,
@@ -149,12 +188,12 @@ def head_forward_wide(feat, weight, bias, bn_weight, bn_bias, running_mean=None,
     entry too; one launch in eval mode, two in train mode -- a frame's rows no longer fit one workgroup, so BatchNorm's batch
     statistics cross workgroups at a kernel boundary): the same arguments, the same return value, or None when the entry does
     not take the shape (K not a multiple of 16, unaligned rows, T B > 2^22 rows, B > 65536).  The Linear output and all of eval
-    mode are bit for bit the narrow entry's.  The scratch is one ``torch.empty`` per call, as ``head_backward`` explains."""
+    mode are bit for bit the narrow entry's.  A bf16 / fp16 ``feat`` is read as it lies (``ctc_amd_head_forward_wide_typed``), as in
+    ``head_forward``.  The scratch is one ``torch.empty`` per call, as ``head_backward`` explains."""
     F._require_hip(feat, "feat")
     T, B, K = feat.shape
     C = weight.shape[0]
     dev = feat.device
-    f = feat if (feat.dtype is torch.float32 and feat.stride(2) == 1) else feat.float().contiguous()
     prm = [t if (t.dtype is torch.float32 and t.is_contiguous()) else t.float().contiguous()
            for t in (weight, bias, bn_weight, bn_bias)]
     rm = rv = None
@@ -174,10 +213,9 @@ def head_forward_wide(feat, weight, bias, bn_weight, bn_bias, running_mean=None,
     inv = torch.empty((T, C), dtype=torch.float32, device=dev) if train else None
     ptr = lambda t: None if t is None else t.data_ptr()     # noqa: E731
     with F._on_device(dev):
-        rc = lib.ctc_amd_head_forward_wide(f.data_ptr(), f.stride(0), f.stride(1), *(t.data_ptr() for t in prm), ptr(rm), ptr(rv),
-                                           float(eps), ptr(mk), T, B, K, C, out.data_ptr(), out.stride(0), out.stride(1),
-                                           ptr(lin), ptr(mean), ptr(var), ptr(inv), scratch.data_ptr(), nbytes,
-                                           F._stream_handle(dev))
+        rc, _ = _feat_call("ctc_amd_head_forward_wide", feat, (), lambda typed: (
+            *(t.data_ptr() for t in prm), ptr(rm), ptr(rv), float(eps), ptr(mk), T, B, K, C, out.data_ptr(), out.stride(0),
+            out.stride(1), ptr(lin), ptr(mean), ptr(var), ptr(inv), scratch.data_ptr(), nbytes, F._stream_handle(dev)))
     if rc == _lib.ERR_UNSUPPORTED_SHAPE:
         return None
     if rc:
@@ -190,7 +228,9 @@ def head_backward_wide(d_out, feat, weight, bn_weight, bn_bias, lin, mean=None, 
     """``head_backward`` for batches beyond 256 samples (``ctc_amd_head_backward_wide``: B up to 65536; the row pass walks a
     frame's blocks of 256 rows, the products and the reduce launch are the narrow entry's -- two launches, three when
     T B > 128): the same arguments, the same return value, or None when the entry does not take the shape (what
-    ``head_forward_wide`` refuses).  Deterministic.  The scratch is one ``torch.empty`` per call, as ``head_backward`` explains."""
+    ``head_forward_wide`` refuses).  Deterministic.  A bf16 / fp16 ``feat`` is read as it lies (``ctc_amd_head_backward_wide_typed``)
+    and ``d_feat`` comes back in ``feat``'s dtype, as in ``head_backward``.  The scratch is one ``torch.empty`` per call, as
+    ``head_backward`` explains."""
     F._require_hip(d_out, "d_out")
     F._require_hip(feat, "feat")
     T, B, K = feat.shape
@@ -198,7 +238,6 @@ def head_backward_wide(d_out, feat, weight, bn_weight, bn_bias, lin, mean=None, 
     dev = feat.device
     f32 = torch.float32
     do = d_out if (d_out.dtype is f32 and d_out.stride(2) == 1) else d_out.float().contiguous()
-    f = feat if (feat.dtype is f32 and feat.stride(2) == 1) else feat.float().contiguous()
     cont = lambda t: None if t is None else (t if (t.dtype is f32 and t.is_contiguous()) else t.float().contiguous())   # noqa: E731
     w, g, be, ln, mn, iv, rm, rv, mk = (cont(t) for t in (weight, bn_weight, bn_bias, lin, mean, invstd, running_mean,
                                                            running_var, mask))
@@ -207,21 +246,24 @@ def head_backward_wide(d_out, feat, weight, bn_weight, bn_bias, lin, mean=None, 
     if nbytes == 0 and min(T, B, K, C) >= 1:
         return None
     scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    d_feat = torch.empty((T, B, K), dtype=f32, device=dev) if need_dfeat else None
     d_weight = torch.empty((C, K), dtype=f32, device=dev)
     d_bias, d_gamma, d_beta = (torch.empty(C, dtype=f32, device=dev) for _ in range(3))
     ptr = lambda t: None if t is None else t.data_ptr()     # noqa: E731
+    d_feat = [None]
+
+    def behind_feat(typed):                                  # d_feat: feat's element type from the typed entry, fp32 from the other
+        if need_dfeat:
+            d_feat[0] = torch.empty((T, B, K), dtype=feat.dtype if typed else f32, device=dev)
+        return (w.data_ptr(), g.data_ptr(), be.data_ptr(), ln.data_ptr(), ptr(mn), ptr(iv), ptr(rm), ptr(rv), float(eps), ptr(mk),
+                T, B, K, C, ptr(d_feat[0]), B * K if need_dfeat else 0, K if need_dfeat else 0, d_weight.data_ptr(),
+                d_bias.data_ptr(), d_gamma.data_ptr(), d_beta.data_ptr(), scratch.data_ptr(), nbytes, F._stream_handle(dev))
     with F._on_device(dev):
-        rc = lib.ctc_amd_head_backward_wide(do.data_ptr(), do.stride(0), do.stride(1), f.data_ptr(), f.stride(0), f.stride(1),
-                                            w.data_ptr(), g.data_ptr(), be.data_ptr(), ln.data_ptr(), ptr(mn), ptr(iv), ptr(rm),
-                                            ptr(rv), float(eps), ptr(mk), T, B, K, C, ptr(d_feat), B * K if need_dfeat else 0,
-                                            K if need_dfeat else 0, d_weight.data_ptr(), d_bias.data_ptr(), d_gamma.data_ptr(),
-                                            d_beta.data_ptr(), scratch.data_ptr(), nbytes, F._stream_handle(dev))
+        rc, _ = _feat_call("ctc_amd_head_backward_wide", feat, (do.data_ptr(), do.stride(0), do.stride(1)), behind_feat)
     if rc == _lib.ERR_UNSUPPORTED_SHAPE:
         return None
     if rc:
         _lib.check(rc, "ctc_amd_head_backward_wide")
-    return d_feat, d_weight, d_bias, d_gamma, d_beta
+    return _dfeat_as(d_feat[0], feat), d_weight, d_bias, d_gamma, d_beta
 
 
 def _head_backward_torch(d_out, feat, weight, gamma, beta, lin, mean, inv, mask, train, need_dfeat):
@@ -510,22 +552,22 @@ def lstm_forward(feat, weight, bias, bn_weight, bn_bias, running_mean, running_v
                  cols=None, pad_value=PAD_LOGIT):
     """EVAL mode, no gradient: ``head_forward`` (running statistics, no mask) and ``lstm_series`` as ONE launch
     (``ctc_amd_lstm_forward``; the head's output stays in LDS) -> v_series [T,B,cols], bit-identical to the two launches, or
-    None when the launch does not take the shape (2 C > 80, K not a multiple of 16, unaligned rows, T C beyond the LDS)."""
+    None when the launch does not take the shape (2 C > 80, K not a multiple of 16, unaligned rows, T C beyond the LDS).  A bf16 /
+    fp16 ``feat`` is read as it lies (``ctc_amd_lstm_forward_typed``, see ``_feat_call``); v_series stays fp32, the same bits."""
     F._require_hip(feat, "feat")
     T, B, K = feat.shape
     C = weight.shape[0]
     cols = C if cols is None else int(cols)
     dev = feat.device
-    f = feat if (feat.dtype is torch.float32 and feat.stride(2) == 1) else feat.float().contiguous()
     args = [t if (t.dtype is torch.float32 and t.is_contiguous()) else t.float().contiguous()
             for t in (weight, bias, bn_weight, bn_bias, running_mean, running_var)]
     cell = [t if (t.dtype is torch.float32 and t.is_contiguous()) else t.float().contiguous()
             for t in (h0, c0, w_ih, w_hh, b_ih, b_hh)]
     series = torch.empty((T, B, cols), dtype=torch.float32, device=dev)
     with F._on_device(dev):
-        rc = _lib.load().ctc_amd_lstm_forward(f.data_ptr(), f.stride(0), f.stride(1), *(t.data_ptr() for t in args), float(eps),
-                                              *(t.data_ptr() for t in cell), T, B, K, C, series.data_ptr(), series.stride(0),
-                                              series.stride(1), cols, float(pad_value), None, None, F._stream_handle(dev))
+        rc, _ = _feat_call("ctc_amd_lstm_forward", feat, (), lambda typed: (
+            *(t.data_ptr() for t in args), float(eps), *(t.data_ptr() for t in cell), T, B, K, C, series.data_ptr(),
+            series.stride(0), series.stride(1), cols, float(pad_value), None, None, F._stream_handle(dev)))
     if rc == _lib.ERR_UNSUPPORTED_SHAPE:
         return None
     if rc:

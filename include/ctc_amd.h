@@ -674,6 +674,76 @@ int ctc_amd_head_backward_wide(const float *d_out, int64_t dout_stride_t, int64_
                                float *d_weight, float *d_bias, float *d_bn_weight, float *d_bn_bias,
                                void *scratch, size_t scratch_bytes, void *stream);
 
+/* The five head entries on a feature operand of element type `feat_dtype` (CTC_AMD_F32 / _BF16 / _F16, as
+ * ctc_amd_noblank_loss_grad_typed takes x): a backbone under autocast hands feat over in bf16 or fp16, and the launches read it
+ * as it lies instead of an fp32 copy.  Each entry is its untyped sibling with these changes only: feat is `const void *feat,
+ * int feat_dtype`; on the backward entries d_feat is `void *d_feat`, of feat's element type; the strides of both are in elements.
+ * CTC_AMD_F32 is exactly the untyped entry.  CTC_AMD_BF16 / CTC_AMD_F16: a lane's four features of a k-block are ONE 8-byte load,
+ * widened to fp32 in registers -- bf16 by a 16-bit shift, fp16 by the exact conversion (subnormals are not flushed) -- and fed to
+ * the fp32 launch's own v_mfma_f32_16x16x4_f32 chain in the fp32 launch's order (k is not re-tiled): every output of the forward
+ * entries and d_weight, d_bias, d_bn_weight, d_bn_bias are bit for bit what the untyped entry gives on the features converted to
+ * fp32, and d_feat is the untyped entry's fp32 value rounded once to nearest even.  Weights, bias, BatchNorm's parameters and
+ * statistics, the mask, linear_out and every other output stay fp32.  The scratch queries do not depend on the element type: the
+ * untyped entries' queries serve.  Same launches, same determinism, same safety under stream capture as the siblings.
+ * Errors: the sibling's, decided in the sibling's order before any HIP call, with these differences.
+ * CTC_AMD_ERR_BAD_ARGUMENT: also a feat_dtype that is none of the three.  CTC_AMD_ERR_UNSUPPORTED_SHAPE for the 2-byte types:
+ * the 16-byte rule on feat becomes an 8-byte rule -- feat not 8-byte aligned, a feat stride that is not a multiple of 4 elements,
+ * K not a multiple of 16 (the weight keeps its 16-byte rule) -- and a d_feat that is not 2-byte aligned (it is written with
+ * 2-byte stores; dfeat_stride_b < K stays CTC_AMD_ERR_BAD_ARGUMENT). */
+/* ctc_amd_head_forward on a typed feat */
+int ctc_amd_head_forward_typed(const void *feat, int feat_dtype, int64_t feat_stride_t, int64_t feat_stride_b,
+                               const float *weight, const float *bias, const float *bn_weight, const float *bn_bias,
+                               const float *running_mean, const float *running_var, float eps, const float *mask,
+                               int T, int B, int K, int C,
+                               float *out, int64_t out_stride_t, int64_t out_stride_b,
+                               float *linear_out, float *save_mean, float *save_var, float *save_invstd, void *stream);
+
+/* ctc_amd_head_forward_wide on a typed feat (only the product launch reads feat; scratch: ctc_amd_head_forward_wide_scratch_bytes) */
+int ctc_amd_head_forward_wide_typed(const void *feat, int feat_dtype, int64_t feat_stride_t, int64_t feat_stride_b,
+                                    const float *weight, const float *bias, const float *bn_weight, const float *bn_bias,
+                                    const float *running_mean, const float *running_var, float eps, const float *mask,
+                                    int T, int B, int K, int C,
+                                    float *out, int64_t out_stride_t, int64_t out_stride_b,
+                                    float *linear_out, float *save_mean, float *save_var, float *save_invstd,
+                                    void *scratch, size_t scratch_bytes, void *stream);
+
+/* ctc_amd_lstm_forward on a typed feat (v_series, h_out and c_out stay fp32) */
+int ctc_amd_lstm_forward_typed(const void *feat, int feat_dtype, int64_t feat_stride_t, int64_t feat_stride_b,
+                               const float *weight, const float *bias, const float *bn_weight, const float *bn_bias,
+                               const float *running_mean, const float *running_var, float eps,
+                               const float *h0, const float *c0,
+                               const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,
+                               int T, int B, int K, int C,
+                               float *series, int64_t series_stride_t, int64_t series_stride_b, int series_cols, float pad_value,
+                               float *h_out, float *c_out, void *stream);
+
+/* ctc_amd_head_backward on a typed feat; d_feat has feat's element type (scratch: ctc_amd_head_backward_scratch_bytes).  Only the
+ * products launch sees feat and d_feat: the row pass and the reduce launch are the untyped entry's. */
+int ctc_amd_head_backward_typed(const float *d_out, int64_t dout_stride_t, int64_t dout_stride_b,
+                                const void *feat, int feat_dtype, int64_t feat_stride_t, int64_t feat_stride_b,
+                                const float *weight, const float *bn_weight, const float *bn_bias,
+                                const float *linear_out,
+                                const float *save_mean, const float *save_invstd,
+                                const float *running_mean, const float *running_var, float eps,
+                                const float *mask,
+                                int T, int B, int K, int C,
+                                void *d_feat, int64_t dfeat_stride_t, int64_t dfeat_stride_b,
+                                float *d_weight, float *d_bias, float *d_bn_weight, float *d_bn_bias,
+                                void *scratch, size_t scratch_bytes, void *stream);
+
+/* ctc_amd_head_backward_wide on a typed feat; d_feat has feat's element type (scratch: ctc_amd_head_backward_wide_scratch_bytes) */
+int ctc_amd_head_backward_wide_typed(const float *d_out, int64_t dout_stride_t, int64_t dout_stride_b,
+                                     const void *feat, int feat_dtype, int64_t feat_stride_t, int64_t feat_stride_b,
+                                     const float *weight, const float *bn_weight, const float *bn_bias,
+                                     const float *linear_out,
+                                     const float *save_mean, const float *save_invstd,
+                                     const float *running_mean, const float *running_var, float eps,
+                                     const float *mask,
+                                     int T, int B, int K, int C,
+                                     void *d_feat, int64_t dfeat_stride_t, int64_t dfeat_stride_b,
+                                     float *d_weight, float *d_bias, float *d_bn_weight, float *d_bn_bias,
+                                     void *scratch, size_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
