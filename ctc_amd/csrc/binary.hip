@@ -69,6 +69,9 @@ static size_t binary_smem_bytes(int T, int SP, int S, int CP)
 //     v_log_f32 (1 - p is either 0 or >= 2^-24), which is good to ~1e-7 relative.
 __device__ __forceinline__ void bce_logs_fast(float x, float &p, float &lp, float &lq)
 {
+    // +-inf (t - n = NaN below) and +-1e30: p, log p, log(1 - p) are those of +-128.  Two selects, not v_med3_f32:
+    // a NaN logit stays NaN (and so does the loss)
+    x = x < -128.0f ? -128.0f : (x > 128.0f ? 128.0f : x);
     const float t = x * -kLog2e;
     const float n = __builtin_rintf(t);
     float r = __builtin_fmaf(x, -kLog2e, -t);                // rounding error of the product
@@ -82,9 +85,9 @@ __device__ __forceinline__ void bce_logs_fast(float x, float &p, float &lp, floa
 }
 
 // The same three quantities where no clamp can fire and 1 - p keeps its bits: |x| < 6 on every lane of the
-// wave (p in [2.5e-3, 1 - 2.5e-3]).  Three transcendentals and five plain operations instead of four and
+// wave (p in [2.5e-3, 1 - 2.5e-3]).  Four transcendentals and eight plain operations instead of four and
 // thirty (the selects, the exact exponential and the second logarithm of bce_logs_fast exist for the tails):
-//     e = exp(-x), p = 1/(1 + e), log p = -log(1 + e), log(1 - p) = log p - x.
+//     e = exp(-x), p = 1/(1 + e), log p = min(x, 0) - log(1 + exp(-|x|)), log(1 - p) = log p - x in that form.
 // log(1 - p) is exact here where the reference rounds 1 - fl(p) first: they differ by <= 2.4e-5 at |x| = 6,
 // 1e-6 of an emission after the mean over C -- the exact (float64) value is the closer one of the two.
 // gradient store: write-through while logits + gradient fit the memory-side cache, non-temporal beyond (common.hpp)
@@ -98,10 +101,13 @@ __device__ __forceinline__ void bin_store(float *p, float v)
 constexpr float kBceFastAbs = 6.0f;
 __device__ __forceinline__ void bce_logs_small(float x, float &p, float &lp, float &lq)
 {
-    const float s = 1.0f + __builtin_amdgcn_exp2f(x * -kLog2e);
-    p = __builtin_amdgcn_rcpf(s);
-    lp = __builtin_amdgcn_logf(s) * -kLn2;
-    lq = lp - x;
+    const float e = __builtin_amdgcn_exp2f(x * -kLog2e);
+    p = __builtin_amdgcn_rcpf(1.0f + e);
+    // w = log(1 + exp(-|x|)), its argument in [1, 2]: log p = min(x, 0) - w and log(1 - p) = -max(x, 0) - w cancel on
+    // neither side of 0 (log p - x did for x < 0, see binary_pipe_kernel, P1a)
+    const float w = __builtin_amdgcn_logf(1.0f + (x >= 0.f ? e : __builtin_amdgcn_rcpf(e))) * kLn2;
+    lp = fminf(x, 0.f) - w;
+    lq = -fmaxf(x, 0.f) - w;
 }
 // wave-uniform: every lane's |x| is small (NaN fails the test and takes the careful path)
 __device__ __forceinline__ bool bce_all_small(float x)
@@ -637,6 +643,7 @@ __device__ __forceinline__ void lattice_chain_fed(const float *em, float *out, f
 // bce_logs_fast, returning s = 1 + exp(-x) (the reciprocal of which is the library's sigmoid to <= 1 ulp)
 __device__ __forceinline__ void bce_logs_fast_s(float x, float &s, float &lp, float &lq)
 {
+    x = x < -128.0f ? -128.0f : (x > 128.0f ? 128.0f : x);   // (as bce_logs_fast: NaN stays NaN)
     const float t = x * -kLog2e;
     const float n = __builtin_rintf(t);
     float r = __builtin_fmaf(x, -kLog2e, -t);
@@ -789,11 +796,13 @@ __global__ __launch_bounds__(kBinThreads) void binary_pipe_kernel(BinaryParams p
     // ---------------- workers, P1a: the logs of the rows -> D image, Q ----------------
     // With s = 1 + exp(-x):  p = 1/s,  log p = -log s,  log(1 - p) = -log s - x,  d = log p - log(1 - p) = x.
     // Usual case, every element of the row in (-16, 6) (no clamp can fire, 1 - p keeps its bits):
-    //     Q = sum_c log(1 - p_c) = -ln2 * log2(prod_j s_j) - sum_j x_j  per lane (the product of <= 4 values
-    //     below 9e6 cannot overflow), one exponential per element and one logarithm per lane; the reciprocal
-    //     waits until the gradient.  log(1 - p) is exact here where the reference rounds 1 - fl(p) first (they
-    //     differ by <= 2.4e-5 at x = 6: 1e-6 of an emission after the mean over C -- the exact (float64) value is the
-    //     closer one); for x < 0 the cancellation in -log s - x costs <= 2e-6 absolute per element.
+    //     log(1 - p) = -max(x, 0) - log(1 + exp(-|x|)): the logarithm's argument lies in [1, 2] on either side of 0, so
+    //     nothing cancels (-log s - x did for x < 0: 7e-7 per element, which a trained model's emissions of -3e-3 per
+    //     frame do not forgive -- nll off by 2.2e-5 at T = 165).  exp(-|x|) is exp(-x) or its reciprocal.
+    //     Q = sum_c log(1 - p_c) = -ln2 * log2(prod_j (1 + exp(-|x_j|))) - sum_j max(x_j, 0)  per lane, one exponential
+    //     per element and one logarithm per lane; the reciprocal of s waits until the gradient.  log(1 - p) is exact
+    //     here where the reference rounds 1 - fl(p) first (they differ by <= 2.4e-5 at x = 6: 1e-6 of an emission after
+    //     the mean over C -- the exact (float64) value is the closer one).
     // Otherwise: bce_logs_fast per element (the reference's clamps and its rounding of 1 - p).
     unsigned slow = 0;                                       // bit 2g+side: that row took the careful path
 #pragma unroll
@@ -813,11 +822,11 @@ __global__ __launch_bounds__(kBinThreads) void binary_pipe_kernel(BinaryParams p
                     for (int j = 0; j < CH; ++j) {
                         const int c = lane + 64 * j;
                         const float xv = v[g][side][j];
-                        const float sv = 1.0f + __builtin_amdgcn_exp2f(xv * -kLog2e);
-                        v[g][side][j] = sv;
+                        const float ev = __builtin_amdgcn_exp2f(xv * -kLog2e);
+                        v[g][side][j] = 1.0f + ev;
                         const bool in = j < CH - 1 || c < p.C;          // (only the last chunk can pass C)
-                        prod *= in ? sv : 1.0f;
-                        sx += in ? xv : 0.f;
+                        prod *= in ? 1.0f + (xv >= 0.f ? ev : __builtin_amdgcn_rcpf(ev)) : 1.0f;   // 1 + exp(-|x|)
+                        sx += in ? fmaxf(xv, 0.f) : 0.f;
                         if (t >= 0 && (j < CH - 1 || c < PD)) sm.dimg[t * PD + c] = in ? xv : 0.f;   // zero K padding
                     }
                     ql = __builtin_fmaf(__builtin_amdgcn_logf(prod), -kLn2, -sx);

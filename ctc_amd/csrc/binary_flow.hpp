@@ -735,12 +735,18 @@ __global__ __launch_bounds__(kBinThreads) void binary_flow_kernel(BinaryParams p
 #ifdef CTC_X_FLOW_NOEXP                                      // (ablation: are the logs bound by their arithmetic or by the rows' arrival?)
                         const float sv = 1.0f + xv * xv;
 #else
-                        const float sv = 1.0f + __builtin_amdgcn_exp2f(xv * -kLog2e);
+                        const float ev = __builtin_amdgcn_exp2f(xv * -kLog2e);
+                        const float sv = 1.0f + ev;
 #endif
                         v[g][side][j] = sv;
                         const bool in = j < CH - 1 || c < p.C;          // (only the last chunk can pass C)
+#ifdef CTC_X_FLOW_NOEXP
                         prod *= in ? sv : 1.0f;
                         sx += in ? xv : 0.f;
+#else
+                        prod *= in ? 1.0f + (xv >= 0.f ? ev : __builtin_amdgcn_rcpf(ev)) : 1.0f;   // 1 + exp(-|x|)
+                        sx += in ? fmaxf(xv, 0.f) : 0.f;
+#endif
                         if (j < CH - 1 || c < PD) drow[64 * j] = in ? xv : 0.f;   // zero K padding
                     }
 #ifdef CTC_X_FLOW_NOEXP

@@ -23,6 +23,10 @@ constexpr int kWave = 64;
 // -inf) keeps every intermediate finite and the float32 roundings identical.
 constexpr float kNeg = -10000000000000.0f;
 constexpr float kInfeasible = 1.0e12f;   // nll above this <=> no alignment exists
+// A log-domain emission is stored no lower than this: a -inf logit on a label class (a masked vocabulary) is a cell of
+// probability 0 -- below every real value and below the sentinel, so a sample whose every alignment crosses one has
+// nll >= kInfeasible -- and the lattice stays free of -inf - (-inf).  It is the value a -1e30 pad logit gives anyway.
+constexpr float kMasked = -1.0e30f;
 
 // S lattice states over the 64 lanes of the chain's wave: K = 1, 2 or 4 per lane, S padded to a multiple of K.
 // K = 8 means S > 256, which no kernel takes.

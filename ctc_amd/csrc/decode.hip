@@ -110,7 +110,7 @@ __device__ __forceinline__ void noblank_emissions(const DecodeParams &p, float *
         for (int c = lane; c < p.C; c += kWave) s += fast_exp(row[c] - m);
         s = wave_sum(s);
         const float lsum = fast_log(s);
-        for (int l = lane; l < p.SP; l += kWave) em[t * p.SP + l] = (l < L) ? (row[lab[l]] - m) - lsum : kNeg;
+        for (int l = lane; l < p.SP; l += kWave) em[t * p.SP + l] = (l < L) ? fmaxf((row[lab[l]] - m) - lsum, kMasked) : kNeg;
     }
 }
 

@@ -104,7 +104,7 @@ __device__ __forceinline__ void token_spans_tail(const TokenSmem &sm, const Toke
 #pragma unroll
             for (int k = 0; k < K; ++k) {
                 const int l = lane + kWave * k;
-                v[k] = l < L ? sm.al[off + l] + sm.be[off + l] - sm.em[off + l] : -__builtin_inff();
+                v[k] = l < L ? cell_posterior_log(sm.al[off + l], sm.be[off + l], sm.em[off + l]) : -__builtin_inff();
                 m = fmaxf(m, v[k]);
             }
             m = wave_max(m);

@@ -94,6 +94,16 @@ __device__ __forceinline__ void lattice_chain(const float *em, float *out, float
     if (prog) { lds_order(); *prog = Tb; }
 }
 
+// log of the unnormalised posterior of one cell, alpha + beta' - e.  A masked cell (emission at the floor kMasked,
+// common.hpp) has none.  Without this select the sum is wrong whenever ONE of the two scans reaches the cell over a
+// sentinel path instead: measured on a sample with a -inf label class, al = -1e30 (fp32 has absorbed the rest of the
+// path), be' = -1e13 (no way on from here), em = -1e30 gives -1e30 - 1e13 + 1e30 = 0, the largest entry of its row,
+// and gamma = 1 on a cell of probability 0.
+__device__ __forceinline__ float cell_posterior_log(float al, float be, float em)
+{
+    return em > kMasked ? al + be - em : -__builtin_inff();
+}
+
 // Posterior row: gamma_t(l) = exp(alpha_t(l) + beta'_t(l) - e_t(l)) / sum_l' (same), written
 // over `be`.  Mathematically every row's normaliser equals exp(-nll); normalising per
 // row cancels the rounding error the two long fp32 scans share (11x smaller error at
@@ -110,7 +120,7 @@ __device__ __forceinline__ void posterior_row(const float *al, float *be, const 
     const int off = t * SP;
     if (SP <= kWave) {                                   // one label per lane: stay in registers
         const bool in = live && ll < L;
-        const float v = in ? al[off + ll] + be[off + ll] - em[off + ll] : -__builtin_inff();
+        const float v = in ? cell_posterior_log(al[off + ll], be[off + ll], em[off + ll]) : -__builtin_inff();
         const float m = group_reduce<true>(v, G);
         const float pexp = in ? fast_exp(v - m) : 0.f;
         const float s = group_reduce<false>(pexp, G);
@@ -118,16 +128,16 @@ __device__ __forceinline__ void posterior_row(const float *al, float *be, const 
     } else {
         float m = -__builtin_inff();
         if (live)
-            for (int l = ll; l < L; l += G) m = fmaxf(m, al[off + l] + be[off + l] - em[off + l]);
+            for (int l = ll; l < L; l += G) m = fmaxf(m, cell_posterior_log(al[off + l], be[off + l], em[off + l]));
         m = group_reduce<true>(m, G);
         float s = 0.f;
         if (live)
-            for (int l = ll; l < L; l += G) s += fast_exp(al[off + l] + be[off + l] - em[off + l] - m);
+            for (int l = ll; l < L; l += G) s += fast_exp(cell_posterior_log(al[off + l], be[off + l], em[off + l]) - m);
         s = group_reduce<false>(s, G);
         const float inv = 1.0f / s;
         if (live)
             for (int l = ll; l < SP; l += G)
-                be[off + l] = (l < L) ? fast_exp(al[off + l] + be[off + l] - em[off + l] - m) * inv : 0.f;
+                be[off + l] = (l < L) ? fast_exp(cell_posterior_log(al[off + l], be[off + l], em[off + l]) - m) * inv : 0.f;
     }
     if (FOLD && live)
         for (int l = ll; l < L; l += G)

@@ -282,7 +282,7 @@ __global__ __launch_bounds__(kThreads, DUAL ? 8 : 4) void noblank_pipelined_kern
             asm volatile("" : "+v"(rsrow[r]));               // keep it in a VGPR: 12 wave-uniform floats
                                                              // would spill the scalar file
             if (t >= 0 && t < Tb && lane < p.SP)             // (t: wave-uniform)
-                sm.em[t * p.SP + lane] = (lane < L) ? (xv[k] - m[k]) - lsum : kNeg;
+                sm.em[t * p.SP + lane] = (lane < L) ? fmaxf((xv[k] - m[k]) - lsum, kMasked) : kNeg;
             lds_order();
             if (lane == 0) sm.cnt[u] = r + 1;                // publishes the slot (same wave: in order)
         }
@@ -362,7 +362,6 @@ __global__ __launch_bounds__(kThreads, DUAL ? 8 : 4) void noblank_pipelined_kern
             lds_order();                                     // lattice rows are read only after the look
         }
         if (starved) raise_status(p.counter, kStatusNoblankStarved);
-        const float gsc = starved ? __builtin_nanf("") : gsc0;
         if (CTC_DIAG(p) < 0) stamp(p, 3 + (2 - gq));             // diagnostic: groups 2,1,0 -> slots 3,4,5
         // gamma_t = softmax_l(alpha_t + beta'_t - e_t): row-normalised posterior (lattice.hpp).
         // Any shift gives the same softmax; every row's log-normaliser equals -nll up to the
@@ -379,7 +378,7 @@ __global__ __launch_bounds__(kThreads, DUAL ? 8 : 4) void noblank_pipelined_kern
                 tl[q] = upper ? tt[2 * q + 1] : tt[2 * q];
                 lvl[q] = tl[q] >= 0 && tl[q] < Tlive;        // per half
                 const int off = (lvl[q] ? tl[q] : 0) * p.SP + hcl;
-                const float zz = sm.al[off] + sm.be[off] - sm.em[off];
+                const float zz = cell_posterior_log(sm.al[off], sm.be[off], sm.em[off]);
                 zp[q] = (hl < L && lvl[q]) ? zz : ninf;
                 pp[q] = zp[q];
             }
@@ -390,6 +389,8 @@ __global__ __launch_bounds__(kThreads, DUAL ? 8 : 4) void noblank_pipelined_kern
                 shift = mx;
                 have_shift = true;
             }
+            const float gsc = starved ? __builtin_nanf("") : gsc0;
+            const bool dead = shift < -kInfeasible;              // (wave-uniform) no alignment: see the dense rows below
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 pp[q] = __builtin_amdgcn_exp2f((pp[q] - shift) * kLog2e);    // exp2(-inf) = 0 beyond L
@@ -400,7 +401,7 @@ __global__ __launch_bounds__(kThreads, DUAL ? 8 : 4) void noblank_pipelined_kern
             for (int q = 0; q < 2; ++q) {
                 const int off = (lvl[q] ? tl[q] : 0) * p.SP;
                 // gamma * grad_scale goes to LDS, so the dense row is one fma and one subtract
-                if (lvl[q] && hl < p.SP) sm.be[off + hl] = pp[q] * (gsc * __builtin_amdgcn_rcpf(zp[q]));
+                if (lvl[q] && hl < p.SP) sm.be[off + hl] = dead ? 0.f : pp[q] * (gsc * __builtin_amdgcn_rcpf(zp[q]));
                 if (any_dup && lvl[q] && my_dup_h) {         // fold repeats onto the first occurrence
                     float tot = sm.be[off + hl];
                     for (int n = sm.nxt[hl]; n >= 0; n = sm.nxt[n]) tot += sm.be[off + n];
@@ -413,7 +414,7 @@ __global__ __launch_bounds__(kThreads, DUAL ? 8 : 4) void noblank_pipelined_kern
             for (int k = 0; k < kGroup; ++k) {
                 const bool lv = tt[k] >= 0 && tt[k] < Tlive;       // wave-uniform; idle slots read row 0 and
                 const int off = (lv ? tt[k] : 0) * p.SP + lcl;     // are masked (row 0 may not exist yet)
-                const float zz = sm.al[off] + sm.be[off] - sm.em[off];
+                const float zz = cell_posterior_log(sm.al[off], sm.be[off], sm.em[off]);
                 z[k] = (in && lv) ? zz : ninf;
                 pe[k] = z[k];
             }
@@ -422,6 +423,8 @@ __global__ __launch_bounds__(kThreads, DUAL ? 8 : 4) void noblank_pipelined_kern
                 shift = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));     // idle slots contribute -inf
                 have_shift = true;
             }
+            const float gsc = starved ? __builtin_nanf("") : gsc0;
+            const bool dead = shift < -kInfeasible;              // (wave-uniform) no alignment: see the dense rows below
 #pragma unroll
             for (int k = 0; k < kGroup; ++k) {
                 pe[k] = __builtin_amdgcn_exp2f((pe[k] - shift) * kLog2e);    // exp2(-inf) = 0 beyond L
@@ -433,7 +436,7 @@ __global__ __launch_bounds__(kThreads, DUAL ? 8 : 4) void noblank_pipelined_kern
                 const int t = tt[k];
                 if (t < 0 || t >= Tlive) continue;           // wave-uniform
                 const int off = t * p.SP;
-                if (lane < p.SP) sm.be[off + lane] = pe[k] * (gsc * __builtin_amdgcn_rcpf(z[k]));
+                if (lane < p.SP) sm.be[off + lane] = dead ? 0.f : pe[k] * (gsc * __builtin_amdgcn_rcpf(z[k]));
                 if (any_dup && my_dup) {
                     float tot = sm.be[off + lane];
                     for (int n = sm.nxt[lane]; n >= 0; n = sm.nxt[n]) tot += sm.be[off + n];
@@ -456,11 +459,14 @@ __global__ __launch_bounds__(kThreads, DUAL ? 8 : 4) void noblank_pipelined_kern
                 continue;
             }
             const int off = t * p.SP;
+            // every row's log-normaliser is -nll: below the threshold no alignment exists (through the emissions alone:
+            // every path crosses a masked cell) and the sample's rows are zero rows, as those of a sample with L_b > T_b
+            const float rsr = shift < -kInfeasible ? 0.f : rsrow[r];
 #pragma unroll
             for (int j = 0; j < CH; ++j) {
                 const int c = lane + 64 * j;
                 const float occ = sm.be[off + first[j]];
-                const float gv = __builtin_fmaf(v[r][j], rsrow[r], has[j] ? -occ : 0.f);
+                const float gv = __builtin_fmaf(v[r][j], rsr, has[j] ? -occ : 0.f);
                 if (j < CH - 1 || c < p.C) stream_store(&g[c], gv);
             }
         }

@@ -894,7 +894,8 @@ __global__ __launch_bounds__(kThreads, 4) void noblank_r16_kernel(NoblankParams 
                 const float ec = (xv[s] - m) * kLog2e;
                 const float e2 = fmaxf(smooth ? p.ls_a * ec : ec, kXrMinLog2);
                 const float fl = __builtin_floorf(e2);
-                const float pm = __builtin_amdgcn_exp2f(e2 - fl);
+                // (an emission at the clamp -- a -inf or pad logit on a label class -- keeps the clamp's exponent and carries no mass)
+                const float pm = e2 > kXrMinLog2 ? __builtin_amdgcn_exp2f(e2 - fl) : 0.f;
                 cell_t *dst = (live && lst[s] < p.SP) ? sm.em + lst[s] * sm.TP + t : spare_w;
                 *dst = own[s] ? make_cell(pm, (int)fl) : zero;
             }
@@ -1069,7 +1070,7 @@ __global__ __launch_bounds__(kThreads, 4) void noblank_r16_kernel(NoblankParams 
             const bool in = live && own[s];
             const int off = crow[s] + (t > 0 ? t : 0);       // a valid address, masked afterwards
             const cell_t a = sm.al[off], bb = sm.be[off], e = sm.em[off];
-            pr[s] = in ? a.x * bb.x * __builtin_amdgcn_rcpf(e.x) : 0.f;
+            pr[s] = (in && e.x > 0.f) ? a.x * bb.x * __builtin_amdgcn_rcpf(e.x) : 0.f;    // (a cell without mass: 0, not 0 / 0)
             ks[s] = cell_k(a) + cell_k(bb) - cell_k(e);
         }
         if (__builtin_amdgcn_ballot_w64(live && !have_ref) != 0) {   // (wave-uniform branch)
@@ -1112,8 +1113,10 @@ __global__ __launch_bounds__(kThreads, 4) void noblank_r16_kernel(NoblankParams 
         // dense rows: grad = softmax(x) * scale - occupancy   (dead rows: scale = occupancy = 0)
         if (t >= 0) {
             E *gp = grow[g];
-            if (smooth) x.template store_grad<NT, true>(gp, trow, i16, rs[g] * (1.f - p.ls_b), col_ok, live ? -p.ls_b * gsc : 0.f);
-            else x.template store_grad<NT, false>(gp, trow, i16, rs[g], col_ok, 0.f);
+            // a live row without mass: no alignment exists (through the emissions alone) -- a zero row, as a dead one
+            const bool mass = !live || tot > 0.f;
+            if (smooth) x.template store_grad<NT, true>(gp, trow, i16, mass ? rs[g] * (1.f - p.ls_b) : 0.f, col_ok, live && mass ? -p.ls_b * gsc : 0.f);
+            else x.template store_grad<NT, false>(gp, trow, i16, mass ? rs[g] : 0.f, col_ok, 0.f);
         }
         lds_order();
         // the tile is all zeros again: the label slots, not three 16-byte stores per lane (an LDS store costs the wave

@@ -322,7 +322,8 @@ __global__ __launch_bounds__(kThreads, DUAL ? 8 : 4) void noblank_xr_kernel(Nobl
             // emission e = log_softmax(x)[lab_l] in log2 units, split into 2^floor * 2^frac
             const float e2 = fmaxf(__builtin_fmaf(xv[k] - m[k], kLog2e, -l2sum), kXrMinLog2);
             const float fl = __builtin_floorf(e2);
-            const float pm = __builtin_amdgcn_exp2f(e2 - fl);
+            // (an emission at the clamp -- a -inf or pad logit on a label class -- keeps the clamp's exponent and carries no mass)
+            const float pm = e2 > kXrMinLog2 ? __builtin_amdgcn_exp2f(e2 - fl) : 0.f;
             if (t >= 0 && t < Tb && lane < p.SP)             // (t: wave-uniform)
                 sm.em[t * p.SP + lane] = (lane < L) ? make_cell(pm, (int)fl) : zero;
             lds_order();
@@ -373,6 +374,7 @@ __global__ __launch_bounds__(kThreads, DUAL ? 8 : 4) void noblank_xr_kernel(Nobl
     const float gsc0 = p.grad_scale;
     int shiftk = 0;                                          // shared exponent shift of the posterior rows
     bool have_shift = false;
+    bool massless = false;                                   // no cell of the first group carries mass: no alignment exists
     const bool pair = p.SP <= 32;
     const bool upper = lane >= 32;
     const int hl = lane & 31, hcl = hl < p.SP ? hl : 0;
@@ -425,6 +427,7 @@ __global__ __launch_bounds__(kThreads, DUAL ? 8 : 4) void noblank_xr_kernel(Nobl
                 float mx = fmaxf(e0, e1);
                 mx = fmaxf(mx, __shfl_xor(mx, 32, kWave));
                 shiftk = mx > ninf ? (int)mx : 0;
+                massless = !(mx > ninf);
                 have_shift = true;
             }
 #pragma unroll
@@ -436,7 +439,7 @@ __global__ __launch_bounds__(kThreads, DUAL ? 8 : 4) void noblank_xr_kernel(Nobl
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 float *gr = sm.grow(lvl[q] ? tl[q] : 0, p.SP);
-                if (lvl[q] && hl < p.SP) gr[hl] = pr[q] * (gsc * __builtin_amdgcn_rcpf(z[q]));
+                if (lvl[q] && hl < p.SP) gr[hl] = massless ? 0.f : pr[q] * (gsc * __builtin_amdgcn_rcpf(z[q]));
                 if (any_dup && lvl[q] && my_dup_h) {
                     float tot = gr[hl];
                     for (int n = sm.nxt[hl]; n >= 0; n = sm.nxt[n]) tot += gr[n];
@@ -462,6 +465,7 @@ __global__ __launch_bounds__(kThreads, DUAL ? 8 : 4) void noblank_xr_kernel(Nobl
                 wave_max4(e[0], e[1], e[2], e[3]);
                 const float mx = fmaxf(fmaxf(e[0], e[1]), fmaxf(e[2], e[3]));
                 shiftk = mx > ninf ? (int)mx : 0;
+                massless = !(mx > ninf);
                 have_shift = true;
             }
 #pragma unroll
@@ -475,7 +479,7 @@ __global__ __launch_bounds__(kThreads, DUAL ? 8 : 4) void noblank_xr_kernel(Nobl
                 const int t = tt[k];
                 if (t < 0 || t >= Tlive) continue;
                 float *gr = sm.grow(t, p.SP);
-                if (lane < p.SP) gr[lane] = pr[k] * (gsc * __builtin_amdgcn_rcpf(z[k]));
+                if (lane < p.SP) gr[lane] = massless ? 0.f : pr[k] * (gsc * __builtin_amdgcn_rcpf(z[k]));
                 if (any_dup && my_dup) {
                     float tot = gr[lane];
                     for (int n = sm.nxt[lane]; n >= 0; n = sm.nxt[n]) tot += gr[n];
@@ -497,7 +501,9 @@ __global__ __launch_bounds__(kThreads, DUAL ? 8 : 4) void noblank_xr_kernel(Nobl
                 continue;
             }
             const float *gr = sm.grow(t, p.SP);
-            const float rsr = DUAL ? rs_lds[r] : rsrow[r];
+            // (every row's total is P(x, labels): without mass no alignment exists, through the emissions alone, and the
+            // sample's rows are zero rows, as those of a sample with L_b > T_b)
+            const float rsr = massless ? 0.f : (DUAL ? rs_lds[r] : rsrow[r]);
 #pragma unroll
             for (int j = 0; j < CH; ++j) {
                 const int c = lane + 64 * j;

@@ -69,6 +69,14 @@ size_t ctc_amd_workspace_bytes(int variant, int T, int B, int C, int S);
  *   grad     [T,B,C] contiguous out, or NULL for a forward-only call:
  *            grad_scale * (softmax(x)[t,b,c] - sum_{l<L_b, lab[b,l]=c} gamma_t(l)),
  *            exactly 0 for t >= T_b and for samples with no alignment
+ * -inf logits are allowed (a masked vocabulary), also on a label class: such a cell has probability 0, its gamma and
+ * the gradient at the -inf entry are exactly 0.  A logit of -1e30 (the producer's pad value) on a label class counts the
+ * same.  A sample is without an alignment when L_b > T_b or when every alignment crosses such a cell: nll >= 1e12, all
+ * of its gradient rows exactly 0.  Which value >= 1e12 depends on the kernel the shape gets: the 1e13 sentinel, a
+ * multiple of it, or the masked magnitude (about 1e30 times the cells crossed); callers test nll >= 1e12 (+inf passes
+ * that test too, and the token spans report +inf).  The read-outs (best path, posteriors, token spans) follow the same
+ * rule; the binary variant takes +-inf logits (p exactly 0 or 1, gradient exactly 0 there).  Outside the contract: a
+ * live row whose logits are ALL -inf (its softmax is 0/0: NaN) and NaN logits (the loss is then NaN).
  */
 int ctc_amd_noblank_loss_grad(const float *x, int64_t stride_t, int64_t stride_b,
                               const void *labels, int labels_i64,
