@@ -96,6 +96,18 @@ PROTOTYPES = {
                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ctc_amd_blank_token_spans": (_int, [_vp, _i64, _i64, _vp, _int, _vp, _vp, _int, _int, _int, _int, _int,
                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the no-blank / binary read-outs on typed logits: the sibling's list with `int x_dtype` behind the x pointer
+    "ctc_amd_noblank_best_path_typed": (_int, [_vp, _int, _i64, _i64, _vp, _int, _vp, _vp, _int, _int, _int, _int,
+                                               _vp, _vp, _vp, _vp]),
+    "ctc_amd_binary_best_path_typed": (_int, [_vp, _int, _i64, _i64, _vp, _vp, _vp, _int, _int, _int, _int, _vp, _vp, _vp, _vp]),
+    "ctc_amd_noblank_posteriors_typed": (_int, [_vp, _int, _i64, _i64, _vp, _int, _vp, _vp, _int, _int, _int, _int,
+                                                _vp, _vp, _vp, _vp]),
+    "ctc_amd_binary_posteriors_typed": (_int, [_vp, _int, _i64, _i64, _vp, _vp, _vp, _int, _int, _int, _int, _vp, _vp, _vp,
+                                               _vp]),
+    "ctc_amd_noblank_token_spans_typed": (_int, [_vp, _int, _i64, _i64, _vp, _int, _vp, _vp, _int, _int, _int, _int,
+                                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ctc_amd_binary_token_spans_typed": (_int, [_vp, _int, _i64, _i64, _vp, _vp, _vp, _int, _int, _int, _int,
+                                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -681,9 +681,12 @@ __device__ __forceinline__ void bin_store_col(float *row, unsigned voff, int j, 
     }
 }
 
-template <int CH, bool WT, bool GAMMA = false>               // GAMMA: the posteriors-only instantiation (ctc_amd_binary_posteriors)
+// GAMMA: the posteriors-only instantiation (ctc_amd_binary_posteriors), which alone also takes 2-byte logits: E is the element
+// type behind p.x (float, __bf16, _Float16) and only decides how logit_f32 brings a logit into its fp32 register
+template <int CH, bool WT, bool GAMMA = false, typename E = float>
 __global__ __launch_bounds__(kBinThreads) void binary_pipe_kernel(BinaryParams p, int PD)
 {
+    static_assert(GAMMA || __is_same(E, float), "the binary loss reads fp32 logits");
     extern __shared__ float4 smem_raw[];
     const BinaryPipeSmem sm(reinterpret_cast<float *>(smem_raw), p.T, p.SP, PD);
     const int b = xcd_sample(blockIdx.x, p.B), tid = threadIdx.x, w = wave_id(), lane = lane_id();
@@ -713,11 +716,11 @@ __global__ __launch_bounds__(kBinThreads) void binary_pipe_kernel(BinaryParams p
 #pragma unroll
                 for (int side = 0; side < 2; ++side) {
                     const int t = slot_row(g, side);
-                    const float *row = p.x + (int64_t)(t >= 0 ? t : 0) * p.st + (int64_t)b * p.sb;
+                    const E *row = reinterpret_cast<const E *>(p.x) + (int64_t)(t >= 0 ? t : 0) * p.st + (int64_t)b * p.sb;
 #pragma unroll
                     for (int j = 0; j < CH; ++j) {
                         const int c = lane + 64 * j;
-                        v[g][side][j] = row[c < p.C ? c : p.C - 1];
+                        v[g][side][j] = logit_f32(row + (c < p.C ? c : p.C - 1));
                     }
                 }
             }
@@ -1102,15 +1105,15 @@ static int binary_image_pitch(int C)
     return PD;
 }
 
-template <bool WT, bool GAMMA = false>
+template <bool WT, bool GAMMA = false, typename E = float>
 static int launch_binary_pipe_wt(int ch, size_t smem, hipStream_t s, const BinaryParams &p, int PD)
 {
     const dim3 grid(p.B), block(kBinThreads);
     switch (ch) {
-        case 1: return launch<binary_pipe_kernel<1, WT, GAMMA>>(grid, block, smem, s, p, PD);
-        case 2: return launch<binary_pipe_kernel<2, WT, GAMMA>>(grid, block, smem, s, p, PD);
-        case 3: return launch<binary_pipe_kernel<3, WT, GAMMA>>(grid, block, smem, s, p, PD);
-        default: return launch<binary_pipe_kernel<4, WT, GAMMA>>(grid, block, smem, s, p, PD);
+        case 1: return launch<binary_pipe_kernel<1, WT, GAMMA, E>>(grid, block, smem, s, p, PD);
+        case 2: return launch<binary_pipe_kernel<2, WT, GAMMA, E>>(grid, block, smem, s, p, PD);
+        case 3: return launch<binary_pipe_kernel<3, WT, GAMMA, E>>(grid, block, smem, s, p, PD);
+        default: return launch<binary_pipe_kernel<4, WT, GAMMA, E>>(grid, block, smem, s, p, PD);
     }
 }
 
@@ -1207,15 +1210,17 @@ extern "C" int ctc_amd_binary_loss_grad(const float *x, int64_t stride_t, int64_
 // Per-step posteriors of the binary lattice: gamma[b,t,l] = P(label row l at step t | x, targets), the
 // quantity the loss gradient contracts with the target rows -- it falls out of the pipelined kernel's gradient phase.
 // Shapes of that kernel only (S <= 64, T <= 168, C <= 256, images within LDS); others: CTC_AMD_ERR_UNSUPPORTED_SHAPE.
-extern "C" int ctc_amd_binary_posteriors(const float *x, int64_t stride_t, int64_t stride_b, const float *y,
-                                         const int64_t *in_len, const int64_t *tgt_len, int T, int B, int C, int S,
-                                         float *nll, float *gamma, void *workspace, void *stream)
+static int binary_posteriors_entry(const void *x, int x_dtype, int64_t stride_t, int64_t stride_b, const float *y,
+                                   const int64_t *in_len, const int64_t *tgt_len, int T, int B, int C, int S,
+                                   float *nll, float *gamma, void *workspace, void *stream)
 {
+    if (x_dtype != CTC_AMD_F32 && x_dtype != CTC_AMD_BF16 && x_dtype != CTC_AMD_F16) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (!x || !y || !in_len || !tgt_len || !nll || !gamma || !workspace) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (T < 1 || B < 1 || C < 1 || S < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (S > kWave || T > kPipeMaxT || C > 256) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
     BinaryParams q;
-    q.x = x; q.st = stride_t; q.sb = stride_b; q.y = y;
+    q.x = static_cast<const float *>(x);                      // (elements of the kernel's E: the kernels cast it back)
+    q.st = stride_t; q.sb = stride_b; q.y = y;
     q.in_len = in_len; q.tgt_len = tgt_len;
     q.T = T; q.B = B; q.C = C; q.S = S;
     q.SP = (S + 3) / 4 * 4;
@@ -1227,13 +1232,33 @@ extern "C" int ctc_amd_binary_posteriors(const float *x, int64_t stride_t, int64
     q.stop = 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int ch = (C + kWave - 1) / kWave;
-    if (T <= kFlowMaxT && ch <= 3) {                          // the streamed kernel, cut off after the posteriors
-        const int PF = binary_flow_pitch(C);
-        const size_t fb = binary_flow_smem_bytes(T, q.SP, PF, C);
-        if (fb <= kMaxLds) return launch_binary_flow_wt<true, true>(ch, fb, s, q, PF);
-    }
-    const int PD = binary_image_pitch(C);
-    const size_t smem = binary_pipe_smem_bytes(T, q.SP, PD);
-    if (smem > kMaxLds) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
-    return launch_binary_pipe_wt<true, true>(ch, smem, s, q, PD);
+    return with_logit_elem(x_dtype, [&](auto elem) {
+        using E = typename decltype(elem)::type;
+        if (T <= kFlowMaxT && ch <= 3) {                      // the streamed kernel, cut off after the posteriors
+            const int PF = binary_flow_pitch(C);
+            const size_t fb = binary_flow_smem_bytes(T, q.SP, PF, C);
+            if (fb <= kMaxLds) return launch_binary_flow_wt<true, true, E>(ch, fb, s, q, PF);
+        }
+        const int PD = binary_image_pitch(C);
+        const size_t smem = binary_pipe_smem_bytes(T, q.SP, PD);
+        if (smem > kMaxLds) return (int)CTC_AMD_ERR_UNSUPPORTED_SHAPE;
+        return launch_binary_pipe_wt<true, true, E>(ch, smem, s, q, PD);
+    });
+}
+
+extern "C" int ctc_amd_binary_posteriors(const float *x, int64_t stride_t, int64_t stride_b, const float *y,
+                                         const int64_t *in_len, const int64_t *tgt_len, int T, int B, int C, int S,
+                                         float *nll, float *gamma, void *workspace, void *stream)
+{
+    return binary_posteriors_entry(x, CTC_AMD_F32, stride_t, stride_b, y, in_len, tgt_len, T, B, C, S, nll, gamma, workspace,
+                                   stream);
+}
+
+// The same on logits of x_dtype (CTC_AMD_F32: the entry above): a 2-byte element is read as it lies and widened exactly.
+extern "C" int ctc_amd_binary_posteriors_typed(const void *x, int x_dtype, int64_t stride_t, int64_t stride_b, const float *y,
+                                               const int64_t *in_len, const int64_t *tgt_len, int T, int B, int C, int S,
+                                               float *nll, float *gamma, void *workspace, void *stream)
+{
+    return binary_posteriors_entry(x, x_dtype, stride_t, stride_b, y, in_len, tgt_len, T, B, C, S, nll, gamma, workspace,
+                                   stream);
 }

@@ -112,9 +112,12 @@ __device__ __forceinline__ f32x4 mfma_bf16(const u32x4 &a, const u32x4 &b, const
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
-template <int CH, bool WT, bool GAMMA = false>
+// E: the element type of the logits behind p.x -- float, or for the posteriors (GAMMA) also __bf16 / _Float16, which only
+// changes how logit_f32 (common.hpp) brings a logit into its fp32 register
+template <int CH, bool WT, bool GAMMA = false, typename E = float>
 __global__ __launch_bounds__(kBinThreads) void binary_flow_kernel(BinaryParams p, int PD)
 {
+    static_assert(GAMMA || __is_same(E, float), "the binary loss reads fp32 logits");
     extern __shared__ float4 smem_raw[];
     const BinaryFlowSmem sm(reinterpret_cast<float *>(smem_raw), p.T, p.SP, PD, p.C);
     const int b = xcd_sample(blockIdx.x, p.B), tid = threadIdx.x, w = wave_id(), lane = lane_id();
@@ -157,11 +160,11 @@ __global__ __launch_bounds__(kBinThreads) void binary_flow_kernel(BinaryParams p
 #pragma unroll
                 for (int side = 0; side < 2; ++side) {
                     const int t = slot_row(g, side);
-                    const float *row = p.x + (int64_t)(t >= 0 ? t : 0) * p.st + (int64_t)b * p.sb;
+                    const E *row = reinterpret_cast<const E *>(p.x) + (int64_t)(t >= 0 ? t : 0) * p.st + (int64_t)b * p.sb;
 #pragma unroll
                     for (int j = 0; j < CH; ++j) {
                         const int c = lane + 64 * j;
-                        v[g][side][j] = row[c < p.C ? c : p.C - 1];
+                        v[g][side][j] = logit_f32(row + (c < p.C ? c : p.C - 1));
                     }
                 }
             }
@@ -525,11 +528,11 @@ __global__ __launch_bounds__(kBinThreads) void binary_flow_kernel(BinaryParams p
 #pragma unroll
                     for (int side = 0; side < 2; ++side) {
                         const int t = slot_row_of(c0 + c, r, side);
-                        const float *row = p.x + (int64_t)(t >= 0 ? t : 0) * p.st + (int64_t)b * p.sb;
+                        const E *row = reinterpret_cast<const E *>(p.x) + (int64_t)(t >= 0 ? t : 0) * p.st + (int64_t)b * p.sb;
 #pragma unroll
                         for (int j = 0; j < CH; ++j) {
                             const int cc = lane + 64 * j;
-                            xh[c][r][side][j] = row[cc < p.C ? cc : p.C - 1];
+                            xh[c][r][side][j] = logit_f32(row + (cc < p.C ? cc : p.C - 1));
                         }
                     }
         }
@@ -834,15 +837,15 @@ __global__ __launch_bounds__(kBinThreads) void binary_flow_kernel(BinaryParams p
     stamp(p, 7);
 }
 
-template <bool WT, bool GAMMA>
+template <bool WT, bool GAMMA, typename E = float>
 static int launch_binary_flow_wt(int ch, size_t smem, hipStream_t s, const BinaryParams &p, int PD)
 {
     const dim3 grid(p.B), block(kBinThreads);
     switch (ch) {
-        case 1: return launch<binary_flow_kernel<1, WT, GAMMA>>(grid, block, smem, s, p, PD);
-        case 2: return launch<binary_flow_kernel<2, WT, GAMMA>>(grid, block, smem, s, p, PD);
-        case 3: return launch<binary_flow_kernel<3, WT, GAMMA>>(grid, block, smem, s, p, PD);
-        default: return launch<binary_flow_kernel<4, WT, GAMMA>>(grid, block, smem, s, p, PD);
+        case 1: return launch<binary_flow_kernel<1, WT, GAMMA, E>>(grid, block, smem, s, p, PD);
+        case 2: return launch<binary_flow_kernel<2, WT, GAMMA, E>>(grid, block, smem, s, p, PD);
+        case 3: return launch<binary_flow_kernel<3, WT, GAMMA, E>>(grid, block, smem, s, p, PD);
+        default: return launch<binary_flow_kernel<4, WT, GAMMA, E>>(grid, block, smem, s, p, PD);
     }
 }
 

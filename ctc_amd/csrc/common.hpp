@@ -349,6 +349,21 @@ __device__ __forceinline__ int load_label(const void *p, int is64, int64_t i)
     return static_cast<const int32_t *>(p)[is64 ? 2 * i : i];
 }
 
+// One logit from global memory into an fp32 register, for the read-outs that take typed logits (include/ctc_amd.h, the
+// *_typed entries of the no-blank and binary lattices).  E = float: the plain load.  2-byte E: ONE 2-byte load by the same
+// lane for the same element, widened exactly -- __bf16 by a 16-bit shift, _Float16 by v_cvt_f32_f16 (subnormals kept: they
+// become normal fp32 numbers), the rule of r16_widen2 (noblank_r16.hpp).  Everything behind it is the fp32 kernel's code,
+// so a 2-byte launch gives the bits of the fp32 launch on x.float().
+template <typename E>
+__device__ __forceinline__ float logit_f32(const E *p)
+{
+    if constexpr (__is_same(E, __bf16)) {
+        return __builtin_bit_cast(float, (unsigned)*reinterpret_cast<const unsigned short *>(p) << 16);
+    } else {
+        return (float)*p;
+    }
+}
+
 // Two int64 values at wave-uniform addresses through the scalar memory path (s_load_dwordx2): loaded through
 // constant-address-space pointers, so the COMPILER emits the scalar loads and tracks them (its own
 // s_waitcnt lgkmcnt in front of the first use; a hand-written asm load would leave the destination SGPRs

@@ -17,7 +17,7 @@
 namespace ctc {
 
 struct DecodeParams {
-    const float *x;
+    const void *x;                              // logits [T,B,C] of the kernel's element type E (float, __bf16, _Float16)
     int64_t st, sb;
     const void *lab;
     int lab64;
@@ -88,7 +88,8 @@ __device__ __forceinline__ void viterbi_wave(const float *em, unsigned char *bp,
 // The emission stage of the no-blank read-outs, by the NW waves of a workgroup: the sample's label classes into lab[SP]
 // (negative labels wrap), then per row the log-softmax statistics and em[t][l] = lp_t(lab_l) for l < L, the sentinel
 // beyond.  Shared by the best-path and the token-span kernels: the same statements, so the same bits in em.
-template <int NW>
+// E: the element type of the logits; it only decides how logit_f32 (common.hpp) brings one into an fp32 register.
+template <int NW, typename E>
 __device__ __forceinline__ void noblank_emissions(const DecodeParams &p, float *em, int *lab, int b, int Tb, int L)
 {
     const int tid = threadIdx.x, w = wave_id(), lane = lane_id();
@@ -102,21 +103,21 @@ __device__ __forceinline__ void noblank_emissions(const DecodeParams &p, float *
     }
     __syncthreads();
     for (int t = w; t < Tb; t += NW) {                                      // rows: any C
-        const float *row = p.x + (int64_t)t * p.st + (int64_t)b * p.sb;
+        const E *row = static_cast<const E *>(p.x) + (int64_t)t * p.st + (int64_t)b * p.sb;
         float m = -__builtin_inff();
-        for (int c = lane; c < p.C; c += kWave) m = fmaxf(m, row[c]);
+        for (int c = lane; c < p.C; c += kWave) m = fmaxf(m, logit_f32(row + c));
         m = wave_max(m);
         float s = 0.f;
-        for (int c = lane; c < p.C; c += kWave) s += fast_exp(row[c] - m);
+        for (int c = lane; c < p.C; c += kWave) s += fast_exp(logit_f32(row + c) - m);
         s = wave_sum(s);
         const float lsum = fast_log(s);
-        for (int l = lane; l < p.SP; l += kWave) em[t * p.SP + l] = (l < L) ? fmaxf((row[lab[l]] - m) - lsum, kMasked) : kNeg;
+        for (int l = lane; l < p.SP; l += kWave) em[t * p.SP + l] = (l < L) ? fmaxf((logit_f32(row + lab[l]) - m) - lsum, kMasked) : kNeg;
     }
 }
 
 // The same for the binary lattice: per row the two clamped logs, their difference in the wave's own LDS row
 // (drow [NW][C]), one dot product per label row of the targets y [B,S,C].
-template <int NW>
+template <int NW, typename E>
 __device__ __forceinline__ void binary_emissions(const DecodeParams &p, const float *y, float *em, float *drow, int b, int Tb,
                                                  int L)
 {
@@ -125,11 +126,11 @@ __device__ __forceinline__ void binary_emissions(const DecodeParams &p, const fl
     float *d = drow + (size_t)w * p.C;
     const float invC = 1.0f / (float)p.C;
     for (int t = w; t < Tb; t += NW) {
-        const float *row = p.x + (int64_t)t * p.st + (int64_t)b * p.sb;
+        const E *row = static_cast<const E *>(p.x) + (int64_t)t * p.st + (int64_t)b * p.sb;
         float q = 0.f;
         for (int c = lane; c < p.C; c += kWave) {
             float pr, lp, lq;
-            bce_logs(row[c], pr, lp, lq);
+            bce_logs(logit_f32(row + c), pr, lp, lq);
             d[c] = lp - lq;
             q += lq;
         }
@@ -146,7 +147,7 @@ __device__ __forceinline__ void binary_emissions(const DecodeParams &p, const fl
     }
 }
 
-template <int K>
+template <int K, typename E = float>
 __global__ __launch_bounds__(kDecThreads) void noblank_best_path_kernel(DecodeParams p)
 {
     extern __shared__ float4 smem_raw[];
@@ -158,7 +159,7 @@ __global__ __launch_bounds__(kDecThreads) void noblank_best_path_kernel(DecodePa
     const bool ok = L64 >= 1 && L64 <= p.S && Tb64 >= L64 && Tb64 <= p.T;
     const int Tb = ok ? (int)Tb64 : 0, L = ok ? (int)L64 : 0;
 
-    noblank_emissions<kDecWaves>(p, em, lab, b, Tb, L);
+    noblank_emissions<kDecWaves, E>(p, em, lab, b, Tb, L);
     __syncthreads();
 
     if (w == 0) viterbi_wave<K>(em, bp, p, b, Tb, L, ok);
@@ -167,7 +168,7 @@ __global__ __launch_bounds__(kDecThreads) void noblank_best_path_kernel(DecodePa
 // The same read-out on the lattice of the binary (multi-label sigmoid) variant: cell (t, l) costs
 // -nn.BCELoss()(sigmoid(x[t,b,:]), y[b,l,:]) (NoBlankBinaryCTC.py:112,:88,:146) -- per row the two clamped logs, their
 // difference in a wave-private LDS row, one dot product per label row of the targets.
-template <int K>
+template <int K, typename E = float>
 __global__ __launch_bounds__(kDecThreads) void binary_best_path_kernel(DecodeParams p, const float *y)
 {
     extern __shared__ float4 smem_raw[];
@@ -178,7 +179,7 @@ __global__ __launch_bounds__(kDecThreads) void binary_best_path_kernel(DecodePar
     const int64_t Tb64 = p.in_len[b], L64 = p.tgt_len[b];
     const bool ok = L64 >= 1 && L64 <= p.S && Tb64 >= L64 && Tb64 <= p.T;
     const int Tb = ok ? (int)Tb64 : 0, L = ok ? (int)L64 : 0;
-    binary_emissions<kDecWaves>(p, y, em, drow, b, Tb, L);
+    binary_emissions<kDecWaves, E>(p, y, em, drow, b, Tb, L);
     __syncthreads();
     if (w == 0) viterbi_wave<K>(em, bp, p, b, Tb, L, ok);
 }
@@ -189,15 +190,16 @@ __global__ __launch_bounds__(kDecThreads) void binary_best_path_kernel(DecodePar
 
 using namespace ctc;
 
-extern "C" int ctc_amd_noblank_best_path(const float *x, int64_t stride_t, int64_t stride_b,
-                                         const void *labels, int labels_i64,
-                                         const int64_t *in_len, const int64_t *tgt_len,
-                                         int T, int B, int C, int S,
-                                         int32_t *path, float *score,
-                                         void *workspace, void *stream)
+static bool logit_dtype_known(int x_dtype) { return x_dtype == CTC_AMD_F32 || x_dtype == CTC_AMD_BF16 || x_dtype == CTC_AMD_F16; }
+
+// Best paths: y == nullptr is the no-blank lattice (labels), else the binary one (targets y [B,S,C] float; SURVEY 8f-1: the
+// reference has no such routine).  x_dtype: the element type of x, CTC_AMD_F32 for the untyped entries.
+static int best_path_entry(const void *x, int x_dtype, int64_t stride_t, int64_t stride_b, const void *labels, int labels_i64,
+                           const float *y, const int64_t *in_len, const int64_t *tgt_len, int T, int B, int C, int S,
+                           int32_t *path, float *score, void *stream)
 {
-    (void)workspace;
-    if (!x || !labels || !in_len || !tgt_len || !path || !score) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (!logit_dtype_known(x_dtype)) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (!x || (!labels && !y) || !in_len || !tgt_len || !path || !score) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (T < 1 || B < 1 || C < 1 || S < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
     const auto [K, SP] = lane_states(S);
     if (K > 4) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
@@ -208,54 +210,83 @@ extern "C" int ctc_amd_noblank_best_path(const float *x, int64_t stride_t, int64
     p.T = T; p.B = B; p.C = C; p.S = S;
     p.SP = SP;
     p.path = path; p.score = score;
-    const size_t smem = ((size_t)T * p.SP + p.SP) * 4 + (size_t)T * p.SP + 16;
+    const size_t smem = y ? ((size_t)T * p.SP + (size_t)kDecWaves * C) * 4 + (size_t)T * p.SP + 16
+                          : ((size_t)T * p.SP + p.SP) * 4 + (size_t)T * p.SP + 16;
     if (smem > kMaxLds) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid(B), block(kDecThreads);
-    switch (K) {
-        case 1: return launch<noblank_best_path_kernel<1>>(grid, block, smem, s, p);
-        case 2: return launch<noblank_best_path_kernel<2>>(grid, block, smem, s, p);
-        default: return launch<noblank_best_path_kernel<4>>(grid, block, smem, s, p);
-    }
+    const int k = K;                                         // (a structured binding cannot be captured)
+    return with_logit_elem(x_dtype, [&](auto elem) {
+        using E = typename decltype(elem)::type;
+        if (y) {
+            switch (k) {
+                case 1: return launch<binary_best_path_kernel<1, E>>(grid, block, smem, s, p, y);
+                case 2: return launch<binary_best_path_kernel<2, E>>(grid, block, smem, s, p, y);
+                default: return launch<binary_best_path_kernel<4, E>>(grid, block, smem, s, p, y);
+            }
+        }
+        switch (k) {
+            case 1: return launch<noblank_best_path_kernel<1, E>>(grid, block, smem, s, p);
+            case 2: return launch<noblank_best_path_kernel<2, E>>(grid, block, smem, s, p);
+            default: return launch<noblank_best_path_kernel<4, E>>(grid, block, smem, s, p);
+        }
+    });
 }
 
+extern "C" int ctc_amd_noblank_best_path(const float *x, int64_t stride_t, int64_t stride_b,
+                                         const void *labels, int labels_i64,
+                                         const int64_t *in_len, const int64_t *tgt_len,
+                                         int T, int B, int C, int S,
+                                         int32_t *path, float *score,
+                                         void *workspace, void *stream)
+{
+    (void)workspace;
+    if (!labels) return CTC_AMD_ERR_BAD_ARGUMENT;
+    return best_path_entry(x, CTC_AMD_F32, stride_t, stride_b, labels, labels_i64, nullptr, in_len, tgt_len, T, B, C, S, path,
+                           score, stream);
+}
 
-// Best alignment on the binary lattice (the reference has no such routine): targets y [B,S,C] float.
+extern "C" int ctc_amd_noblank_best_path_typed(const void *x, int x_dtype, int64_t stride_t, int64_t stride_b,
+                                               const void *labels, int labels_i64,
+                                               const int64_t *in_len, const int64_t *tgt_len,
+                                               int T, int B, int C, int S,
+                                               int32_t *path, float *score,
+                                               void *workspace, void *stream)
+{
+    (void)workspace;
+    if (!labels) return CTC_AMD_ERR_BAD_ARGUMENT;
+    return best_path_entry(x, x_dtype, stride_t, stride_b, labels, labels_i64, nullptr, in_len, tgt_len, T, B, C, S, path,
+                           score, stream);
+}
+
 extern "C" int ctc_amd_binary_best_path(const float *x, int64_t stride_t, int64_t stride_b, const float *y,
                                         const int64_t *in_len, const int64_t *tgt_len,
                                         int T, int B, int C, int S,
                                         int32_t *path, float *score, void *workspace, void *stream)
 {
     (void)workspace;
-    if (!x || !y || !in_len || !tgt_len || !path || !score) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (T < 1 || B < 1 || C < 1 || S < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
-    const auto [K, SP] = lane_states(S);
-    if (K > 4) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
-    DecodeParams p;
-    p.x = x; p.st = stride_t; p.sb = stride_b;
-    p.lab = nullptr; p.lab64 = 0;
-    p.in_len = in_len; p.tgt_len = tgt_len;
-    p.T = T; p.B = B; p.C = C; p.S = S;
-    p.SP = SP;
-    p.path = path; p.score = score;
-    const size_t smem = ((size_t)T * p.SP + (size_t)kDecWaves * C) * 4 + (size_t)T * p.SP + 16;
-    if (smem > kMaxLds) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid(B), block(kDecThreads);
-    switch (K) {
-        case 1: return launch<binary_best_path_kernel<1>>(grid, block, smem, s, p, y);
-        case 2: return launch<binary_best_path_kernel<2>>(grid, block, smem, s, p, y);
-        default: return launch<binary_best_path_kernel<4>>(grid, block, smem, s, p, y);
-    }
+    if (!y) return CTC_AMD_ERR_BAD_ARGUMENT;
+    return best_path_entry(x, CTC_AMD_F32, stride_t, stride_b, nullptr, 0, y, in_len, tgt_len, T, B, C, S, path, score, stream);
+}
+
+extern "C" int ctc_amd_binary_best_path_typed(const void *x, int x_dtype, int64_t stride_t, int64_t stride_b, const float *y,
+                                              const int64_t *in_len, const int64_t *tgt_len,
+                                              int T, int B, int C, int S,
+                                              int32_t *path, float *score, void *workspace, void *stream)
+{
+    (void)workspace;
+    if (!y) return CTC_AMD_ERR_BAD_ARGUMENT;
+    return best_path_entry(x, x_dtype, stride_t, stride_b, nullptr, 0, y, in_len, tgt_len, T, B, C, S, path, score, stream);
 }
 
 
 // Token spans: one launch of decode_spans.hpp's kernel per call.
-static int token_spans_entry(const float *x, int64_t stride_t, int64_t stride_b, const void *labels, int labels_i64,
+static int token_spans_entry(const void *x, int x_dtype, int64_t stride_t, int64_t stride_b, const void *labels, int labels_i64,
                              const float *y, const int64_t *in_len, const int64_t *tgt_len, int T, int B, int C, int S,
                              int32_t *path, float *score, float *nll, float *frame_conf, int32_t *start, int32_t *end,
                              float *conf, void *stream)
 {
+    if (!logit_dtype_known(x_dtype)) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (!x || (!labels && !y) || !in_len || !tgt_len || !path || !score || !nll || !frame_conf || !start || !end || !conf)
         return CTC_AMD_ERR_BAD_ARGUMENT;
     if (T < 1 || B < 1 || C < 1 || S < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
@@ -271,7 +302,10 @@ static int token_spans_entry(const float *x, int64_t stride_t, int64_t stride_b,
     p.path = path; p.score = score;
     q.nll = nll; q.frame_conf = frame_conf;
     q.start = start; q.end = end; q.conf = conf;
-    return run_token_spans(q, y, K, static_cast<hipStream_t>(stream));
+    const int k = K;
+    return with_logit_elem(x_dtype, [&](auto elem) {
+        return run_token_spans<typename decltype(elem)::type>(q, y, k, static_cast<hipStream_t>(stream));
+    });
 }
 
 extern "C" int ctc_amd_noblank_token_spans(const float *x, int64_t stride_t, int64_t stride_b,
@@ -283,8 +317,21 @@ extern "C" int ctc_amd_noblank_token_spans(const float *x, int64_t stride_t, int
                                            void *workspace, void *stream)
 {
     (void)workspace;
-    return token_spans_entry(x, stride_t, stride_b, labels, labels_i64, nullptr, in_len, tgt_len, T, B, C, S, path, score,
-                             nll, frame_conf, start, end, conf, stream);
+    return token_spans_entry(x, CTC_AMD_F32, stride_t, stride_b, labels, labels_i64, nullptr, in_len, tgt_len, T, B, C, S, path,
+                             score, nll, frame_conf, start, end, conf, stream);
+}
+
+extern "C" int ctc_amd_noblank_token_spans_typed(const void *x, int x_dtype, int64_t stride_t, int64_t stride_b,
+                                                 const void *labels, int labels_i64,
+                                                 const int64_t *in_len, const int64_t *tgt_len,
+                                                 int T, int B, int C, int S,
+                                                 int32_t *path, float *score, float *nll, float *frame_conf,
+                                                 int32_t *start, int32_t *end, float *conf,
+                                                 void *workspace, void *stream)
+{
+    (void)workspace;
+    return token_spans_entry(x, x_dtype, stride_t, stride_b, labels, labels_i64, nullptr, in_len, tgt_len, T, B, C, S, path,
+                             score, nll, frame_conf, start, end, conf, stream);
 }
 
 extern "C" int ctc_amd_binary_token_spans(const float *x, int64_t stride_t, int64_t stride_b, const float *y,
@@ -295,6 +342,18 @@ extern "C" int ctc_amd_binary_token_spans(const float *x, int64_t stride_t, int6
                                           void *workspace, void *stream)
 {
     (void)workspace;
-    return token_spans_entry(x, stride_t, stride_b, nullptr, 0, y, in_len, tgt_len, T, B, C, S, path, score, nll,
+    return token_spans_entry(x, CTC_AMD_F32, stride_t, stride_b, nullptr, 0, y, in_len, tgt_len, T, B, C, S, path, score, nll,
+                             frame_conf, start, end, conf, stream);
+}
+
+extern "C" int ctc_amd_binary_token_spans_typed(const void *x, int x_dtype, int64_t stride_t, int64_t stride_b, const float *y,
+                                                const int64_t *in_len, const int64_t *tgt_len,
+                                                int T, int B, int C, int S,
+                                                int32_t *path, float *score, float *nll, float *frame_conf,
+                                                int32_t *start, int32_t *end, float *conf,
+                                                void *workspace, void *stream)
+{
+    (void)workspace;
+    return token_spans_entry(x, x_dtype, stride_t, stride_b, nullptr, 0, y, in_len, tgt_len, T, B, C, S, path, score, nll,
                              frame_conf, start, end, conf, stream);
 }

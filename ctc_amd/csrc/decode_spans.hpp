@@ -153,7 +153,7 @@ __device__ __forceinline__ void token_spans_tail(const TokenSmem &sm, const Toke
     }
 }
 
-template <int K>
+template <int K, typename E = float>
 __global__ __launch_bounds__(kTokThreads) void noblank_token_spans_kernel(TokenSpanParams q)
 {
     extern __shared__ float4 smem_raw[];
@@ -164,12 +164,12 @@ __global__ __launch_bounds__(kTokThreads) void noblank_token_spans_kernel(TokenS
     const bool ok = L64 >= 1 && L64 <= p.S && Tb64 >= L64 && Tb64 <= p.T;
     const int Tb = ok ? (int)Tb64 : 0, L = ok ? (int)L64 : 0;
     token_pad_rows(sm, p.T, p.SP);
-    noblank_emissions<kTokWaves>(p, sm.em, reinterpret_cast<int *>(sm.extra), b, Tb, L);
+    noblank_emissions<kTokWaves, E>(p, sm.em, reinterpret_cast<int *>(sm.extra), b, Tb, L);
     __syncthreads();
     token_spans_tail<K>(sm, q, b, Tb, L, ok);
 }
 
-template <int K>
+template <int K, typename E = float>
 __global__ __launch_bounds__(kTokThreads) void binary_token_spans_kernel(TokenSpanParams q, const float *y)
 {
     extern __shared__ float4 smem_raw[];
@@ -180,12 +180,13 @@ __global__ __launch_bounds__(kTokThreads) void binary_token_spans_kernel(TokenSp
     const bool ok = L64 >= 1 && L64 <= p.S && Tb64 >= L64 && Tb64 <= p.T;
     const int Tb = ok ? (int)Tb64 : 0, L = ok ? (int)L64 : 0;
     token_pad_rows(sm, p.T, p.SP);
-    binary_emissions<kTokWaves>(p, y, sm.em, sm.extra, b, Tb, L);
+    binary_emissions<kTokWaves, E>(p, y, sm.em, sm.extra, b, Tb, L);
     __syncthreads();
     token_spans_tail<K>(sm, q, b, Tb, L, ok);
 }
 
-// y == nullptr: the no-blank lattice
+// y == nullptr: the no-blank lattice.  E: the element type of q.d.x
+template <typename E>
 static int run_token_spans(const TokenSpanParams &q, const float *y, int K, hipStream_t s)
 {
     const DecodeParams &p = q.d;
@@ -194,15 +195,15 @@ static int run_token_spans(const TokenSpanParams &q, const float *y, int K, hipS
     const dim3 grid(p.B), block(kTokThreads);
     if (y) {
         switch (K) {
-            case 1: return launch<binary_token_spans_kernel<1>>(grid, block, smem, s, q, y);
-            case 2: return launch<binary_token_spans_kernel<2>>(grid, block, smem, s, q, y);
-            default: return launch<binary_token_spans_kernel<4>>(grid, block, smem, s, q, y);
+            case 1: return launch<binary_token_spans_kernel<1, E>>(grid, block, smem, s, q, y);
+            case 2: return launch<binary_token_spans_kernel<2, E>>(grid, block, smem, s, q, y);
+            default: return launch<binary_token_spans_kernel<4, E>>(grid, block, smem, s, q, y);
         }
     }
     switch (K) {
-        case 1: return launch<noblank_token_spans_kernel<1>>(grid, block, smem, s, q);
-        case 2: return launch<noblank_token_spans_kernel<2>>(grid, block, smem, s, q);
-        default: return launch<noblank_token_spans_kernel<4>>(grid, block, smem, s, q);
+        case 1: return launch<noblank_token_spans_kernel<1, E>>(grid, block, smem, s, q);
+        case 2: return launch<noblank_token_spans_kernel<2, E>>(grid, block, smem, s, q);
+        default: return launch<noblank_token_spans_kernel<4, E>>(grid, block, smem, s, q);
     }
 }
 

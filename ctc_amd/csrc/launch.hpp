@@ -49,6 +49,19 @@ inline int diag_env(const char *name, int fallback = 0)
 #endif
 }
 
+// x_dtype of the typed read-out entries -> the element type E of their kernels: f(LogitElem<E>{})
+template <typename E> struct LogitElem { using type = E; };
+template <typename F>
+inline int with_logit_elem(int x_dtype, F f)
+{
+    switch (x_dtype) {
+    case CTC_AMD_F32: return f(LogitElem<float>{});
+    case CTC_AMD_BF16: return f(LogitElem<__bf16>{});
+    case CTC_AMD_F16: return f(LogitElem<_Float16>{});
+    default: return CTC_AMD_ERR_BAD_ARGUMENT;
+    }
+}
+
 template <auto kern, typename... Args>
 inline int launch(dim3 grid, dim3 block, size_t smem, hipStream_t stream, Args... args)
 {

@@ -698,7 +698,8 @@ static int noblank_run(const void *x, int64_t stride_t, int64_t stride_b,
     const NoblankQuery q = {T, B, C, S, x_dtype, stride_t, stride_b,
                             (unsigned)(reinterpret_cast<uintptr_t>(x) & 15), (unsigned)(reinterpret_cast<uintptr_t>(grad) & 15),
                             p.grad != nullptr, gamma != nullptr, label_smoothing >= 0.f,
-                            device_cus(),                    // (per device: a process may drive several)
+                            gamma ? 0 : device_cus(),        // (per device: a process may drive several; the posteriors' plan
+                                                             // does not read it, and refuses a shape before any HIP call)
                             sw};
     return noblank_launch(noblank_plan(q), x_dtype, p, static_cast<hipStream_t>(stream));
 }
@@ -793,6 +794,21 @@ extern "C" int ctc_amd_noblank_posteriors(const float *x, int64_t stride_t, int6
     if (!gamma) return CTC_AMD_ERR_BAD_ARGUMENT;
     return noblank_run(x, stride_t, stride_b, labels, labels_i64, in_len, tgt_len, T, B, C, S, 0.f, 0.f, nll, nullptr,
                        nullptr, workspace, stream, -1.f, CTC_AMD_F32, gamma);
+}
+
+// The same on logits of x_dtype (CTC_AMD_F32: the entry above).  2-byte logits: the r16 kernel's shape domain only, as for
+// ctc_amd_noblank_loss_grad_typed; CTC_AMD_ERR_UNSUPPORTED_SHAPE outside it.
+extern "C" int ctc_amd_noblank_posteriors_typed(const void *x, int x_dtype, int64_t stride_t, int64_t stride_b,
+                                                const void *labels, int labels_i64,
+                                                const int64_t *in_len, const int64_t *tgt_len,
+                                                int T, int B, int C, int S,
+                                                float *nll, float *gamma,
+                                                void *workspace, void *stream)
+{
+    if (x_dtype != CTC_AMD_F32 && x_dtype != CTC_AMD_BF16 && x_dtype != CTC_AMD_F16) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (!gamma) return CTC_AMD_ERR_BAD_ARGUMENT;
+    return noblank_run(x, stride_t, stride_b, labels, labels_i64, in_len, tgt_len, T, B, C, S, 0.f, 0.f, nll, nullptr,
+                       nullptr, workspace, stream, -1.f, x_dtype, gamma);
 }
 
 #ifdef CTC_AMD_DIAGNOSTICS

@@ -820,7 +820,7 @@ __global__ __launch_bounds__(kThreads, 4) void noblank_r16_kernel(NoblankParams 
     // is published, every scale is 0, the gradient rows come out as zeros): ONE path through the loop.  The compiler
     // places its waits for the next sample's row loads by control-flow paths; with a side path that loads and leaves,
     // the main path waited for its own last gradient stores at the end of every sample.
-    const bool has_grad = PS || p.grad != nullptr, has_gamma = !PS && !Row::kLowp && p.gamma != nullptr;
+    const bool has_grad = PS || p.grad != nullptr, has_gamma = !PS && p.gamma != nullptr;
     // PS: the next sample's rows into the spare register set (all of this sample's rows are in `v` by then)
     // (unconditional, like every load of a next sample's rows: behind the workgroup's last sample they fetch that
     // sample's rows once more, and nobody waits for them -- a load under a condition leaves the compiler with two
@@ -841,7 +841,7 @@ __global__ __launch_bounds__(kThreads, 4) void noblank_r16_kernel(NoblankParams 
             for (int g = 0; g < G; ++g)
                 if (tv[g] >= 0) Row::template store_zero<NT>(reinterpret_cast<E *>(p.grad) + ((int64_t)tv[g] * p.B + b) * p.C, i16, col_ok);
         }
-        if (!Row::kLowp && p.gamma) {                                       // posteriors of a sample without alignment: zeros
+        if (p.gamma) {                                                      // posteriors of a sample without alignment: zeros
 #pragma unroll
             for (int g = 0; g < G; ++g)
                 for (int l = i16; l < p.S && tv[g] >= 0; l += 16) p.gamma[((int64_t)b * p.T + tv[g]) * p.S + l] = 0.f;

@@ -17,6 +17,10 @@ Forward runs ONE fused HIP launch that produces the loss and (when the input nee
 a gradient) the whole input gradient; backward multiplies that buffer by the upstream
 gradient on the device (a no-op launch when it is 1.0, i.e. ``loss.backward()``).
 There is no CPU path: non-HIP tensors raise.
+
+The read-outs of the no-blank and the binary lattice (``*_best_path``, ``*_posteriors``, ``*_token_spans``) take float32,
+bfloat16 or float16 logits: 2-byte logits are read as they lie by the ``_typed`` entries of include/ctc_amd.h, and every
+output is bit for bit that of the same call on ``logits.float()``.
 """
 import os
 from typing import NamedTuple
@@ -31,6 +35,10 @@ _VALIDATE = os.environ.get("CTC_AMD_VALIDATE", "0") == "1"
 # 2-byte logits the no-blank loss reads natively (include/ctc_amd.h, ctc_amd_noblank_loss_grad_typed)
 _LOWP_CODE = {torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
 _LOWP_DOMAIN = ("C even <= 256, S <= 31, T <= 168, even strides and 4-byte aligned rows")
+# 2-byte logits the no-blank / binary read-outs hand to their `_typed` entries as they lie.  A dtype that is
+# accepted (`_LOWP_CODE`) but missing here is cast with `.float()` in front of the untyped entry -- the same bits, one more
+# launch: tools/readout_typed_bench.py empties this dict to time that path in the same process.
+_LOWP_READOUT = {torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
@@ -500,14 +508,16 @@ def blank_ctc_loss(log_probs, targets, input_lengths, target_lengths, blank=0, b
 
 
 def _readout_inputs(x, name, targets, in_len, tgt_len, variant):
-    """What the read-outs (best path, posteriors) do before their launch -> (xs, tg, il, tl, T, B, C, S, dev): float32
-    logits [T,B,C] on a HIP device, detached and with unit class stride; targets of `variant` and int64 lengths on that
-    device.  The blank read-outs refuse empty shapes here (target lengths may be 0); the no-blank and binary ones leave
-    that to the library, which answers with its own error."""
+    """What the read-outs (best path, posteriors, token spans) do before their launch -> (xs, tg, il, tl, T, B, C, S, dev):
+    logits [T,B,C] on a HIP device, detached and with unit class stride -- float32, or for the no-blank and binary variants
+    also bfloat16 / float16, kept in their own dtype (a copy for the class stride included); targets of `variant` and int64
+    lengths on that device.  The blank read-outs refuse empty shapes here (target lengths may be 0); the no-blank and binary
+    ones leave that to the library, which answers with its own error."""
     blank = variant == _lib.BLANK
     _require_hip(x, name)
-    if x.dim() != 3 or x.dtype != torch.float32:
-        raise ValueError("ctc_amd: %s must be float32 [T,B,C]" % name)
+    if x.dim() != 3 or (x.dtype != torch.float32 and (blank or x.dtype not in _LOWP_CODE)):
+        raise ValueError("ctc_amd: %s must be float32 [T,B,C]" % name if blank else
+                         "ctc_amd: %s must be float32, bfloat16 or float16 [T,B,C]" % name)
     T, B, C = x.shape
     if blank and (T < 1 or B < 1 or C < 1):
         raise ValueError("ctc_amd: empty %s %s" % (name, tuple(x.shape)))
@@ -534,10 +544,28 @@ def _readout_inputs(x, name, targets, in_len, tgt_len, variant):
     return xs, tg, il, tl, T, B, C, S, dev
 
 
-def _readout(entry, variant, x, name, targets, in_len, tgt_len, width, out_dtype, extra=(), workspace=True):
+def _logits_call(entry, xs, rest, fallback=False):
+    """The C-ABI call `entry`(x, stride_t, stride_b, *rest) on the logits `xs` -> its return code.  float32 logits go to
+    `entry`.  bfloat16 / float16 logits go to `entry + "_typed"` as they lie (no fp32 image, no cast launch); `fallback`:
+    when that entry answers UNSUPPORTED_SHAPE -- only ctc_amd_noblank_posteriors_typed has a narrower domain than its
+    sibling -- and for a 2-byte dtype that `_LOWP_READOUT` does not hold, the cast and the untyped entry, which then
+    answers as it does for float32 input, its own error included."""
+    lib = _lib.load()
+    code = _LOWP_READOUT.get(xs.dtype)
+    if code is not None:
+        rc = getattr(lib, entry + "_typed")(xs.data_ptr(), code, xs.stride(0), xs.stride(1), *rest)
+        if rc != _lib.ERR_UNSUPPORTED_SHAPE or not fallback:
+            return rc
+    if xs.dtype is not torch.float32:
+        xs = xs.float()                                      # (keeps the unit class stride)
+    return getattr(lib, entry)(xs.data_ptr(), xs.stride(0), xs.stride(1), *rest)
+
+
+def _readout(entry, variant, x, name, targets, in_len, tgt_len, width, out_dtype, extra=(), workspace=True, fallback=False):
     """One read-out launch -> (out[B,T,width] or out[B,T] of out_dtype, per_sample[B] fp32).  `entry`: the C-ABI call
     (x, strides, targets[, labels_i64], lengths, T, B, C, S, *extra, per-sample or main output as the header orders
-    them, workspace, stream); `width(S)`: last dimension of the main output, None for [B,T]."""
+    them, workspace, stream), its `_typed` sibling for 2-byte logits (`_logits_call`); `width(S)`: last dimension of the
+    main output, None for [B,T]."""
     xs, tg, il, tl, T, B, C, S, dev = _readout_inputs(x, name, targets, in_len, tgt_len, variant)
     w = width(S) if width else None
     out = torch.empty((B, T) if w is None else (B, T, w), dtype=out_dtype, device=dev)
@@ -548,8 +576,8 @@ def _readout(entry, variant, x, name, targets, in_len, tgt_len, width, out_dtype
     with _on_device(dev):
         stream = _stream_handle(dev)
         ws = _workspace(variant, T, B, C, S, dev, stream).data_ptr() if workspace else None
-        rc = getattr(_lib.load(), entry)(xs.data_ptr(), xs.stride(0), xs.stride(1), tg.data_ptr(), *lab, il.data_ptr(),
-                                         tl.data_ptr(), T, B, C, S, *extra, *outs, ws, stream)
+        rc = _logits_call(entry, xs, (tg.data_ptr(), *lab, il.data_ptr(), tl.data_ptr(), T, B, C, S, *extra, *outs, ws,
+                                      stream), fallback)
     _lib.check(rc, entry)
     if variant == _lib.BLANK and _VALIDATE:
         check_status(dev)
@@ -562,6 +590,10 @@ def noblank_best_path(logits, targets, input_lengths, target_lengths):
     ``path[b,t]`` is the label POSITION l_t (index into targets[b]) occupied at step t, -1 for
     ``t >= T_b`` or when no alignment exists; ``score[b]`` its log-probability.  Max-semiring
     twin of the loss recursion (NoBlankCTC.py:71-87); SURVEY 8(f) rank 1.
+
+    ``logits``: float32, bfloat16 or float16 logits [T,B,C].  2-byte logits are read as they lie
+    (``ctc_amd_noblank_best_path_typed``: no fp32 copy, any shape the float32 call takes); path and score are bit for bit
+    those of the call on ``logits.float()``.
     """
     return _readout("ctc_amd_noblank_best_path", _lib.NOBLANK, logits, "logits", targets, input_lengths, target_lengths,
                     None, torch.int32, workspace=False)
@@ -570,7 +602,9 @@ def noblank_best_path(logits, targets, input_lengths, target_lengths):
 def binary_best_path(logits, targets, input_lengths, target_lengths):
     """Best (Viterbi) alignment on the lattice of the binary variant -> (path[B,T] int32, score[B]); ``targets`` [B,S,C]
     float label rows, ``path[b,t]`` the label ROW occupied at step t (-1 for ``t >= T_b`` or when no alignment exists).
-    Max-semiring twin of NoBlankBinaryCTC's recursion (NoBlankBinaryCTC.py:72-95); SURVEY 8(f) rank 1."""
+    Max-semiring twin of NoBlankBinaryCTC's recursion (NoBlankBinaryCTC.py:72-95); SURVEY 8(f) rank 1.  float32, bfloat16
+    or float16 logits: 2-byte logits are read as they lie (``ctc_amd_binary_best_path_typed``), with the bits of the call on
+    ``logits.float()``."""
     return _readout("ctc_amd_binary_best_path", _lib.BINARY, logits, "logits", targets, input_lengths, target_lengths,
                     None, torch.int32, workspace=False)
 
@@ -717,10 +751,10 @@ def _token_spans(entry, variant, logits, targets, in_len, tgt_len):
     nll = torch.empty(B, dtype=torch.float32, device=dev)
     lab = () if variant == _lib.BINARY else (int(tg.dtype is torch.int64),)
     with _on_device(dev):
-        rc = getattr(_lib.load(), entry)(
-            xs.data_ptr(), xs.stride(0), xs.stride(1), tg.data_ptr(), *lab, il.data_ptr(), tl.data_ptr(), T, B, C, S,
+        rc = _logits_call(entry, xs, (
+            tg.data_ptr(), *lab, il.data_ptr(), tl.data_ptr(), T, B, C, S,
             path.data_ptr(), score.data_ptr(), nll.data_ptr(), frame_conf.data_ptr(), start.data_ptr(), end.data_ptr(),
-            conf.data_ptr(), None, _stream_handle(dev))
+            conf.data_ptr(), None, _stream_handle(dev)))
     if rc == _lib.ERR_UNSUPPORTED_SHAPE:
         raise _lib.CtcAmdError(
             "ctc_amd: %s holds a sample's lattice in LDS: S <= %d label columns and about 13 bytes per cell of T x S "
@@ -735,7 +769,9 @@ def noblank_token_spans(logits, targets, input_lengths, target_lengths):
     """The segmentation of a clip by its transcript on the no-blank lattice, in one launch ->
     ``TokenSpans(start, end, conf, frame_conf, path, score, nll)``.
 
-    Same inputs as ``noblank_best_path``: float32 logits [T,B,C] on a HIP device (any batch / time strides), ``targets``
+    Same inputs as ``noblank_best_path``: float32, bfloat16 or float16 logits [T,B,C] on a HIP device (any batch / time
+    strides; 2-byte logits are read as they lie by ``ctc_amd_noblank_token_spans_typed`` -- the same shapes, and every output
+    bit for bit that of the call on ``logits.float()``), ``targets``
     [B,S] int32 / int64 (negative labels inside L_b wrap as there), lengths on the host or on the device.  For sample b
     with T_b frames and L_b labels:
 
@@ -763,7 +799,8 @@ def noblank_token_spans(logits, targets, input_lengths, target_lengths):
 def binary_token_spans(logits, targets, input_lengths, target_lengths):
     """``noblank_token_spans`` on the lattice of the binary variant -> ``TokenSpans``: ``targets`` [B,S,C] float label
     rows as in ``binary_best_path``, whose ``path`` / ``score`` these are bit for bit; the class of span j is row j of
-    the targets.  ``nll`` is ``+inf`` for a sample without an alignment (the loss itself reports the reference's sentinel
+    the targets.  float32, bfloat16 or float16 logits, 2-byte ones read as they lie (``ctc_amd_binary_token_spans_typed``)
+    with the bits of the call on ``logits.float()``.  ``nll`` is ``+inf`` for a sample without an alignment (the loss itself reports the reference's sentinel
     magnitude there).  LDS bound: ``((3T + 8) SP + 2T + 2 SP + 16 C + 8) * 4 + T * SP + 16`` bytes within 160 KB (S <=
     256; T = 150 at every S <= 64 and C <= 256 -- not ``binary_posteriors``' T <= 168, S <= 64, C <= 256);
     ``CtcAmdError`` beyond."""
@@ -775,15 +812,22 @@ def noblank_posteriors(logits, targets, input_lengths, target_lengths):
 
     ``gamma[b,t,l]`` = P(label position l at step t | logits, targets): the soft alignment whose
     class-scatter is the loss gradient; rows sum to 1 for ``t < T_b``.  SURVEY 8(f) rank 1.
+
+    ``logits``: float32, bfloat16 or float16 logits [T,B,C].  2-byte logits are read as they lie
+    (``ctc_amd_noblank_posteriors_typed``) inside the reduced-precision domain of the no-blank loss -- C even <= 256,
+    S <= 31, T <= 168, even strides, 4-byte aligned rows; outside it they are cast with ``.float()`` and take the float32
+    entry.  Either way gamma and nll are bit for bit those of the call on ``logits.float()``.
     """
     return _readout("ctc_amd_noblank_posteriors", _lib.NOBLANK, logits, "logits", targets, input_lengths,
-                    target_lengths, lambda S: S, torch.float32)
+                    target_lengths, lambda S: S, torch.float32, fallback=True)
 
 
 def binary_posteriors(logits, targets, input_lengths, target_lengths):
     """Per-step posteriors of the binary (multi-hot) lattice -> (gamma[B,T,S], nll[B]): ``gamma[b,t,l]`` =
     P(target row l at step t | logits, targets), rows sum to 1 for ``t < T_b``.  SURVEY 8(f) rank 1, the sibling of
-    ``noblank_posteriors``; shapes of the pipelined binary kernel (S <= 64, T <= 168, C <= 256)."""
+    ``noblank_posteriors``; shapes of the pipelined binary kernel (S <= 64, T <= 168, C <= 256).  float32, bfloat16 or
+    float16 logits: 2-byte logits are read as they lie (``ctc_amd_binary_posteriors_typed``, the same shapes), with the bits
+    of the call on ``logits.float()``."""
     return _readout("ctc_amd_binary_posteriors", _lib.BINARY, logits, "logits", targets, input_lengths,
                     target_lengths, lambda S: S, torch.float32)
 

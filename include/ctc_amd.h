@@ -447,6 +447,59 @@ int ctc_amd_binary_posteriors(const float *x, int64_t stride_t, int64_t stride_b
                               float *nll, float *gamma,
                               void *workspace, void *stream);
 
+/* The read-outs of the no-blank and the binary lattice on typed logits: each entry below is its untyped sibling's
+ * argument list with (const void *x, int x_dtype) in place of (const float *x) -- the convention of
+ * ctc_amd_noblank_loss_grad_typed and of the typed head entries.  A model trained under autocast hands its logits
+ * over in bf16 / fp16, and the read-outs take them as they lie instead of an fp32 copy.
+ *   x_dtype CTC_AMD_F32: exactly the untyped entry -- the same kernel, the same instantiation, the same answers.
+ *   CTC_AMD_BF16 / CTC_AMD_F16: x [T,B,C] is a 2-byte array, strides in elements, stride over the classes 1.  Every kernel
+ *     reads each logit with ONE 2-byte load by the lane that read the fp32 element and widens it exactly (bf16: a 16-bit
+ *     shift; fp16: the exact conversion, subnormals kept); everything behind that load is the fp32 kernel's code.  So
+ *     every output is BIT FOR BIT what the untyped entry writes for the fp32 image of x (NaN logits aside).
+ *   Any other x_dtype: CTC_AMD_ERR_BAD_ARGUMENT, before anything else is looked at.
+ * Outputs keep their types: path / start / end int32; score, nll, gamma, frame_conf, conf fp32.  Null pointers and T, B,
+ * C, S < 1: CTC_AMD_ERR_BAD_ARGUMENT; S > 256: CTC_AMD_ERR_UNSUPPORTED_SHAPE -- all before any HIP call.
+ * Shape domains for 2-byte x:
+ *   best paths, token spans, binary posteriors: those of the untyped entry -- any C, any strides, x 2-byte aligned, the
+ *     same LDS bounds.
+ *   ctc_amd_noblank_posteriors_typed: the four-rows-per-wave kernel only, as ctc_amd_noblank_loss_grad_typed -- C even
+ *     <= 256, S <= 31, T <= 168, even strides, x 4-byte aligned, arrays within LDS; CTC_AMD_ERR_UNSUPPORTED_SHAPE
+ *     otherwise (the untyped entry on an fp32 copy takes every shape). */
+int ctc_amd_noblank_best_path_typed(const void *x, int x_dtype, int64_t stride_t, int64_t stride_b,
+                                    const void *labels, int labels_i64,
+                                    const int64_t *in_len, const int64_t *tgt_len,
+                                    int T, int B, int C, int S,
+                                    int32_t *path, float *score,
+                                    void *workspace, void *stream);
+int ctc_amd_binary_best_path_typed(const void *x, int x_dtype, int64_t stride_t, int64_t stride_b, const float *y,
+                                   const int64_t *in_len, const int64_t *tgt_len,
+                                   int T, int B, int C, int S,
+                                   int32_t *path, float *score, void *workspace, void *stream);
+int ctc_amd_noblank_token_spans_typed(const void *x, int x_dtype, int64_t stride_t, int64_t stride_b,
+                                      const void *labels, int labels_i64,
+                                      const int64_t *in_len, const int64_t *tgt_len,
+                                      int T, int B, int C, int S,
+                                      int32_t *path, float *score, float *nll, float *frame_conf,
+                                      int32_t *start, int32_t *end, float *conf,
+                                      void *workspace, void *stream);
+int ctc_amd_binary_token_spans_typed(const void *x, int x_dtype, int64_t stride_t, int64_t stride_b, const float *y,
+                                     const int64_t *in_len, const int64_t *tgt_len,
+                                     int T, int B, int C, int S,
+                                     int32_t *path, float *score, float *nll, float *frame_conf,
+                                     int32_t *start, int32_t *end, float *conf,
+                                     void *workspace, void *stream);
+int ctc_amd_noblank_posteriors_typed(const void *x, int x_dtype, int64_t stride_t, int64_t stride_b,
+                                     const void *labels, int labels_i64,
+                                     const int64_t *in_len, const int64_t *tgt_len,
+                                     int T, int B, int C, int S,
+                                     float *nll, float *gamma,
+                                     void *workspace, void *stream);
+int ctc_amd_binary_posteriors_typed(const void *x, int x_dtype, int64_t stride_t, int64_t stride_b, const float *y,
+                                    const int64_t *in_len, const int64_t *tgt_len,
+                                    int T, int B, int C, int S,
+                                    float *nll, float *gamma,
+                                    void *workspace, void *stream);
+
 /* The producer step of the logits: one torch.nn.LSTMCell step of the reference's LSTM_cell.forward
  * (LSTM.py:39-51: `v_hsn, v_csn = self.v_cell(v, (v_hsn, v_csn)); v_series[time] = v_hsn`), fused with the write of
  * the hidden state into the logits tensor the losses read.
