@@ -108,6 +108,10 @@ PROTOTYPES = {
                                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ctc_amd_binary_token_spans_typed": (_int, [_vp, _int, _i64, _i64, _vp, _vp, _vp, _int, _int, _int, _int,
                                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # evaluation: frames -> tokens with spans, tokens -> distance from the reference transcript
+    "ctc_amd_collapse_frames": (_int, [_vp, _int, _i64, _i64, _vp, _vp, _i64, _i64, _int, _int, _int, _int,
+                                       _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ctc_amd_edit_distance": (_int, [_vp, _int, _i64, _vp, _vp, _int, _i64, _vp, _int, _int, _int, _vp, _vp]),
 }
 
 _lib = None

@@ -863,3 +863,114 @@ def dedup_multihot_targets(rows, exact_rows=False):
     if rc:
         _lib.check(rc, "ctc_amd_dedup_multihot_targets")
     return out, length
+
+
+class CollapsedTokens(NamedTuple):
+    """What ``collapse_frames`` returns (shapes and meanings: its docstring)."""
+    tokens: torch.Tensor
+    lengths: torch.Tensor
+    start: torch.Tensor
+    end: torch.Tensor
+    conf: torch.Tensor
+
+
+EDIT_DISTANCE_MAX_REF = 1023       # ctc_amd_edit_distance: M <= 1023, the one limit on target widths (BLANK_MAX_LABELS)
+
+
+def _eval_labels(t, name, batch=None):
+    """a [B,*] int32 / int64 tensor on a HIP device, or ValueError (rank, dtype, device, batch size)"""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype not in (torch.int32, torch.int64):
+        raise ValueError("ctc_amd: %s must be an int32 or int64 tensor of rank 2" % name)
+    if not t.is_cuda:
+        raise ValueError("ctc_amd: %s must be on a HIP (cuda) device -- the engine has no CPU path" % name)
+    if batch is not None and t.shape[0] != batch:
+        raise ValueError("ctc_amd: %s has %d rows, the batch has %d" % (name, t.shape[0], batch))
+    return t.detach()
+
+
+def collapse_frames(frames, input_lengths, blank=None, frame_conf=None, max_tokens=None):
+    """Per-frame decisions to tokens with frame spans, on the device -> ``CollapsedTokens(tokens, lengths, start, end,
+    conf)``: maximal runs of equal labels are merged and the runs of ``blank`` dropped.
+
+    ``frames`` [B,T] int32 / int64 on a HIP device, any strides (the ``.t()`` view of a [T,B] tensor takes no copy): the
+    greedy decision ``logits.argmax(-1).t()``, the classes along ``blank_best_path``'s path, or the per-frame label
+    positions of ``noblank_best_path`` / ``binary_best_path``.  ``input_lengths`` [B], 0 <= T_b <= T; frames at ``t >=
+    T_b`` are never read.  ``blank``: the class that separates tokens (``a, blank, a`` gives two tokens, ``a, a`` one);
+    ``None``: no blank -- every run is a token, a run of -1 included (the decode of the no-blank and binary lattices).
+
+    * ``tokens`` [B,W] int32, W = ``max_tokens`` (default T): the label of each run; ``lengths`` [B] int64 their number --
+      the true count even where it exceeds W, so a truncation shows.
+    * ``start``, ``end`` [B,W] int32: first and last frame of the run, both inclusive.
+    * ``conf`` [B,W] fp32 when ``frame_conf`` [B,T] fp32 is given (else ``None``): the float32 sum of ``frame_conf`` over
+      the run in ascending t, then one float32 division by the frame count -- a float32 loop reproduces the bits.
+
+    Columns at and beyond ``lengths[b]`` hold -1 / -1 / -1 / 0.  int64 labels are read through their low 32 bits.  One
+    launch, no host synchronisation, capture-safe.  include/ctc_amd.h, DESIGN.md 3.12."""
+    fr = _eval_labels(frames, "frames")
+    B, T = fr.shape
+    dev = fr.device
+    W = T if max_tokens is None else int(max_tokens)
+    if T < 1 or B < 1 or W < 1:
+        raise ValueError("ctc_amd: collapse_frames needs B, T and max_tokens >= 1, got B=%d, T=%d, max_tokens=%d" % (B, T, W))
+    fc = None
+    if frame_conf is not None:
+        if not isinstance(frame_conf, torch.Tensor) or frame_conf.dtype != torch.float32 \
+                or tuple(frame_conf.shape) != (B, T):
+            raise ValueError("ctc_amd: frame_conf must be float32 [B,T] = [%d,%d]" % (B, T))
+        if frame_conf.device != dev:
+            raise ValueError("ctc_amd: frame_conf must be on the device of frames")
+        fc = frame_conf.detach()
+    il = _lengths(input_lengths, B, "input_lengths", dev, T, lo=0)
+    tokens = torch.empty((B, W), dtype=torch.int32, device=dev)
+    start = torch.empty((B, W), dtype=torch.int32, device=dev)
+    end = torch.empty((B, W), dtype=torch.int32, device=dev)
+    conf = torch.empty((B, W), dtype=torch.float32, device=dev) if fc is not None else None
+    lengths = torch.empty(B, dtype=torch.int64, device=dev)
+    with _on_device(dev):
+        rc = _lib.load().ctc_amd_collapse_frames(
+            fr.data_ptr(), int(fr.dtype is torch.int64), fr.stride(0), fr.stride(1), il.data_ptr(),
+            None if fc is None else fc.data_ptr(), 0 if fc is None else fc.stride(0), 0 if fc is None else fc.stride(1),
+            T, B, -1 if blank is None else int(blank), W, tokens.data_ptr(), lengths.data_ptr(), start.data_ptr(),
+            end.data_ptr(), None if conf is None else conf.data_ptr(), _stream_handle(dev))
+    _lib.check(rc, "ctc_amd_collapse_frames")
+    return CollapsedTokens(tokens, lengths, start, end, conf)
+
+
+def edit_distance(hyp, hyp_lengths, ref, ref_lengths):
+    """Levenshtein distance (unit costs) between ``hyp[b,:hyp_lengths[b]]`` and ``ref[b,:ref_lengths[b]]`` -> ``dist``
+    [B] int32, on the device.  ``hyp`` [B,N], ``ref`` [B,M] int32 / int64 on a HIP device (the two dtypes may differ; any
+    batch stride, so a row slice of a wider tensor takes no copy); lengths may be 0 and elements beyond a length are never
+    read.  M <= 1023, the limit on target widths everywhere here (``CtcAmdError`` beyond); any N.  Exact; one launch, no
+    host synchronisation, capture-safe.  include/ctc_amd.h, DESIGN.md 3.12."""
+    h = _eval_labels(hyp, "hyp")
+    B, N = h.shape
+    r = _eval_labels(ref, "ref", B)
+    M = r.shape[1]
+    dev = h.device
+    if r.device != dev:
+        raise ValueError("ctc_amd: hyp and ref must be on the same device")
+    if B < 1:
+        raise ValueError("ctc_amd: edit_distance needs B >= 1")
+    if N > 1 and h.stride(1) != 1:
+        h = h.contiguous()
+    if M > 1 and r.stride(1) != 1:
+        r = r.contiguous()
+    hl = _lengths(hyp_lengths, B, "hyp_lengths", dev, N, lo=0)
+    rl = _lengths(ref_lengths, B, "ref_lengths", dev, M, lo=0)
+    dist = torch.empty(B, dtype=torch.int32, device=dev)
+    with _on_device(dev):
+        rc = _lib.load().ctc_amd_edit_distance(
+            h.data_ptr() if N else None, int(h.dtype is torch.int64), h.stride(0), hl.data_ptr(),
+            r.data_ptr() if M else None, int(r.dtype is torch.int64), r.stride(0), rl.data_ptr(),
+            B, N, M, dist.data_ptr(), _stream_handle(dev))
+    _lib.check(rc, "ctc_amd_edit_distance")
+    return dist
+
+
+def label_error_rate(hyp, hyp_lengths, ref, ref_lengths):
+    """The standard CTC metric -> ``(ler, dist)``: ``dist`` [B] int32 is ``edit_distance``'s, ``ler = sum(dist) /
+    max(sum(ref_lengths), 1)`` a 0-dim float32 tensor on the device (the sums are integer; no host synchronisation)."""
+    dist = edit_distance(hyp, hyp_lengths, ref, ref_lengths)
+    rl = _lengths(ref_lengths, dist.shape[0], "ref_lengths", dist.device, ref.shape[1], lo=0)
+    ler = dist.sum(dtype=torch.int64).to(torch.float32) / rl.sum().clamp(min=1).to(torch.float32)
+    return ler, dist

@@ -805,6 +805,55 @@ int ctc_amd_head_backward_wide_typed(const float *d_out, int64_t dout_stride_t, 
                                      float *d_weight, float *d_bias, float *d_bn_weight, float *d_bn_bias,
                                      void *scratch, size_t scratch_bytes, void *stream);
 
+/* Evaluation: from per-frame decisions to a token sequence, and from a token sequence to its distance
+ * from the reference transcript.  Target-free: no logits, no lattice, no workspace.  Both entries are integer-exact, use
+ * no atomics and no waiting between workgroups (deterministic), allocate nothing and never synchronise the host.
+ * int64 labels are read through their low 32 bits, as everywhere in this library (class indices and -1 fit).
+ *
+ * ctc_amd_collapse_frames: merge maximal runs of equal labels, drop the blank runs.
+ *   frames     label of frame t of sample b at frames[b * stride_b + t * stride_t] (strides in elements; int32, or int64
+ *              with frames_i64 = 1): a [B,T] tensor, a [T,B] one (argmax of [T,B,C]) or a slice of a wider batch alike --
+ *              a best path (ctc_amd_blank_best_path: collapse the path's classes; ctc_amd_noblank_best_path /
+ *              ctc_amd_binary_best_path: the label positions themselves, blank < 0) or logits.argmax(-1)
+ *   in_len     [B] int64, 0 <= T_b <= T (clamped to that range); frames t >= T_b are never read
+ *   blank      >= 0: runs of this label separate tokens and are dropped (a, blank, a -> two tokens; a, a -> one);
+ *              < 0: there is no blank -- every run is a token, a run of -1 (a failed best path) included
+ *   frame_conf per-frame confidence at frame_conf[b * conf_stride_b + t * conf_stride_t], or NULL; NULL exactly when conf is
+ *   tokens     [B,W] int32 out: the label of the run (its low 32 bits)
+ *   out_len    [B] int64 out: the number of tokens -- the true count even when it exceeds W (the first W are stored)
+ *   start, end [B,W] int32 out: first and last frame of the run, both INCLUSIVE
+ *   conf       [B,W] fp32 out or NULL: the sum of frame_conf over start .. end -- from 0.0f, in ascending t, in fp32 --
+ *              followed by one correctly rounded fp32 division by float(end - start + 1).  The order is part of the
+ *              contract: a float32 loop in that order reproduces the bits.
+ * Columns at and beyond out_len[b] hold -1 / -1 / -1 / 0: every element of every output is written.
+ * NULL pointers (conf and frame_conf apart: both or neither), T, B or W < 1: CTC_AMD_ERR_BAD_ARGUMENT before any HIP
+ * call.  One workgroup per sample keeps the sample's labels and the spans of its first min(W, T) tokens in LDS:
+ * 4 (T + 2 min(W, T) + 1) bytes <= 160 KB -- every T <= 13653 with any W (T <= 40957 at W = 1);
+ * CTC_AMD_ERR_UNSUPPORTED_SHAPE beyond. */
+int ctc_amd_collapse_frames(const void *frames, int frames_i64,
+                            int64_t stride_b, int64_t stride_t,
+                            const int64_t *in_len,
+                            const float *frame_conf, int64_t conf_stride_b, int64_t conf_stride_t,
+                            int T, int B, int blank, int W,
+                            int32_t *tokens, int64_t *out_len,
+                            int32_t *start, int32_t *end, float *conf,
+                            void *stream);
+
+/* ctc_amd_edit_distance: dist[b] = the Levenshtein distance (insertions, deletions, substitutions, unit costs) between
+ * hyp[b, :hyp_len[b]] and ref[b, :ref_len[b]] -- the numerator of the label error rate.
+ *   hyp  [B,N], ref [B,M]: row b at hyp + b * hyp_stride_b / ref + b * ref_stride_b (strides in elements), unit stride
+ *        inside a row; int32, or int64 with hyp_i64 / ref_i64 = 1 (the two may differ).  A pointer may be NULL only
+ *        where its width is 0.
+ *   hyp_len, ref_len [B] int64, 0 <= . <= N / M (clamped to that range); elements beyond a length are never read
+ *   dist [B] int32 out
+ * NULL pointers, B < 1, N < 0 or M < 0: CTC_AMD_ERR_BAD_ARGUMENT; M > 1023, the library's one limit on target widths:
+ * CTC_AMD_ERR_UNSUPPORTED_SHAPE; both before any HIP call.  Any N >= 0 (a hypothesis may be as long as T).
+ * One wave per sample holds the row of the recurrence over the reference in registers (1, 2, 4, 8 or 16 cells per lane
+ * for M <= 64, 128, 256, 512, 1023) and steps through the hypothesis. */
+int ctc_amd_edit_distance(const void *hyp, int hyp_i64, int64_t hyp_stride_b, const int64_t *hyp_len,
+                          const void *ref, int ref_i64, int64_t ref_stride_b, const int64_t *ref_len,
+                          int B, int N, int M, int32_t *dist, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
