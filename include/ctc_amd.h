@@ -92,7 +92,9 @@ int ctc_amd_noblank_loss_grad(const float *x, int64_t stride_t, int64_t stride_b
  * everything else as ctc_amd_noblank_loss_grad; grad = grad_scale * ((1 - b) softmax - a occupancy - b) with
  * b = (1 - lambda)/C, a = lambda - b.  The reference never runs this code (parity unpinned: checked against
  * the numpy restatement and finite differences).  Shapes: C even <= 256, S <= 31, T <= 168, 8-byte aligned
- * rows (the four-rows-per-wave kernel); others return CTC_AMD_ERR_UNSUPPORTED_SHAPE.  lambda in [0, 1]. */
+ * rows (the four-rows-per-wave kernel); others return CTC_AMD_ERR_UNSUPPORTED_SHAPE.  lambda in [0, 1].
+ * Every one of the C columns counts as a class in the sum over n, so do not combine this entry with a pad column
+ * (LSTM_cell(pad_classes=True): its lp = -1e30 enters every frame's emission and every sample reports nll >= 1e12). */
 int ctc_amd_noblank_smoothed_loss_grad(const float *x, int64_t stride_t, int64_t stride_b,
                                        const void *labels, int labels_i64,
                                        const int64_t *in_len, const int64_t *tgt_len,
