@@ -112,6 +112,10 @@ PROTOTYPES = {
     "ctc_amd_collapse_frames": (_int, [_vp, _int, _i64, _i64, _vp, _vp, _i64, _i64, _int, _int, _int, _int,
                                        _vp, _vp, _vp, _vp, _vp, _vp]),
     "ctc_amd_edit_distance": (_int, [_vp, _int, _i64, _vp, _vp, _int, _i64, _vp, _int, _int, _int, _vp, _vp]),
+    # decoding without a transcript: prefix beam search on the blank (blank >= 0) and the no-blank lattice
+    "ctc_amd_beam_search_scratch_bytes": (_sz, [_int, _int, _int]),
+    "ctc_amd_beam_search": (_int, [_vp, _i64, _i64, _vp, _int, _int, _int, _int, _int, _int, _int, _int,
+                                   _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -974,3 +974,87 @@ def label_error_rate(hyp, hyp_lengths, ref, ref_lengths):
     rl = _lengths(ref_lengths, dist.shape[0], "ref_lengths", dist.device, ref.shape[1], lo=0)
     ler = dist.sum(dtype=torch.int64).to(torch.float32) / rl.sum().clamp(min=1).to(torch.float32)
     return ler, dist
+
+
+class BeamHypotheses(NamedTuple):
+    """What ``blank_beam_search`` / ``noblank_beam_search`` return (shapes and meanings: their docstrings)."""
+    tokens: torch.Tensor
+    lengths: torch.Tensor
+    scores: torch.Tensor
+    count: torch.Tensor
+
+
+BEAM_MAX_WIDTH = 64                # ctc_amd_beam_search: 1 <= nbest <= beam_width <= 64
+BEAM_MAX_CLASSES = 32              # ... and 1 <= top_classes <= 32
+
+
+def _beam_search(x, name, input_lengths, beam_width, nbest, top_classes, blank, max_tokens):
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.dtype != torch.float32:
+        raise ValueError("ctc_amd: %s must be a float32 tensor [T,B,C]" % name)
+    T, B, C = x.shape
+    W, N, K = int(beam_width), int(nbest), int(top_classes)
+    L = T if max_tokens is None else int(max_tokens)
+    if T < 1 or B < 1 or C < 2:
+        raise ValueError("ctc_amd: %s needs T >= 1, B >= 1 and C >= 2, got %s" % (name, tuple(x.shape)))
+    if not 1 <= N <= W <= BEAM_MAX_WIDTH:
+        raise ValueError("ctc_amd: beam search needs 1 <= nbest <= beam_width <= %d, got nbest=%d, beam_width=%d"
+                         % (BEAM_MAX_WIDTH, N, W))
+    if not 1 <= K <= BEAM_MAX_CLASSES:
+        raise ValueError("ctc_amd: beam search needs 1 <= top_classes <= %d, got %d" % (BEAM_MAX_CLASSES, K))
+    if L < 1:
+        raise ValueError("ctc_amd: beam search needs max_tokens >= 1, got %d" % L)
+    if blank is not None and not 0 <= int(blank) < C:
+        raise ValueError("ctc_amd: blank must lie in [0, %d), got %d" % (C, int(blank)))
+    if not x.is_cuda:
+        raise ValueError("ctc_amd: %s must be on a HIP (cuda) device -- the engine has no CPU path" % name)
+    K = min(K, C if blank is None else C - 1)
+    dev = x.device
+    xs = x.detach()
+    if xs.stride(2) != 1:
+        xs = xs.contiguous()
+    il = _lengths(input_lengths, B, "input_lengths", dev, T, lo=0)
+    tokens = torch.empty((B, N, L), dtype=torch.int32, device=dev)
+    lengths = torch.empty((B, N), dtype=torch.int64, device=dev)
+    scores = torch.empty((B, N), dtype=torch.float32, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    need = lib.ctc_amd_beam_search_scratch_bytes(T, B, W)
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    with _on_device(dev):
+        rc = lib.ctc_amd_beam_search(xs.data_ptr(), xs.stride(0), xs.stride(1), il.data_ptr(), T, B, C,
+                                     -1 if blank is None else int(blank), W, K, N, L, tokens.data_ptr(),
+                                     lengths.data_ptr(), scores.data_ptr(), count.data_ptr(), scratch.data_ptr(), need,
+                                     _stream_handle(dev))
+    _lib.check(rc, "ctc_amd_beam_search")
+    return BeamHypotheses(tokens, lengths, scores, count)
+
+
+def blank_beam_search(log_probs, input_lengths, beam_width=16, nbest=1, top_classes=16, blank=0, max_tokens=None):
+    """CTC prefix beam search on the blank lattice, on the device -> ``BeamHypotheses(tokens, lengths, scores, count)``:
+    the ``nbest`` most probable LABEL SEQUENCES of each sample, best first.  A sequence's probability is the sum over all
+    of its alignments, so this is not ``argmax`` + ``collapse_frames`` (the best single alignment).
+
+    ``log_probs`` [T,B,C] float32 normalised log-probabilities on a HIP device (the contract of ``blank_ctc_loss``), any
+    frame / batch strides (a view with another class stride is made contiguous); ``input_lengths`` [B], 0 <= T_b <= T.
+    Per frame every prefix of the beam is extended by the ``top_classes`` (<= 32, clamped to C - 1) non-blank classes of
+    the largest inputs and the ``beam_width`` (<= 64) most probable prefixes are kept; ties go to a prefix that stays over
+    one that is extended, then to the lower beam slot, then to the more probable class (include/ctc_amd.h states the
+    rules in full).
+
+    * ``tokens`` [B,nbest,L] int32, L = ``max_tokens`` (default T), -1 behind a sequence's end; ``lengths`` [B,nbest] int64,
+      the true token count even where it exceeds L, so a truncation shows.
+    * ``scores`` [B,nbest] float32: natural-log probability of the sequence as the search summed it -- at most the exact
+      ``-nll`` of that sequence, equal to it when nothing of it was pruned.
+    * ``count`` [B] int32: the hypotheses that exist; rows at and beyond it hold -1 / 0 / -inf.  T_b = 0 gives the one
+      empty hypothesis with score 0.
+
+    One launch, no host synchronisation, capture-safe (the scratch tensor, 8 B (T beam_width + 1) bytes, is allocated
+    here), deterministic.  NaN inputs give an unspecified result.  DESIGN.md 3.13."""
+    return _beam_search(log_probs, "log_probs", input_lengths, beam_width, nbest, top_classes, int(blank), max_tokens)
+
+
+def noblank_beam_search(logits, input_lengths, beam_width=16, nbest=1, top_classes=16, max_tokens=None):
+    """``blank_beam_search`` on the no-blank lattice: ``logits`` [T,B,C] float32 RAW logits, as for every other
+    ``noblank_*`` function -- the kernel subtracts each row's log-sum-exp itself, in fp32.  There is no blank: a label
+    sequence has no equal neighbours, the empty sequence exists only for T_b = 0, and ``top_classes`` is clamped to C."""
+    return _beam_search(logits, "logits", input_lengths, beam_width, nbest, top_classes, None, max_tokens)

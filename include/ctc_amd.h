@@ -856,6 +856,43 @@ int ctc_amd_edit_distance(const void *hyp, int hyp_i64, int64_t hyp_stride_b, co
                           const void *ref, int ref_i64, int64_t ref_stride_b, const int64_t *ref_len,
                           int B, int N, int M, int32_t *dist, void *stream);
 
+/* Decoding without a transcript: CTC prefix beam search, the most probable LABEL SEQUENCES of each sample
+ * -- a sequence's probability is the sum over all of its alignments, which argmax + ctc_amd_collapse_frames (the best
+ * single alignment) does not give.  One launch, one workgroup per sample; no atomics, no waiting between workgroups
+ * (deterministic: the same inputs give the same bits), no allocation and no host synchronisation.
+ *
+ * ctc_amd_beam_search_scratch_bytes: the bytes `scratch` must hold -- 8 B (T W + 1), the trie of prefixes; 0 when T, B or
+ *   W is out of range.  The caller allocates; the contents before and after a call mean nothing.
+ * ctc_amd_beam_search:
+ *   x          [T,B,C] fp32 at x[t * stride_t + b * stride_b + c] (strides in elements, unit class stride).  blank >= 0:
+ *              normalised log-probabilities, the contract of ctc_amd_blank_loss_grad.  blank < 0: the no-blank lattice,
+ *              x holds raw logits and the kernel subtracts each row's log-sum-exp in fp32.
+ *   in_len     [B] int64, 0 <= T_b <= T (clamped to that range); frames t >= T_b are never read
+ *   W, K, N, L beam width (1 .. 64); classes a prefix is extended by per frame (1 .. 32, clamped to the number of
+ *              non-blank classes); hypotheses written per sample (1 .. W); token columns per hypothesis (>= 1)
+ *   tokens     [B,N,L] int32 out; lengths [B,N] int64 out: the true token count, also beyond L (the first L are stored,
+ *              the rest of the row holds -1); scores [B,N] fp32 out: natural-log probability of the label sequence as the
+ *              search summed it (a lower bound of the exact value: alignments through pruned prefixes are missing);
+ *              count [B] int32 out: the hypotheses that exist, <= N.  Hypotheses are sorted best first; rows at and
+ *              beyond count[b] hold -1 / 0 / -inf: every element of every output is written.  T_b = 0: the one empty
+ *              hypothesis, score 0.
+ * The search, per frame of row lp (x, or x - logsumexp(x)): the class candidates are the K non-blank classes of the largest
+ * x[t,b,c] (ties to the lower class, -inf left out).  Beam i (pb, pnb: log probability of its prefix ending in blank / in
+ * a label; tot = logaddexp(pb, pnb)) stays with pb' = tot + lp[blank], pnb' = pnb + lp[last] and is extended by candidate
+ * c with v = lp[c] + (c == last ? pb : tot); an extension that is the prefix of a beam j (j's parent prefix is beam i's,
+ * j's last token is c) is added into j's pnb', every other one is a candidate with pb' = -inf, pnb' = v.  The W best
+ * candidates of score logaddexp(pb', pnb') > -inf are kept under the total order: score descending, stay before
+ * extension, beam slot ascending, class rank ascending.  The no-blank lattice has no pb: lp[blank] counts as -inf.
+ * NaN inputs: the result is unspecified, the launch ends.
+ * A NULL pointer, T or B < 1, C < 2, blank >= C, W, K, N or L out of range (N <= W), scratch_bytes below
+ * ctc_amd_beam_search_scratch_bytes(T, B, W): CTC_AMD_ERR_BAD_ARGUMENT before any HIP call.  Any C: the row is streamed. */
+size_t ctc_amd_beam_search_scratch_bytes(int T, int B, int W);
+int ctc_amd_beam_search(const float *x, int64_t stride_t, int64_t stride_b, const int64_t *in_len,
+                        int T, int B, int C, int blank /* < 0: the no-blank lattice, x raw logits */,
+                        int W, int K, int N, int L,
+                        int32_t *tokens, int64_t *lengths, float *scores, int32_t *count,
+                        void *scratch, size_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
