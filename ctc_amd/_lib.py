@@ -116,6 +116,9 @@ PROTOTYPES = {
     "ctc_amd_beam_search_scratch_bytes": (_sz, [_int, _int, _int]),
     "ctc_amd_beam_search": (_int, [_vp, _i64, _i64, _vp, _int, _int, _int, _int, _int, _int, _int, _int,
                                    _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # ... fused with a bigram table (language model / transition grammar) and a token bonus
+    "ctc_amd_beam_search_lm": (_int, [_vp, _i64, _i64, _vp, _int, _int, _int, _int, _int, _int, _int, _int,
+                                      _vp, _i64, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

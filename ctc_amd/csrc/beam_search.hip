@@ -23,6 +23,11 @@
 //   select   every wave extracts the W largest of its keys (W wave reductions, no barrier);                       barrier
 //            the 4 W keys are ranked by counting; the key of rank r < W becomes beam r of the next frame.          barrier
 // After the last frame the beams are in final order (the selection key of a frame is the final score of its prefix).
+//
+// beam_search_kernel<true> is the same search under a bigram table: every beam carries g, the sum of its
+// tokens' increments lm_weight lm[previous or C][c] + token_bonus, which enters the selection keys; an extension thread
+// gathers its table entry first thing behind the barrier that publishes the class list.  beam_search_kernel<false> is the
+// plain search: no instruction of it knows of the table.
 #include <limits.h>
 
 #include "common.hpp"
@@ -52,6 +57,17 @@ struct BeamParams {
     int32_t *count;                             // [B]
     int2 *trie;                                 // [B][T W + 1] (parent, token)
 };
+
+// the fused search: a bigram table beside the acoustic search.  The plain kernel's arguments come first
+// and unchanged, so the LM = false instantiation is the kernel it was.
+struct BeamLmParams : BeamParams {
+    const float *lm;                            // [C + 1][C] through lm_stride, unit column stride; row C: the first token
+    int64_t lm_stride;
+    float lm_weight, token_bonus;
+    float *ctc_scores;                          // [B][N]
+};
+template <bool LM> struct BeamArgs { typedef BeamParams type; };
+template <> struct BeamArgs<true> { typedef BeamLmParams type; };
 
 // fp32 -> 32 bits whose unsigned order is the order of the values (-inf lowest; -0 has become +0 before)
 __device__ __forceinline__ unsigned ordered_bits(float f)
@@ -142,7 +158,11 @@ __device__ __forceinline__ void load_row_pass(float (&v)[kRowRegs], const float 
     }
 }
 
-__global__ __launch_bounds__(kBeamThreads) void beam_search_kernel(BeamParams p)
+// LM: every beam carries g, the sum of lm_weight lm[last or C][c] + token_bonus over its tokens, beside (pb, pnb).  A
+// candidate's selection key is its acoustic score + g; an extension whose table entry is -inf is no candidate; an extension
+// merged into the beam that is its prefix adds its acoustic value alone (that beam's g was formed from the same numbers).
+template <bool LM>
+__global__ __launch_bounds__(kBeamThreads) void beam_search_kernel(typename BeamArgs<LM>::type p)
 {
     __shared__ key_t s_list[kBeamWaves * kBeamMaxW];            // the waves' extracted keys: 4 K of the row, 4 W candidates
     __shared__ float s_pb[2][kBeamMaxW], s_pnb[2][kBeamMaxW];
@@ -152,6 +172,8 @@ __global__ __launch_bounds__(kBeamThreads) void beam_search_kernel(BeamParams p)
     __shared__ int s_cls[kBeamMaxK];
     __shared__ float s_clp[kBeamMaxK];
     __shared__ float s_red[2 * kBeamWaves];                     // no-blank lattice: the waves' (max, sum exp)
+    __shared__ float s_g[2][LM ? kBeamMaxW : 1];                // LM: the beams' g
+    __shared__ float s_extg[LM ? kBeamMaxW * kBeamMaxK : 1];    // LM: g of extension (beam, rank), beside s_ext
 
     const float ninf = -__builtin_inff();
     const int b = blockIdx.x, tid = threadIdx.x, lane = lane_id(), wave = wave_id();
@@ -168,6 +190,7 @@ __global__ __launch_bounds__(kBeamThreads) void beam_search_kernel(BeamParams p)
     if (tid == 0) {
         s_pb[0][0] = 0.0f; s_pnb[0][0] = ninf;
         s_last[0][0] = -1; s_node[0][0] = 0; s_par[0][0] = -1; s_len[0][0] = 0;
+        if constexpr (LM) s_g[0][0] = 0.0f;
     }
     float ahead[kRowRegs] = {ninf, ninf, ninf, ninf};           // the first pass of the next frame's row
     if (Tb > 0) load_row_pass(ahead, xb, 0, C, tid);
@@ -272,18 +295,34 @@ __global__ __launch_bounds__(kBeamThreads) void beam_search_kernel(BeamParams p)
                     }
                     s_spb[i] = spb;
                     s_spnb[i] = spnb;
-                    const float score = beam_lae(spb, spnb);
+                    float score = beam_lae(spb, spnb);
+                    if constexpr (LM) score += s_g[cur][i];
                     if (score > ninf) ck[q] = make_key(score, kTieMask - (unsigned)(i << 5));
                 }
             } else if (idx < ncand) {
                 const int e = idx - W, i = e / K, r = e - i * K;
                 if (i < nbeam && r < ncls) {
                     const int c = s_cls[r], node = s_node[cur][i];
+                    // LM: the table entry of this extension, asked for as soon as the class list stands -- one dependent
+                    // gather from L2, in flight across the W-long comparison below.  Row: the beam's own last token or C;
+                    // column: a class of the kernel's list (never the blank; never the diagonal on the no-blank lattice).
+                    float entry = ninf;
+                    if constexpr (LM) {
+                        const int last = s_last[cur][i];
+                        if (blank >= 0 || c != last) entry = p.lm[(int64_t)(last < 0 ? C : last) * p.lm_stride + c];
+                    }
                     const float v = s_clp[r] + (c == s_last[cur][i] ? s_pb[cur][i] : s_tot[i]);
                     bool is_beam = false;
                     for (int j = 0; j < nbeam; ++j) is_beam |= s_par[cur][j] == node && s_last[cur][j] == c;
                     s_ext[e] = v;
-                    if (!is_beam && v > ninf) ck[q] = make_key(v, kTieMask - (unsigned)(kExtBit | (i << 5) | r));
+                    if constexpr (LM) {
+                        const float g = s_g[cur][i] + (p.lm_weight * entry + p.token_bonus);
+                        s_extg[e] = g;
+                        if (!is_beam && entry > ninf && v + g > ninf)
+                            ck[q] = make_key(v + g, kTieMask - (unsigned)(kExtBit | (i << 5) | r));
+                    } else {
+                        if (!is_beam && v > ninf) ck[q] = make_key(v, kTieMask - (unsigned)(kExtBit | (i << 5) | r));
+                    }
                 }
             }
         }
@@ -303,6 +342,7 @@ __global__ __launch_bounds__(kBeamThreads) void beam_search_kernel(BeamParams p)
                 s_node[nx][rank] = node;
                 s_par[nx][rank] = s_node[cur][i];
                 s_len[nx][rank] = s_len[cur][i] + 1;
+                if constexpr (LM) s_g[nx][rank] = s_extg[i * K + r];
                 trie[node] = make_int2(s_node[cur][i], c);
             } else {
                 s_pb[nx][rank] = s_spb[i];
@@ -311,6 +351,7 @@ __global__ __launch_bounds__(kBeamThreads) void beam_search_kernel(BeamParams p)
                 s_node[nx][rank] = s_node[cur][i];
                 s_par[nx][rank] = s_par[cur][i];
                 s_len[nx][rank] = s_len[cur][i];
+                if constexpr (LM) s_g[nx][rank] = s_g[cur][i];
             }
         }
         nbeam = min(nz, W);
@@ -327,7 +368,13 @@ __global__ __launch_bounds__(kBeamThreads) void beam_search_kernel(BeamParams p)
         const bool have = tid < cnt;
         const int len = have ? s_len[cur][tid] : 0;
         p.lengths[o] = len;
-        p.scores[o] = have ? beam_lae(s_pb[cur][tid], s_pnb[cur][tid]) : ninf;
+        const float acoustic = have ? beam_lae(s_pb[cur][tid], s_pnb[cur][tid]) : ninf;
+        if constexpr (LM) {
+            p.scores[o] = have ? acoustic + s_g[cur][tid] : ninf;
+            p.ctc_scores[o] = acoustic;
+        } else {
+            p.scores[o] = acoustic;
+        }
         int node = have ? s_node[cur][tid] : 0;
         for (int pos = len - 1; pos >= 0; --pos) {                              // len <= T_b
             if (node <= 0 || node >= nodes) break;                              // (memory safety; never taken)
@@ -358,21 +405,50 @@ extern "C" size_t ctc_amd_beam_search_scratch_bytes(int T, int B, int W)
     return (size_t)B * ((size_t)T * W + 1) * sizeof(int2);
 }
 
-extern "C" int ctc_amd_beam_search(const float *x, int64_t stride_t, int64_t stride_b, const int64_t *in_len,
-                                   int T, int B, int C, int blank, int W, int K, int N, int L,
-                                   int32_t *tokens, int64_t *lengths, float *scores, int32_t *count,
-                                   void *scratch, size_t scratch_bytes, void *stream)
+// the checks both entries share, and the plain kernel's arguments
+static int beam_params(BeamParams &p, const float *x, int64_t stride_t, int64_t stride_b, const int64_t *in_len,
+                       int T, int B, int C, int blank, int W, int K, int N, int L,
+                       int32_t *tokens, int64_t *lengths, float *scores, int32_t *count,
+                       void *scratch, size_t scratch_bytes)
 {
     if (!x || !in_len || !tokens || !lengths || !scores || !count || !scratch) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (!beam_sizes_ok(T, B, W) || C < 2 || blank >= C) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (N < 1 || N > W || K < 1 || K > kBeamMaxK || L < 1 || (int64_t)N * L > INT_MAX) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (scratch_bytes < ctc_amd_beam_search_scratch_bytes(T, B, W)) return CTC_AMD_ERR_BAD_ARGUMENT;
-    BeamParams p;
     p.x = x; p.st = stride_t; p.sb = stride_b; p.in_len = in_len;
     p.T = T; p.B = B; p.C = C; p.blank = blank < 0 ? -1 : blank;
     const int classes = blank < 0 ? C : C - 1;                  // the classes a prefix can be extended by
     p.W = W; p.K = K < classes ? K : classes; p.N = N; p.L = L;
     p.tokens = tokens; p.lengths = lengths; p.scores = scores; p.count = count;
     p.trie = static_cast<int2 *>(scratch);
-    return launch<beam_search_kernel>(dim3(B), dim3(kBeamThreads), 0, static_cast<hipStream_t>(stream), p);
+    return 0;
+}
+
+extern "C" int ctc_amd_beam_search(const float *x, int64_t stride_t, int64_t stride_b, const int64_t *in_len,
+                                   int T, int B, int C, int blank, int W, int K, int N, int L,
+                                   int32_t *tokens, int64_t *lengths, float *scores, int32_t *count,
+                                   void *scratch, size_t scratch_bytes, void *stream)
+{
+    BeamParams p;
+    const int rc = beam_params(p, x, stride_t, stride_b, in_len, T, B, C, blank, W, K, N, L, tokens, lengths, scores, count,
+                               scratch, scratch_bytes);
+    if (rc != 0) return rc;
+    return launch<beam_search_kernel<false>>(dim3(B), dim3(kBeamThreads), 0, static_cast<hipStream_t>(stream), p);
+}
+
+extern "C" int ctc_amd_beam_search_lm(const float *x, int64_t stride_t, int64_t stride_b, const int64_t *in_len,
+                                      int T, int B, int C, int blank, int W, int K, int N, int L,
+                                      const float *lm, int64_t lm_stride, float lm_weight, float token_bonus,
+                                      int32_t *tokens, int64_t *lengths, float *scores, float *ctc_scores, int32_t *count,
+                                      void *scratch, size_t scratch_bytes, void *stream)
+{
+    if (!lm || !ctc_scores || lm_stride < C) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (!(lm_weight >= 0.0f) || !__builtin_isfinite(lm_weight) || !__builtin_isfinite(token_bonus))
+        return CTC_AMD_ERR_BAD_ARGUMENT;
+    BeamLmParams p;
+    const int rc = beam_params(p, x, stride_t, stride_b, in_len, T, B, C, blank, W, K, N, L, tokens, lengths, scores, count,
+                               scratch, scratch_bytes);
+    if (rc != 0) return rc;
+    p.lm = lm; p.lm_stride = lm_stride; p.lm_weight = lm_weight; p.token_bonus = token_bonus; p.ctc_scores = ctc_scores;
+    return launch<beam_search_kernel<true>>(dim3(B), dim3(kBeamThreads), 0, static_cast<hipStream_t>(stream), p);
 }

@@ -22,6 +22,7 @@ The read-outs of the no-blank and the binary lattice (``*_best_path``, ``*_poste
 bfloat16 or float16 logits: 2-byte logits are read as they lie by the ``_typed`` entries of include/ctc_amd.h, and every
 output is bit for bit that of the same call on ``logits.float()``.
 """
+import math
 import os
 from typing import NamedTuple
 
@@ -984,11 +985,36 @@ class BeamHypotheses(NamedTuple):
     count: torch.Tensor
 
 
+class FusedBeamHypotheses(NamedTuple):
+    """What ``blank_beam_search`` / ``noblank_beam_search`` return when a table ``lm`` is given: ``scores`` is the fused
+    score the hypotheses are ordered by, ``ctc_scores`` the acoustic log-probability alone."""
+    tokens: torch.Tensor
+    lengths: torch.Tensor
+    scores: torch.Tensor
+    count: torch.Tensor
+    ctc_scores: torch.Tensor
+
+
 BEAM_MAX_WIDTH = 64                # ctc_amd_beam_search: 1 <= nbest <= beam_width <= 64
 BEAM_MAX_CLASSES = 32              # ... and 1 <= top_classes <= 32
 
 
-def _beam_search(x, name, input_lengths, beam_width, nbest, top_classes, blank, max_tokens):
+def _beam_lm_table(lm, C, dev):
+    """the bigram table as the library is given it: float32 [C+1, C] on `dev`, unit column stride, row stride >= C (such a
+    view is passed as it lies, any other is made contiguous)"""
+    if not isinstance(lm, torch.Tensor) or lm.dtype != torch.float32 or tuple(lm.shape) != (C + 1, C):
+        raise ValueError("ctc_amd: lm must be a float32 tensor [C+1, C] = [%d, %d], got %s" % (
+            C + 1, C, "%s %s" % (lm.dtype, tuple(lm.shape)) if isinstance(lm, torch.Tensor) else type(lm).__name__))
+    if lm.device != dev:
+        raise ValueError("ctc_amd: lm must be on the logits' device %s, got %s" % (dev, lm.device))
+    lm = lm.detach()
+    if lm.stride(1) != 1 or lm.stride(0) < C:
+        lm = lm.contiguous()
+    return lm
+
+
+def _beam_search(x, name, input_lengths, beam_width, nbest, top_classes, blank, max_tokens, lm=None, lm_weight=1.0,
+                 token_bonus=0.0):
     if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.dtype != torch.float32:
         raise ValueError("ctc_amd: %s must be a float32 tensor [T,B,C]" % name)
     T, B, C = x.shape
@@ -1013,6 +1039,15 @@ def _beam_search(x, name, input_lengths, beam_width, nbest, top_classes, blank, 
     if xs.stride(2) != 1:
         xs = xs.contiguous()
     il = _lengths(input_lengths, B, "input_lengths", dev, T, lo=0)
+    alpha, beta = float(lm_weight), float(token_bonus)
+    if lm is None:
+        if alpha != 1.0 or beta != 0.0:
+            raise ValueError("ctc_amd: lm_weight and token_bonus need a table lm (a pure length bonus: a table of zeros)")
+    else:
+        lm = _beam_lm_table(lm, C, dev)
+        if not (math.isfinite(alpha) and alpha >= 0.0 and math.isfinite(beta)):
+            raise ValueError("ctc_amd: beam search needs a finite lm_weight >= 0 and a finite token_bonus, got %r, %r"
+                             % (lm_weight, token_bonus))
     tokens = torch.empty((B, N, L), dtype=torch.int32, device=dev)
     lengths = torch.empty((B, N), dtype=torch.int64, device=dev)
     scores = torch.empty((B, N), dtype=torch.float32, device=dev)
@@ -1020,6 +1055,16 @@ def _beam_search(x, name, input_lengths, beam_width, nbest, top_classes, blank, 
     lib = _lib.load()
     need = lib.ctc_amd_beam_search_scratch_bytes(T, B, W)
     scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    if lm is not None:
+        ctc_scores = torch.empty((B, N), dtype=torch.float32, device=dev)
+        with _on_device(dev):
+            rc = lib.ctc_amd_beam_search_lm(xs.data_ptr(), xs.stride(0), xs.stride(1), il.data_ptr(), T, B, C,
+                                            -1 if blank is None else int(blank), W, K, N, L, lm.data_ptr(), lm.stride(0),
+                                            alpha, beta, tokens.data_ptr(), lengths.data_ptr(), scores.data_ptr(),
+                                            ctc_scores.data_ptr(), count.data_ptr(), scratch.data_ptr(), need,
+                                            _stream_handle(dev))
+        _lib.check(rc, "ctc_amd_beam_search_lm")
+        return FusedBeamHypotheses(tokens, lengths, scores, count, ctc_scores)
     with _on_device(dev):
         rc = lib.ctc_amd_beam_search(xs.data_ptr(), xs.stride(0), xs.stride(1), il.data_ptr(), T, B, C,
                                      -1 if blank is None else int(blank), W, K, N, L, tokens.data_ptr(),
@@ -1029,7 +1074,8 @@ def _beam_search(x, name, input_lengths, beam_width, nbest, top_classes, blank, 
     return BeamHypotheses(tokens, lengths, scores, count)
 
 
-def blank_beam_search(log_probs, input_lengths, beam_width=16, nbest=1, top_classes=16, blank=0, max_tokens=None):
+def blank_beam_search(log_probs, input_lengths, beam_width=16, nbest=1, top_classes=16, blank=0, max_tokens=None,
+                      lm=None, lm_weight=1.0, token_bonus=0.0):
     """CTC prefix beam search on the blank lattice, on the device -> ``BeamHypotheses(tokens, lengths, scores, count)``:
     the ``nbest`` most probable LABEL SEQUENCES of each sample, best first.  A sequence's probability is the sum over all
     of its alignments, so this is not ``argmax`` + ``collapse_frames`` (the best single alignment).
@@ -1049,12 +1095,28 @@ def blank_beam_search(log_probs, input_lengths, beam_width=16, nbest=1, top_clas
       empty hypothesis with score 0.
 
     One launch, no host synchronisation, capture-safe (the scratch tensor, 8 B (T beam_width + 1) bytes, is allocated
-    here), deterministic.  NaN inputs give an unspecified result.  DESIGN.md 3.13."""
-    return _beam_search(log_probs, "log_probs", input_lengths, beam_width, nbest, top_classes, int(blank), max_tokens)
+    here), deterministic.  NaN inputs give an unspecified result.  DESIGN.md 3.13.
+
+    ``lm``: a float32 table [C+1, C] on the same device, shared by the batch -- ``lm[p, c]`` the log-score
+    of token c behind token p, row C that of a first token; a finite entry is a score, ``-inf`` forbids the transition
+    whatever ``lm_weight`` is.  Every token of a prefix adds ``lm_weight * lm[previous or C, c] + token_bonus`` to the
+    score the prefixes are ranked by, frame by frame (shallow fusion with a bigram language model; a 0 / -inf table is a
+    transition grammar; a pure length bonus is a table of zeros).  ``lm_weight`` is finite and >= 0, ``token_bonus``
+    finite; without ``lm`` both must keep their defaults.  The class candidates of a frame are still chosen on
+    ``log_probs`` alone, and the blank's column of ``lm`` is never read.  A view of ``lm`` with unit column stride and a
+    row stride >= C is read as it lies, any other is made contiguous.  With ``lm`` the result is
+    ``FusedBeamHypotheses(tokens, lengths, scores, count, ctc_scores)``: ``scores`` the fused score, which orders the
+    hypotheses, ``ctc_scores`` [B,nbest] float32 the acoustic log-probability alone (what ``scores`` is without ``lm``)."""
+    return _beam_search(log_probs, "log_probs", input_lengths, beam_width, nbest, top_classes, int(blank), max_tokens,
+                        lm, lm_weight, token_bonus)
 
 
-def noblank_beam_search(logits, input_lengths, beam_width=16, nbest=1, top_classes=16, max_tokens=None):
+def noblank_beam_search(logits, input_lengths, beam_width=16, nbest=1, top_classes=16, max_tokens=None,
+                        lm=None, lm_weight=1.0, token_bonus=0.0):
     """``blank_beam_search`` on the no-blank lattice: ``logits`` [T,B,C] float32 RAW logits, as for every other
     ``noblank_*`` function -- the kernel subtracts each row's log-sum-exp itself, in fp32.  There is no blank: a label
-    sequence has no equal neighbours, the empty sequence exists only for T_b = 0, and ``top_classes`` is clamped to C."""
-    return _beam_search(logits, "logits", input_lengths, beam_width, nbest, top_classes, None, max_tokens)
+    sequence has no equal neighbours, the empty sequence exists only for T_b = 0, and ``top_classes`` is clamped to C.
+    ``lm``, ``lm_weight``, ``token_bonus``: as there -- here typically a transition grammar over the classes; the diagonal
+    of ``lm`` is never read.  If row C forbids every class, no hypothesis exists for T_b >= 1 (``count`` 0)."""
+    return _beam_search(logits, "logits", input_lengths, beam_width, nbest, top_classes, None, max_tokens,
+                        lm, lm_weight, token_bonus)

@@ -893,6 +893,34 @@ int ctc_amd_beam_search(const float *x, int64_t stride_t, int64_t stride_b, cons
                         int32_t *tokens, int64_t *lengths, float *scores, int32_t *count,
                         void *scratch, size_t scratch_bytes, void *stream);
 
+/* The same search under a prior over label sequences: shallow fusion with a bigram language model and a
+ * token insertion bonus, or a transition grammar -- one dense table covers both.
+ *   lm           [C+1, C] fp32 at lm[p * lm_stride + c] (lm_stride >= C in elements, unit column stride), shared by the
+ *                batch.  lm[p, c], p < C: the log-score of token c behind token p; row C scores a sequence's first token.
+ *                A finite entry is a score; -inf FORBIDS the transition, whatever lm_weight is.
+ *   lm_weight    alpha, finite and >= 0;  token_bonus  beta, finite
+ *   scores       [B,N] fp32 out: the fused score logaddexp(pb, pnb) + g; hypotheses are sorted by it, best first
+ *   ctc_scores   [B,N] fp32 out: logaddexp(pb, pnb) alone, the acoustic log-probability as the search summed it (what
+ *                `scores` of ctc_amd_beam_search means); -inf in rows at and beyond count[b]
+ *   every other argument: as for ctc_amd_beam_search, the same limits, the same scratch.
+ * The rules are those above with three differences.  Every prefix carries g beside (pb, pnb): g(empty) = 0,
+ * g(prefix + c) = g(prefix) + inc, inc = alpha lm[last or C, c] + beta; where lm[last or C, c] is -inf the extension is no
+ * candidate.  (1) The selection key of a stay candidate is logaddexp(pb', pnb') + g(beam), that of an extension candidate
+ * v + (g(beam) + inc); the tie order is unchanged and keys of -inf are dropped.  (2) An extension that is the prefix of a
+ * beam j still adds its acoustic v into j's pnb'; g(j) is untouched (g depends on the prefix alone and was formed from the
+ * same numbers when j was created; a forbidden bigram is never a beam).  (3) The outputs, as listed.  Unchanged: the K class
+ * candidates of a frame are chosen on x alone; the blank's column of lm is never read, nor the diagonal on the no-blank
+ * lattice (a label has no equal neighbour there); T_b = 0 gives the empty hypothesis with both scores 0.
+ * NaN or +inf in lm: the result is unspecified, but nothing outside the table is read -- the row is a beam's own last token
+ * or C, the column one of the kernel's own class candidates.
+ * Whatever ctc_amd_beam_search refuses, a NULL lm or ctc_scores, lm_stride < C, lm_weight negative or not finite,
+ * token_bonus not finite: CTC_AMD_ERR_BAD_ARGUMENT before any HIP call. */
+int ctc_amd_beam_search_lm(const float *x, int64_t stride_t, int64_t stride_b, const int64_t *in_len,
+                           int T, int B, int C, int blank, int W, int K, int N, int L,
+                           const float *lm, int64_t lm_stride, float lm_weight, float token_bonus,
+                           int32_t *tokens, int64_t *lengths, float *scores, float *ctc_scores, int32_t *count,
+                           void *scratch, size_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
