@@ -27,6 +27,10 @@ constexpr float kInfeasible = 1.0e12f;   // nll above this <=> no alignment exis
 // probability 0 -- below every real value and below the sentinel, so a sample whose every alignment crosses one has
 // nll >= kInfeasible -- and the lattice stays free of -inf - (-inf).  It is the value a -1e30 pad logit gives anyway.
 constexpr float kMasked = -1.0e30f;
+// e stored no lower than kMasked -- and a NaN kept: fmaxf() answers its other operand for a NaN, which would turn a row
+// with a NaN logit (its log-sum-exp is NaN) into a masked one and the sample into one "without an alignment" with a finite
+// loss, where include/ctc_amd.h promises a NaN loss.  The comparison is false for a NaN, so it passes through.
+__device__ __forceinline__ float masked_floor(float e) { return e < kMasked ? kMasked : e; }
 
 // S lattice states over the 64 lanes of the chain's wave: K = 1, 2 or 4 per lane, S padded to a multiple of K.
 // K = 8 means S > 256, which no kernel takes.

@@ -179,7 +179,7 @@ struct Rows {
                     const float q = __shfl(v[r][j], k & 63, kWave);
                     if ((k >> 6) == j) xv = q;
                 }
-                if (l < p.SP) sm.em[t * p.SP + l] = (l < L) ? fmaxf((xv - m) - lsum, kMasked) : kNeg;
+                if (l < p.SP) sm.em[t * p.SP + l] = (l < L) ? masked_floor((xv - m) - lsum) : kNeg;
             }
         }
     }
@@ -229,7 +229,7 @@ __device__ __forceinline__ void rows_emit_generic(const NoblankParams &p, const 
         const float lsum = fast_log(s);
         if (lane == 0) { sm.mx[t] = m; sm.ls[t] = lsum; }
         for (int l = lane; l < p.SP; l += kWave)
-            sm.em[t * p.SP + l] = (l < L) ? fmaxf((row[sm.lab[l]] - m) - lsum, kMasked) : kNeg;
+            sm.em[t * p.SP + l] = (l < L) ? masked_floor((row[sm.lab[l]] - m) - lsum) : kNeg;
     }
 }
 

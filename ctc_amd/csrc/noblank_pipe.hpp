@@ -282,7 +282,7 @@ __global__ __launch_bounds__(kThreads, DUAL ? 8 : 4) void noblank_pipelined_kern
             asm volatile("" : "+v"(rsrow[r]));               // keep it in a VGPR: 12 wave-uniform floats
                                                              // would spill the scalar file
             if (t >= 0 && t < Tb && lane < p.SP)             // (t: wave-uniform)
-                sm.em[t * p.SP + lane] = (lane < L) ? fmaxf((xv[k] - m[k]) - lsum, kMasked) : kNeg;
+                sm.em[t * p.SP + lane] = (lane < L) ? masked_floor((xv[k] - m[k]) - lsum) : kNeg;
             lds_order();
             if (lane == 0) sm.cnt[u] = r + 1;                // publishes the slot (same wave: in order)
         }

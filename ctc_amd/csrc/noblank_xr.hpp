@@ -320,10 +320,13 @@ __global__ __launch_bounds__(kThreads, DUAL ? 8 : 4) void noblank_xr_kernel(Nobl
                 asm volatile("" : "+v"(rsrow[r]));
             }
             // emission e = log_softmax(x)[lab_l] in log2 units, split into 2^floor * 2^frac
-            const float e2 = fmaxf(__builtin_fmaf(xv[k] - m[k], kLog2e, -l2sum), kXrMinLog2);
+            const float e2raw = __builtin_fmaf(xv[k] - m[k], kLog2e, -l2sum);
+            const float e2 = fmaxf(e2raw, kXrMinLog2);
             const float fl = __builtin_floorf(e2);
-            // (an emission at the clamp -- a -inf or pad logit on a label class -- keeps the clamp's exponent and carries no mass)
-            const float pm = e2 > kXrMinLog2 ? __builtin_amdgcn_exp2f(e2 - fl) : 0.f;
+            // (an emission at the clamp -- a -inf or pad logit on a label class -- keeps the clamp's exponent and carries no mass.
+            // A NaN logit anywhere in the row makes the row's log-sum NaN, and fmaxf() answers the clamp for it: the mantissa
+            // keeps the NaN, so that the chains end in nll = NaN and not in the "no alignment" sentinel)
+            const float pm = e2 > kXrMinLog2 ? __builtin_amdgcn_exp2f(e2 - fl) : (e2raw != e2raw ? e2raw : 0.f);
             if (t >= 0 && t < Tb && lane < p.SP)             // (t: wave-uniform)
                 sm.em[t * p.SP + lane] = (lane < L) ? make_cell(pm, (int)fl) : zero;
             lds_order();

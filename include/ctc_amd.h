@@ -148,6 +148,8 @@ int ctc_amd_binary_loss_grad(const float *x, int64_t stride_t, int64_t stride_b,
  * with no alignment -- through its lengths (T_b < L_b + adjacent repeats) or through its emissions (every path crosses a
  * -inf entry; an empty target whose blank has a hole) -- has nll = +inf and an all-zero gradient, where torch gives NaN;
  * the other samples of the batch are not touched by it (loss, their sum, is +inf).
+ * NaN log-probs are outside the contract and, unlike the no-blank and binary losses, do not make the loss NaN: the max-based
+ * log-sum-exp of the lattice drops a NaN cell, so the sample reports +inf, or a finite nll over the paths that avoid the cell.
  * 1 <= S <= 1023 label columns (2S+1 <= 2047 lattice states; CTC_AMD_ERR_UNSUPPORTED_SHAPE beyond, and when C no
  * longer fits beside the padded lattice row in a gradient wave's LDS: 4 (C + 2 NSP) floats <= 160 KB, NSP = 512 for
  * S <= 255).  Up to 255 labels a chain is one wave; 256..1023 labels take the WIDE path: three launches, a chain

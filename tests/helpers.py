@@ -43,3 +43,26 @@ def synth_blank(seed, T, B, C, S, var_T=False):
 
 def np_(t):
     return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+
+
+NOBLANK_PLAN_FIELDS = ("family", "n4", "n2", "nt", "ps", "ch", "dual", "K", "glb", "grid", "lds", "next_round", "koff")
+NOBLANK_PLAN_FAMILIES = ("unsupported", "r16", "km", "xr", "pipelined", "fused")
+
+
+def noblank_plan_entry():
+    """`ctc_amd_debug_noblank_plan` of the diagnostics build (built on first use; no GPU needed), bound once for the tests
+    that ask which kernel a no-blank call gets -> call(T, B, C, S, dtype, st, sb, x_low, grad_low, want_grad, want_gamma,
+    smooth, cus, sw) -> {field: value} of NOBLANK_PLAN_FIELDS"""
+    import ctypes
+    from ctc_amd import build
+    fn = ctypes.CDLL(build.build_diag()).ctc_amd_debug_noblank_plan
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_int] * 5 + [ctypes.c_int64] * 2 + [ctypes.c_uint] * 2 + [ctypes.c_int] * 5 + \
+        [ctypes.POINTER(ctypes.c_int64)]
+    out = (ctypes.c_int64 * len(NOBLANK_PLAN_FIELDS))()
+
+    def call(T, B, C, S, dtype, st, sb, x_low, grad_low, want_grad, want_gamma, smooth, cus, sw):
+        rc = fn(T, B, C, S, dtype, st, sb, x_low, grad_low, int(want_grad), int(want_gamma), int(smooth), cus, sw, out)
+        assert rc == 0, (T, B, C, S, dtype, st, sb, x_low, grad_low, want_grad, want_gamma, smooth, cus, sw)
+        return dict(zip(NOBLANK_PLAN_FIELDS, out))
+    return call

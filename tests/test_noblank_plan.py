@@ -13,6 +13,8 @@ import math
 
 import pytest
 
+from tests.helpers import NOBLANK_PLAN_FAMILIES, NOBLANK_PLAN_FIELDS, noblank_plan_entry
+
 F32, BF16, F16 = 0, 1, 2
 CUS = 256
 MAX_LDS = 160 * 1024
@@ -20,8 +22,7 @@ WAVE, PREFETCH = 64, 4
 PIPE_WORKERS, PIPE_MAX_T, KM_WORKERS = 14, 168, 12
 NT_BYTES = 230 << 20
 NOPIPE, NOXR, NOR16, NOPS, KM = 1, 2, 4, 8, 16
-FIELDS = ("family", "n4", "n2", "nt", "ps", "ch", "dual", "K", "glb", "grid", "lds", "next_round", "koff")
-FAMILIES = ("unsupported", "r16", "km", "xr", "pipelined", "fused")
+FIELDS, FAMILIES = NOBLANK_PLAN_FIELDS, NOBLANK_PLAN_FAMILIES
 PS_PAIRS = {(0, 1), (0, 2), (1, 0), (1, 1), (1, 2), (2, 0), (2, 1), (2, 2), (3, 0)}
 
 
@@ -217,19 +218,11 @@ def grid():
 
 @pytest.fixture(scope="module")
 def plan():
-    from ctc_amd import build
-    lib = ctypes.CDLL(build.build_diag())
-    fn = lib.ctc_amd_debug_noblank_plan
-    fn.restype = ctypes.c_int
-    fn.argtypes = [ctypes.c_int] * 5 + [ctypes.c_int64] * 2 + [ctypes.c_uint] * 2 + [ctypes.c_int] * 5 + \
-        [ctypes.POINTER(ctypes.c_int64)]
-    out = (ctypes.c_int64 * len(FIELDS))()
+    entry = noblank_plan_entry()
 
     def call(q):
-        rc = fn(q.T, q.B, q.C, q.S, q.dtype, q.st, q.sb, q.x_low, q.grad_low, int(q.want_grad), int(q.want_gamma),
-                int(q.smooth), CUS, q.sw, out)
-        assert rc == 0, q.key()
-        return dict(zip(FIELDS, out))
+        return entry(q.T, q.B, q.C, q.S, q.dtype, q.st, q.sb, q.x_low, q.grad_low, q.want_grad, q.want_gamma, q.smooth, CUS,
+                     q.sw)
     return call
 
 
