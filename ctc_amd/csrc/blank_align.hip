@@ -10,9 +10,10 @@
 // Every step is one select chain and one add, so a float32 restatement run in the same order is bit-identical.
 //
 // Two launches:
-//   blank_align_gather_kernel   (bandwidth, every CU)  em[b,t,:] = lp[t,b,{l_0 .. l_{32K-1}, blank}] (labels j >= L
+//   blank_table_gather_kernel   (bandwidth, every CU)  em[b,t,:] = lp[t,b,{l_0 .. l_{NL-1}, blank}] (labels j >= L
 //                               -> -inf): the 4 KB rows of log_probs are read once, all CUs at once, into a
-//                               compact [B][T][RW] table in the workspace (RW = 32K + 4 floats).
+//                               compact [B][T][NL + 4] table in the workspace (NL = 32K label columns; the layout is
+//                               stated once, at the kernel).  Every read-out of this file starts from it.
 //   blank_align_kernel<K>       (latency, one 512-thread workgroup per sample)  wave 0 runs the max-plus scan,
 //                               K states per lane, the two lower neighbours of a lane's first states through ONE DPP
 //                               wave shift; waves 1..7 copy the compact rows into an LDS ring ahead of it.  Back-pointers
@@ -53,7 +54,6 @@ struct AlignParams {
     int RW, R, WL, NWS;              // row pitch (floats), ring rows (power of two), LDS word rows, spilled word rows
 };
 
-__host__ __device__ constexpr int align_row_pitch(int K) { return 32 * K + 4; }
 __host__ __device__ constexpr int align_steps_per_word(int K) { return 16 / K; }
 
 __device__ __forceinline__ bool align_sample(const AlignParams &p, int b, int &Tb, int &L)
@@ -71,41 +71,74 @@ __device__ __forceinline__ int align_label(const AlignParams &p, int b, int j)
     return c < 0 ? 0 : (c >= p.C ? p.C - 1 : c);             // memory safety for bad labels
 }
 
-// ---- launch 1: the compact emission rows ---------------------------------------------------------
-// grid (ceil(T / (4 * kAlignGatherRows)), B); every wave takes kAlignGatherRows rows, all loads in flight at once
-template <int K>
-__global__ __launch_bounds__(kAlignGatherThreads) void blank_align_gather_kernel(AlignParams p)
+// ---- launch 1: the compact emission table -------------------------------------------------------
+// THE table of every read-out here, narrow and wide: em [B][T][NL + 4] floats, NL label columns (32 K narrow, 256 W
+// wide).  Row (b, t): columns j < NL = lp[t, b, l_j] (-inf for labels j >= L_b), column NL = lp[t, b, blank], column
+// NL + 1 = the row's emission maximum c_t when CMAX (over the blank and the L_b labels, 0 for a row without a finite
+// emission; the wide posteriors' chains read it), else -inf like the rest of the padding.  Rows t >= T_b are not written.
+// grid (ceil(T / (4 * ROWS)), B); a wave takes ROWS rows, a row's NL + 4 columns dealt over its lanes in M passes, all
+// loads in flight at once
+__host__ __device__ constexpr int align_row_pitch(int K) { return 32 * K + 4; }   // NL + 4 at K states per lane
+template <int NL, int ROWS, bool CMAX>
+__global__ __launch_bounds__(kAlignGatherThreads) void blank_table_gather_kernel(AlignParams p)
 {
-    constexpr int RW = align_row_pitch(K), M = (RW + kWave - 1) / kWave;
+    constexpr int RW = NL + 4, M = (RW + kWave - 1) / kWave;
+    static_assert(!CMAX || ROWS == 4, "one wave_max4 for the rows of a wave");
     const int b = blockIdx.y, lane = lane_id();
     int Tb, L;
     if (!align_sample(p, b, Tb, L)) return;
-    const int t0 = (blockIdx.x * (kAlignGatherThreads / kWave) + wave_id()) * kAlignGatherRows;
-    if (t0 >= Tb) return;
+    const int t0 = (blockIdx.x * (kAlignGatherThreads / kWave) + wave_id()) * ROWS;
+    if (t0 >= Tb) return;                                         // (wave-uniform)
     int col[M];
 #pragma unroll
     for (int m = 0; m < M; ++m) {
         const int j = lane + kWave * m;
-        col[m] = j < L ? align_label(p, b, j) : (j == 32 * K ? p.blank : -1);
+        col[m] = j < L ? align_label(p, b, j) : (j == NL ? p.blank : -1);
     }
     const float *__restrict__ lp = p.lp + (int64_t)b * p.sb;
-    float v[kAlignGatherRows][M];
+    float v[ROWS][M], cm[ROWS];
 #pragma unroll
-    for (int r = 0; r < kAlignGatherRows; ++r) {
+    for (int r = 0; r < ROWS; ++r) {
         const int t = min(t0 + r, Tb - 1);
 #pragma unroll
         for (int m = 0; m < M; ++m) v[r][m] = lp[(int64_t)t * p.st + (col[m] >= 0 ? col[m] : p.blank)];
     }
+    if constexpr (CMAX) {
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+            cm[r] = -__builtin_inff();
+#pragma unroll
+            for (int m = 0; m < M; ++m) {
+                v[r][m] = col[m] >= 0 ? v[r][m] : -__builtin_inff();
+                cm[r] = fmaxf(cm[r], v[r][m]);
+            }
+        }
+        wave_max4(cm[0], cm[1], cm[2], cm[3]);
+    }
     float *__restrict__ out = p.em + ((int64_t)b * p.T + t0) * RW;
 #pragma unroll
-    for (int r = 0; r < kAlignGatherRows; ++r) {
+    for (int r = 0; r < ROWS; ++r) {
         if (t0 + r >= Tb) break;
+        float c = 0.f;                                            // (a row without a finite emission: post_row_max4)
+        if constexpr (CMAX) c = cm[r] > -__builtin_inff() ? cm[r] : c;
 #pragma unroll
         for (int m = 0; m < M; ++m) {
             const int j = lane + kWave * m;
-            if (j < RW) out[r * RW + j] = col[m] >= 0 ? v[r][m] : -__builtin_inff();
+            if constexpr (CMAX) {
+                if (j < RW) out[r * RW + j] = j == NL + 1 ? c : v[r][m];
+            } else {
+                if (j < RW) out[r * RW + j] = col[m] >= 0 ? v[r][m] : -__builtin_inff();
+            }
         }
     }
+}
+
+template <int NL, int ROWS, bool CMAX>
+static int launch_blank_table_gather(const AlignParams &p, hipStream_t s)
+{
+    const int rows_per_block = (kAlignGatherThreads / kWave) * ROWS;
+    return launch<blank_table_gather_kernel<NL, ROWS, CMAX>>(dim3((p.T + rows_per_block - 1) / rows_per_block, p.B),
+                                                             dim3(kAlignGatherThreads), 0, s, p);
 }
 
 // ---- launch 2: scan + walk back ------------------------------------------------------------------
@@ -155,6 +188,47 @@ __device__ __forceinline__ bool align_loader(const AlignParams &p, int *flags, f
         }
     }
     return true;
+}
+
+// THE transition rule: a label state s (odd) may be entered from s - 2 when its class is no blank and differs from that
+// of s - 2.  The flag of state s, k = s % K (even k are blanks: a lane's first state is even): FWD, s takes from s - 2
+// (the scans, alpha); !FWD, s takes from s + 2 under the same rule for s + 2 (beta').  (One flag per call, the loop over
+// k at the call site: a routine that fills the whole array moves the instructions of every scan and chain kernel.)
+template <bool FWD>
+__device__ __forceinline__ bool align_skip_flag(const AlignParams &p, int b, int L, int s, int k)
+{
+    bool sk = false;
+    if ((k & 1) && (FWD ? (s >= 3 && s <= 2 * L - 1) : (s + 2 <= 2 * L - 1))) {
+        const int c1 = align_label(p, b, (s - 1) >> 1), c2 = align_label(p, b, FWD ? (s - 3) >> 1 : (s + 1) >> 1);
+        sk = FWD ? (c1 != p.blank && c1 != c2) : (c2 != p.blank && c2 != c1);
+    }
+    return sk;
+}
+
+// THE max-plus step of K states per lane: the select chain stay -> advance -> skip, one add; the 2-bit back-pointer
+// codes go into step `sub` of `word`.  el[j] = the emission of label state 2 j + 1, eb = the blank's; `fill` = the state
+// below the wave's first (-inf, or the edge of the wave below: blank_align_wide.hpp)
+template <int K>
+__device__ __forceinline__ void align_select_step(float (&a)[K], const bool (&skip)[K], const float (&el)[K / 2], float eb,
+                                                  float fill, int sub, unsigned &word)
+{
+    const float nb = wave_shr1(a[K - 1], fill);
+    float n[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const float adv = k == 0 ? nb : a[k - 1];
+        float best = a[k];
+        unsigned c = 0;
+        if (adv > best) { best = adv; c = 1; }
+        if (k & 1) {
+            const float sk = k == 1 ? nb : a[k - 2];
+            if (skip[k] && sk > best) { best = sk; c = 2; }
+        }
+        n[k] = best + ((k & 1) ? el[k / 2] : eb);
+        word |= c << (2 * K * sub + 2 * k);
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) a[k] = n[k];
 }
 
 // the emissions of one step in the scan's registers: el[j] = label (lane K/2 + j), eb = blank
@@ -246,28 +320,6 @@ struct AlignScan {
         else spill[(w - WL) * kWave + lane_id()] = word;
     }
 
-    // one step: the select chain stay -> advance -> skip, one add; 2-bit codes into `word`
-    __device__ __forceinline__ void step(const AlignRow<K> &e, int sub, unsigned &word)
-    {
-        const float nb = wave_shr1(a[K - 1], -__builtin_inff());
-        float n[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const float adv = k == 0 ? nb : a[k - 1];
-            float best = a[k];
-            unsigned c = 0;
-            if (adv > best) { best = adv; c = 1; }
-            if (k & 1) {
-                const float sk = k == 1 ? nb : a[k - 2];
-                if (skip[k] && sk > best) { best = sk; c = 2; }
-            }
-            n[k] = best + ((k & 1) ? e.el[k / 2] : e.eb);
-            word |= c << (2 * K * sub + 2 * k);
-        }
-#pragma unroll
-        for (int k = 0; k < K; ++k) a[k] = n[k];
-    }
-
     template <bool GUARD>
     __device__ __forceinline__ void group(const AlignRow<K> (&buf)[G], int t0)
     {
@@ -282,7 +334,7 @@ struct AlignScan {
                 for (int k = 0; k < K; ++k)
                     a[k] = s0 + k == 0 ? buf[j].eb : (s0 + k == 1 ? buf[j].el[0] : -__builtin_inff());
             } else {
-                step(buf[j], j % P, word);
+                align_select_step<K>(a, skip, buf[j].el, buf[j].eb, -__builtin_inff(), j % P, word);
             }
             if (j % P == P - 1 || (GUARD && t == Tb - 1)) {
                 store_word(t / P, word);
@@ -394,20 +446,8 @@ __global__ __launch_bounds__(kAlignThreads) void blank_align_kernel(AlignParams 
 
     __builtin_amdgcn_s_setprio(3);
     AlignScan<K> sc(p, flags, ring, bp, p.spill + (int64_t)b * p.NWS * kWave, Tb);
-    {
-        const int s0 = lane * K;
 #pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int s = s0 + k;
-            // a label state s >= 3 may come from s - 2 when its class is no blank and differs from that of s - 2
-            bool sk = false;
-            if ((k & 1) && s >= 3 && s <= 2 * L - 1) {
-                const int c = align_label(p, b, (s - 1) >> 1), c2 = align_label(p, b, (s - 3) >> 1);
-                sk = c != p.blank && c != c2;
-            }
-            sc.skip[k] = sk;
-        }
-    }
+    for (int k = 0; k < K; ++k) sc.skip[k] = align_skip_flag<true>(p, b, L, lane * K + k, k);
     const bool done = sc.scan();
     if (!done) {                                                  // a wait ran out: NaN score, no path
         align_store(flags + kSlotAbort, 1);
@@ -444,9 +484,7 @@ static int run_blank_align(AlignParams &p, hipStream_t s)
     p.spill = reinterpret_cast<unsigned *>(ws + (size_t)p.B * p.T * RW * sizeof(float));
     const size_t need = 256 + (size_t)p.B * p.T * RW * sizeof(float) + (size_t)p.B * p.NWS * kWave * sizeof(unsigned);
     if (need > ctc_amd_workspace_bytes(CTC_AMD_BLANK, p.T, p.B, p.C, p.S)) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
-    const int rows_per_block = (kAlignGatherThreads / kWave) * kAlignGatherRows;
-    const dim3 ggrid((p.T + rows_per_block - 1) / rows_per_block, p.B);
-    int rc = launch<blank_align_gather_kernel<K>>(ggrid, dim3(kAlignGatherThreads), 0, s, p);
+    int rc = launch_blank_table_gather<32 * K, kAlignGatherRows, false>(p, s);
     if (rc) return rc;
     const size_t lds = head + ring + (size_t)p.WL * kWave * sizeof(unsigned);
     return launch<blank_align_kernel<K>>(dim3(p.B), dim3(kAlignThreads), lds, s, p);
@@ -454,7 +492,7 @@ static int run_blank_align(AlignParams &p, hipStream_t s)
 
 // ==== per-frame state posteriors (ctc_amd_blank_posteriors) =======================================
 // gamma_t(s) = exp(alpha_t(s) + beta'_t(s) + nll): the sum-semiring twin of the scan above, in three launches --
-//   blank_align_gather_kernel<K>  (as above) the compact emission table em [B][T][RW];
+//   blank_table_gather_kernel     (as above) the compact emission table em [B][T][RW];
 //   blank_post_chain_kernel<K>    one 128-thread workgroup per sample: wave 0 runs alpha forward, wave 1 beta' backward
 //                                 (beta' leaves out the emission of its own step), K states per lane, neighbours
 //                                 through DPP, emission rows loaded kPostAhead rows ahead into registers; each wave
@@ -621,16 +659,7 @@ __device__ __forceinline__ void post_chain(const PostParams &p, int b, int Tb, i
     c.off = 0.0;
     c.coff = 0.0;
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int s = s0 + k;
-        bool sk = false;
-        // alpha: s from s-2 when l'_s is no blank and differs from l'_{s-2}; beta: s from s+2 under the same rule for s+2
-        if ((k & 1) && (FWD ? (s >= 3 && s <= 2 * L - 1) : (s + 2 <= 2 * L - 1))) {
-            const int c1 = align_label(p.a, b, (s - 1) >> 1), c2 = align_label(p.a, b, FWD ? (s - 3) >> 1 : (s + 1) >> 1);
-            sk = FWD ? (c1 != p.a.blank && c1 != c2) : (c2 != p.a.blank && c2 != c1);
-        }
-        c.skip[k] = sk;
-    }
+    for (int k = 0; k < K; ++k) c.skip[k] = align_skip_flag<FWD>(p.a, b, L, s0 + k, k);
     float *dst = out + (int64_t)(FWD ? 0 : Tb - 1) * p.NSP;
     {
         AlignRow<K> e0[kPostRows];
@@ -695,8 +724,9 @@ __global__ __launch_bounds__(2 * kWave) void blank_post_chain_kernel(PostParams 
 // rows t0 .. t0 + kPostRows - 1 of a sample, state s = lane + 64 k.  In: z[r][k] = alpha' + beta' (-inf outside the
 // support) and m[r] = the lane's maximum over its k.  Out: m[r] = the row maximum, z[r][k] = exp2(z - m) (0 outside the
 // support), sum[r] = the row sum, both in every lane.  gamma = z * post_row_inv(sum).
-// (The masked loads in front stay in each kernel's body: moved in here -- by value, by reference, whole or per element --
-// they changed the order of blank_post_gamma_kernel's instructions)
+// (The masked loads in front stay in each kernel's body: moved into a routine they reorder the instructions of all twelve
+// combine kernels, and the one run that had them so did not show the wide posteriors as fast as before at W = 3;
+// profiles/r24_blank_readouts_refactor.md.)
 template <int K>
 __device__ __forceinline__ void post_row_terms(float (&z)[kPostRows][K], float (&m)[kPostRows], float (&sum)[kPostRows])
 {
@@ -781,9 +811,7 @@ static int run_blank_post(PostParams &pp, hipStream_t s)
     int rc = blank_post_layout<K>(pp);
     if (rc) return rc;
     AlignParams &p = pp.a;
-    const int rows_per_block = (kAlignGatherThreads / kWave) * kAlignGatherRows;
-    rc = launch<blank_align_gather_kernel<K>>(dim3((p.T + rows_per_block - 1) / rows_per_block, p.B),
-                                              dim3(kAlignGatherThreads), 0, s, p);
+    rc = launch_blank_table_gather<32 * K, kAlignGatherRows, false>(p, s);
     if (rc) return rc;
     rc = launch<blank_post_chain_kernel<K>>(dim3(p.B), dim3(2 * kWave), 0, s, pp);
     if (rc) return rc;
@@ -799,22 +827,37 @@ static int run_blank_post(PostParams &pp, hipStream_t s)
 
 using namespace ctc;
 
+// What the five entries have in common: the null and range checks, and the inputs and the shape into `p`.
+// `outputs`: the entry's own output pointers are all non-null.
+static int blank_readout_params(AlignParams &p, const float *log_probs, int64_t stride_t, int64_t stride_b,
+                                const void *targets, int targets_i64, const int64_t *in_len, const int64_t *tgt_len,
+                                int T, int B, int C, int S, int blank, bool outputs, void *workspace)
+{
+    if (!log_probs || !targets || !in_len || !tgt_len || !outputs || !workspace) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (T < 1 || B < 1 || C < 1 || S < 1 || blank < 0 || blank >= C) return CTC_AMD_ERR_BAD_ARGUMENT;
+    p.lp = log_probs; p.st = stride_t; p.sb = stride_b;
+    p.tgt = targets; p.tgt64 = targets_i64;
+    p.in_len = in_len; p.tgt_len = tgt_len;
+    p.T = T; p.B = B; p.C = C; p.S = S; p.blank = blank;
+    p.counter = static_cast<unsigned *>(workspace);
+    return 0;
+}
+
+// states per lane of the narrow kernels (S <= 255): 2S+1 <= 128 / 256 / 512
+static int align_states_per_lane(int S) { return 2 * S + 1 <= kWave * 2 ? 2 : (2 * S + 1 <= kWave * 4 ? 4 : 8); }
+
 extern "C" int ctc_amd_blank_best_path_wide(const float *log_probs, int64_t stride_t, int64_t stride_b,
                                             const void *targets, int targets_i64,
                                             const int64_t *in_len, const int64_t *tgt_len,
                                             int T, int B, int C, int S, int blank,
                                             int32_t *path, float *score, void *workspace, void *stream)
 {
-    if (!log_probs || !targets || !in_len || !tgt_len || !path || !score || !workspace) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (T < 1 || B < 1 || C < 1 || S < 1 || blank < 0 || blank >= C) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (S < 256 || S > 1023) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;           // 513 <= 2S+1 <= 2047: two to four waves of 512
     AlignParams p;
-    p.lp = log_probs; p.st = stride_t; p.sb = stride_b;
-    p.tgt = targets; p.tgt64 = targets_i64;
-    p.in_len = in_len; p.tgt_len = tgt_len;
-    p.T = T; p.B = B; p.C = C; p.S = S; p.blank = blank;
+    const int rc = blank_readout_params(p, log_probs, stride_t, stride_b, targets, targets_i64, in_len, tgt_len, T, B, C, S,
+                                        blank, path && score, workspace);
+    if (rc) return rc;
+    if (S < 256 || S > 1023) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;           // 513 <= 2S+1 <= 2047: two to four waves of 512
     p.path = path; p.score = score;
-    p.counter = static_cast<unsigned *>(workspace);
     return run_blank_align_wide(p, static_cast<hipStream_t>(stream));
 }
 
@@ -824,21 +867,15 @@ extern "C" int ctc_amd_blank_best_path(const float *log_probs, int64_t stride_t,
                                        int T, int B, int C, int S, int blank,
                                        int32_t *path, float *score, void *workspace, void *stream)
 {
-    if (!log_probs || !targets || !in_len || !tgt_len || !path || !score || !workspace) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (T < 1 || B < 1 || C < 1 || S < 1 || blank < 0 || blank >= C) return CTC_AMD_ERR_BAD_ARGUMENT;
-    const int ns = 2 * S + 1;
-    if (ns > kWave * 8) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;                 // S <= 255
     AlignParams p;
-    p.lp = log_probs; p.st = stride_t; p.sb = stride_b;
-    p.tgt = targets; p.tgt64 = targets_i64;
-    p.in_len = in_len; p.tgt_len = tgt_len;
-    p.T = T; p.B = B; p.C = C; p.S = S; p.blank = blank;
+    const int rc = blank_readout_params(p, log_probs, stride_t, stride_b, targets, targets_i64, in_len, tgt_len, T, B, C, S,
+                                        blank, path && score, workspace);
+    if (rc) return rc;
+    if (S > 255) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;                        // 2S+1 <= 512: one wave
     p.path = path; p.score = score;
-    p.counter = static_cast<unsigned *>(workspace);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (ns <= kWave * 2) return run_blank_align<2>(p, s);
-    if (ns <= kWave * 4) return run_blank_align<4>(p, s);
-    return run_blank_align<8>(p, s);
+    return with_constant<2, 4, 8>(align_states_per_lane(S), [&](auto k) {
+        return run_blank_align<decltype(k)::value>(p, static_cast<hipStream_t>(stream));
+    });
 }
 
 extern "C" int ctc_amd_blank_posteriors(const float *log_probs, int64_t stride_t, int64_t stride_b,
@@ -847,22 +884,15 @@ extern "C" int ctc_amd_blank_posteriors(const float *log_probs, int64_t stride_t
                                         int T, int B, int C, int S, int blank,
                                         float *nll, float *gamma, void *workspace, void *stream)
 {
-    if (!log_probs || !targets || !in_len || !tgt_len || !nll || !gamma || !workspace) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (T < 1 || B < 1 || C < 1 || S < 1 || blank < 0 || blank >= C) return CTC_AMD_ERR_BAD_ARGUMENT;
-    const int ns = 2 * S + 1;
-    if (ns > kWave * 8) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;                 // S <= 255
     PostParams pp = {};
-    AlignParams &p = pp.a;
-    p.lp = log_probs; p.st = stride_t; p.sb = stride_b;
-    p.tgt = targets; p.tgt64 = targets_i64;
-    p.in_len = in_len; p.tgt_len = tgt_len;
-    p.T = T; p.B = B; p.C = C; p.S = S; p.blank = blank;
-    p.counter = static_cast<unsigned *>(workspace);
+    const int rc = blank_readout_params(pp.a, log_probs, stride_t, stride_b, targets, targets_i64, in_len, tgt_len, T, B, C,
+                                        S, blank, nll && gamma, workspace);
+    if (rc) return rc;
+    if (S > 255) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;                        // 2S+1 <= 512: one wave
     pp.nll = nll; pp.gamma = gamma;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (ns <= kWave * 2) return run_blank_post<2>(pp, s);
-    if (ns <= kWave * 4) return run_blank_post<4>(pp, s);
-    return run_blank_post<8>(pp, s);
+    return with_constant<2, 4, 8>(align_states_per_lane(S), [&](auto k) {
+        return run_blank_post<decltype(k)::value>(pp, static_cast<hipStream_t>(stream));
+    });
 }
 
 extern "C" int ctc_amd_blank_posteriors_wide(const float *log_probs, int64_t stride_t, int64_t stride_b,
@@ -871,16 +901,11 @@ extern "C" int ctc_amd_blank_posteriors_wide(const float *log_probs, int64_t str
                                              int T, int B, int C, int S, int blank,
                                              float *nll, float *gamma, void *workspace, void *stream)
 {
-    if (!log_probs || !targets || !in_len || !tgt_len || !nll || !gamma || !workspace) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (T < 1 || B < 1 || C < 1 || S < 1 || blank < 0 || blank >= C) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (S < 256 || S > 1023) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;           // 513 <= 2S+1 <= 2047: two to four waves of 512
     PostParams pp = {};
-    AlignParams &p = pp.a;
-    p.lp = log_probs; p.st = stride_t; p.sb = stride_b;
-    p.tgt = targets; p.tgt64 = targets_i64;
-    p.in_len = in_len; p.tgt_len = tgt_len;
-    p.T = T; p.B = B; p.C = C; p.S = S; p.blank = blank;
-    p.counter = static_cast<unsigned *>(workspace);
+    const int rc = blank_readout_params(pp.a, log_probs, stride_t, stride_b, targets, targets_i64, in_len, tgt_len, T, B, C,
+                                        S, blank, nll && gamma, workspace);
+    if (rc) return rc;
+    if (S < 256 || S > 1023) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;           // 513 <= 2S+1 <= 2047: two to four waves of 512
     pp.nll = nll; pp.gamma = gamma;
     return run_blank_post_wide(pp, static_cast<hipStream_t>(stream));
 }
@@ -893,25 +918,15 @@ extern "C" int ctc_amd_blank_token_spans(const float *log_probs, int64_t stride_
                                          int32_t *start, int32_t *end, float *conf,
                                          void *workspace, void *stream)
 {
-    if (!log_probs || !targets || !in_len || !tgt_len || !path || !score || !nll || !frame_conf || !start || !end ||
-        !conf || !workspace)
-        return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (T < 1 || B < 1 || C < 1 || S < 1 || blank < 0 || blank >= C) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (S > 1023) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;                       // 2S+1 <= 2047: four waves of 512
     SpanParams q = {};
-    AlignParams &p = q.p.a;
-    p.lp = log_probs; p.st = stride_t; p.sb = stride_b;
-    p.tgt = targets; p.tgt64 = targets_i64;
-    p.in_len = in_len; p.tgt_len = tgt_len;
-    p.T = T; p.B = B; p.C = C; p.S = S; p.blank = blank;
-    p.path = path; p.score = score;
-    p.counter = static_cast<unsigned *>(workspace);
+    const int rc = blank_readout_params(q.p.a, log_probs, stride_t, stride_b, targets, targets_i64, in_len, tgt_len, T, B, C,
+                                        S, blank, path && score && nll && frame_conf && start && end && conf, workspace);
+    if (rc) return rc;
+    if (S > 1023) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;                       // 2S+1 <= 2047: four waves of 512
+    q.p.a.path = path; q.p.a.score = score;
     q.p.nll = nll;
     q.frame_conf = frame_conf; q.start = start; q.end = end; q.conf = conf;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int ns = 2 * S + 1;
-    if (ns <= kWave * 2) return run_blank_spans<2>(q, s);
-    if (ns <= kWave * 4) return run_blank_spans<4>(q, s);
-    if (ns <= kWave * 8) return run_blank_spans<8>(q, s);
-    return run_blank_spans_wide(q, s);
+    if (S > 255) return run_blank_spans_wide(q, s);
+    return with_constant<2, 4, 8>(align_states_per_lane(S), [&](auto k) { return run_blank_spans<decltype(k)::value>(q, s); });
 }

@@ -1,9 +1,9 @@
 // Best path (Viterbi forced alignment) on blank-CTC lattices wider than one wave: 256 <= S <= 1023 labels,
 // 513 <= 2S+1 <= 2047 states.  Included by blank_align.hip, which owns the arithmetic and the
-// input rules (AlignParams, align_sample, align_label, align_state_value): the same select chain, wider.
+// input rules (AlignParams, align_sample, align_label, align_state_value), the transition rule (align_skip_flag) and
+// the step (align_select_step): the same select chain, wider.
 // Two launches:
-//   blank_align_wide_gather_kernel<W>  (bandwidth, every CU)  em[b,t,:] = lp[t,b,{l_0 .. l_{256W-1}, blank}] (labels
-//                                      j >= L -> -inf): the narrow gather's layout with a row of 256 W + 4 floats.
+//   blank_table_gather_kernel          (bandwidth, every CU)  the table of blank_align.hip with NL = 256 W label columns.
 //   blank_align_wide_kernel            (latency, one workgroup of W = ceil((2S+1)/512) waves per sample)  wave w owns
 //                                      states [512 w, 512 w + 512), K = 8 per lane.  K is even, so the only operand
 //                                      that crosses a wave is the previous wave's LAST state of step t-1 (v(s-1) of a
@@ -29,54 +29,11 @@ static_assert(kWideAlignAhead % 2 == 0, "a step's half of its back-pointer word 
 // two blocks of the walk back move the state by at most 4 * 2 * kAlignWalkWords < 512: they stay within two waves
 static_assert(8 * kAlignWalkWords < kWideAlignSpan, "the walk's two fetched slices cover two blocks");
 
-__host__ __device__ constexpr int align_wide_row_pitch(int W) { return 256 * W + 4; }
-
 struct AlignWideParams {
     AlignParams a;                   // inputs, shape, outputs, em (the table), spill (the back-pointer words)
     int W, NW;                       // waves per sample, back-pointer word rows per sample ((T + 1) / 2)
 };
 
-// ---- launch 1: the compact emission rows ---------------------------------------------------------
-// grid (ceil(T / (4 * kWideAlignGatherRows)), B); a wave takes kWideAlignGatherRows rows, a row's 256 W + 1 columns dealt
-// over its lanes in M passes, all loads in flight at once.  (blank_post_wide_gather_kernel in blank_post_wide.hpp is a
-// copy of this body plus the row maximum: a change to the table's layout goes into both.)
-template <int W>
-__global__ __launch_bounds__(kAlignGatherThreads) void blank_align_wide_gather_kernel(AlignWideParams q)
-{
-    constexpr int RW = align_wide_row_pitch(W), M = (RW + kWave - 1) / kWave, NL = 256 * W;
-    const AlignParams &p = q.a;
-    const int b = blockIdx.y, lane = lane_id();
-    int Tb, L;
-    if (!align_sample(p, b, Tb, L)) return;
-    const int t0 = (blockIdx.x * (kAlignGatherThreads / kWave) + wave_id()) * kWideAlignGatherRows;
-    if (t0 >= Tb) return;
-    int col[M];
-#pragma unroll
-    for (int m = 0; m < M; ++m) {
-        const int j = lane + kWave * m;
-        col[m] = j < L ? align_label(p, b, j) : (j == NL ? p.blank : -1);
-    }
-    const float *__restrict__ lp = p.lp + (int64_t)b * p.sb;
-    float v[kWideAlignGatherRows][M];
-#pragma unroll
-    for (int r = 0; r < kWideAlignGatherRows; ++r) {
-        const int t = min(t0 + r, Tb - 1);
-#pragma unroll
-        for (int m = 0; m < M; ++m) v[r][m] = lp[(int64_t)t * p.st + (col[m] >= 0 ? col[m] : p.blank)];
-    }
-    float *__restrict__ out = p.em + ((int64_t)b * p.T + t0) * RW;
-#pragma unroll
-    for (int r = 0; r < kWideAlignGatherRows; ++r) {
-        if (t0 + r >= Tb) break;
-#pragma unroll
-        for (int m = 0; m < M; ++m) {
-            const int j = lane + kWave * m;
-            if (j < RW) out[r * RW + j] = col[m] >= 0 ? v[r][m] : -__builtin_inff();
-        }
-    }
-}
-
-// ---- launch 2: scan + walk back ------------------------------------------------------------------
 // the emissions of one step of a wave's slice: el = the lane's four labels (one 16-byte load), eb = the blank
 struct AlignWideRow {
     float4 el;
@@ -127,6 +84,22 @@ __device__ __forceinline__ void align_wide_walk(const unsigned *bp, int W, int T
     }
 }
 
+// The last two states of a sample, 2L and 2L-1 (state 0 twice when L = 0), may sit in two waves (2L = 512 w: the first
+// state of wave w, 2L-1 the last of wave w-1): s_fin[0] = a(2L), s_fin[1] = a(2L-1), each from lane 0 of the wave that
+// holds it.  The caller's barrier makes them visible.
+__device__ __forceinline__ void wide_final_states(const float (&a)[kWideAlignK], int L, float (&s_fin)[2])
+{
+    const int sa = 2 * L, sb = L > 0 ? 2 * L - 1 : 0;
+    if (sa / kWideAlignSpan == wave_id()) {
+        const float x = align_state_value<kWideAlignK>(a, sa & (kWideAlignSpan - 1));
+        if (lane_id() == 0) s_fin[0] = x;
+    }
+    if (sb / kWideAlignSpan == wave_id()) {
+        const float x = align_state_value<kWideAlignK>(a, sb & (kWideAlignSpan - 1));
+        if (lane_id() == 0) s_fin[1] = x;
+    }
+}
+
 // grid B, block 64 W
 __global__ __launch_bounds__(kWideAlignMaxWaves * kWave) void blank_align_wide_kernel(AlignWideParams q)
 {
@@ -138,7 +111,7 @@ __global__ __launch_bounds__(kWideAlignMaxWaves * kWave) void blank_align_wide_k
     __shared__ float s_fin[2];                                    // v(2L), v(2L-1) from the waves that hold them
     constexpr int K = kWideAlignK, D = kWideAlignAhead;
     const AlignParams &p = q.a;
-    const int W = q.W, RW = align_wide_row_pitch(W);
+    const int W = q.W, RW = align_row_pitch(K * W);
     const int b = blockIdx.x, tid = threadIdx.x, w = wave_id(), lane = lane_id();
     const int nthreads = W * kWave;
     int32_t *out = p.path + (int64_t)b * p.T;
@@ -153,16 +126,7 @@ __global__ __launch_bounds__(kWideAlignMaxWaves * kWave) void blank_align_wide_k
     const int s0 = w * kWideAlignSpan + lane * K;                 // the lane's first state: a blank
     bool skip[K];
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int s = s0 + k;
-        // a label state s >= 3 may come from s - 2 when its class is no blank and differs from that of s - 2
-        bool sk = false;
-        if ((k & 1) && s >= 3 && s <= 2 * L - 1) {
-            const int c = align_label(p, b, (s - 1) >> 1), c2 = align_label(p, b, (s - 3) >> 1);
-            sk = c != p.blank && c != c2;
-        }
-        skip[k] = sk;
-    }
+    for (int k = 0; k < K; ++k) skip[k] = align_skip_flag<true>(p, b, L, s0 + k, k);
     if (tid < 2) xch[tid][0] = -__builtin_inff();                 // (before the first barrier)
     // the lane's labels of a row, and the blank through a per-lane address: a vector load, counted with the rows
     // (a scalar load would be waited for with the LDS hand-off at every barrier)
@@ -187,28 +151,10 @@ __global__ __launch_bounds__(kWideAlignMaxWaves * kWave) void blank_align_wide_k
                      :
                      : "memory");
     };
-    // one step: the select chain stay -> advance -> skip, one add (AlignScan<8>::step with the neighbour wave's edge as
-    // the fill of the shift); 2-bit codes into half `sub` of the word
+    // one step (align_select_step with the edge of the wave below as the fill of the shift) into half `sub` of the word
     auto step = [&](int i, const AlignWideRow &e, int sub) {
-        const float in0 = xch[i & 1][w];                          // (wave-uniform)
-        const float nb = wave_shr1(a[K - 1], in0);
         const float el[K / 2] = {e.el.x, e.el.y, e.el.z, e.el.w};
-        float n[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const float adv = k == 0 ? nb : a[k - 1];
-            float best = a[k];
-            unsigned c = 0;
-            if (adv > best) { best = adv; c = 1; }
-            if (k & 1) {
-                const float sk = k == 1 ? nb : a[k - 2];
-                if (skip[k] && sk > best) { best = sk; c = 2; }
-            }
-            n[k] = best + ((k & 1) ? el[k / 2] : e.eb);
-            word |= c << (2 * K * sub + 2 * k);
-        }
-#pragma unroll
-        for (int k = 0; k < K; ++k) a[k] = n[k];
+        align_select_step<K>(a, skip, el, e.eb, xch[i & 1][w], sub, word);    // (the fill is wave-uniform)
         if (sub == 1) {                                           // the word of steps i - 1, i is complete
             bp[(int64_t)(i >> 1) * W * kWave] = word;
             word = 0;
@@ -238,19 +184,11 @@ __global__ __launch_bounds__(kWideAlignMaxWaves * kWave) void blank_align_wide_k
         if (i + j < Tb) step(i + j, ring[j], (j + 1) & 1);        // (uniform over the workgroup)
     if (((Tb - 1) & 1) == 0) bp[(int64_t)((Tb - 1) >> 1) * W * kWave] = word;   // a last word with its lower half only
 
-    // v(2L) and v(2L-1) may sit in two waves (2L = 512 w: the first state of wave w, 2L-1 the last of wave w-1)
-    const int sa = 2 * L, sb = L > 0 ? 2 * L - 1 : 0;
-    if (sa / kWideAlignSpan == w) {
-        const float x = align_state_value<K>(a, sa & (kWideAlignSpan - 1));
-        if (lane == 0) s_fin[0] = x;
-    }
-    if (sb / kWideAlignSpan == w) {
-        const float x = align_state_value<K>(a, sb & (kWideAlignSpan - 1));
-        if (lane == 0) s_fin[1] = x;
-    }
+    wide_final_states(a, L, s_fin);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // this wave's back-pointer words have left it
     __syncthreads();
     if (w != 0) return;
+    const int sa = 2 * L, sb = L > 0 ? 2 * L - 1 : 0;
     int sfin = 0;
     if (L > 0) sfin = s_fin[0] > s_fin[1] ? sa : sb;
     const float score = sfin == sa ? s_fin[0] : s_fin[1];
@@ -262,34 +200,39 @@ __global__ __launch_bounds__(kWideAlignMaxWaves * kWave) void blank_align_wide_k
     align_wide_walk(p.spill + (int64_t)b * q.NW * W * kWave, W, Tb, __builtin_amdgcn_readfirstlane(sfin), out);
 }
 
-// 256 <= p.S <= 1023 (the caller has checked); the table and the back-pointer words lie in the three lattice areas of
-// ctc_amd_workspace_bytes(CTC_AMD_BLANK, ...): (256 W + 4) + 32 W words per (b, t) (+ 32 W per sample at odd T) of 1536 W
+// Where the wide read-outs' workspace lies (256 <= p.S <= 1023: the caller has checked).  W waves per sample; behind the
+// 256-byte header the table em [B][T][256 W + 4], and behind the table `rest` bytes for the caller's rows: what is left
+// of the three lattice areas of ctc_amd_workspace_bytes(CTC_AMD_BLANK, ...), 1536 W floats per (b, t).  Nothing is
+// written to the header or behind the areas.
+static int blank_wide_layout(AlignParams &p, int &W, size_t &rest)
+{
+    W = (2 * p.S + 1 + kWideAlignSpan - 1) / kWideAlignSpan;
+    p.RW = align_row_pitch(kWideAlignK * W);
+    p.em = reinterpret_cast<float *>(reinterpret_cast<char *>(p.counter) + 256);
+    const size_t cells = (size_t)p.B * p.T;
+    const size_t areas = 3 * cells * W * kWideAlignSpan * sizeof(float);
+    if (256 + areas > ctc_amd_workspace_bytes(CTC_AMD_BLANK, p.T, p.B, p.C, p.S)) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
+    rest = areas - cells * p.RW * sizeof(float);
+    return 0;
+}
+
+// the table, then the back-pointer words: (256 W + 4) + 32 W words per (b, t) (+ 32 W per sample at odd T) of 1536 W
 static int run_blank_align_wide(AlignParams &p, hipStream_t s)
 {
     AlignWideParams q;
-    q.W = (2 * p.S + 1 + kWideAlignSpan - 1) / kWideAlignSpan;
+    size_t rest;
+    const int rc = blank_wide_layout(p, q.W, rest);
+    if (rc) return rc;
     q.NW = (p.T + 1) / 2;
-    const int RW = align_wide_row_pitch(q.W);
-    p.RW = RW;
     p.R = p.WL = 0;
     p.NWS = q.NW;
-    char *ws = reinterpret_cast<char *>(p.counter) + 256;
-    const size_t table = (size_t)p.B * p.T * RW * sizeof(float);
-    const size_t words = (size_t)p.B * q.NW * q.W * kWave * sizeof(unsigned);
-    p.em = reinterpret_cast<float *>(ws);
-    p.spill = reinterpret_cast<unsigned *>(ws + table);
-    const size_t areas = 3 * (size_t)p.B * p.T * q.W * kWideAlignSpan * sizeof(float);
-    if (table + words > areas || 256 + areas > ctc_amd_workspace_bytes(CTC_AMD_BLANK, p.T, p.B, p.C, p.S))
-        return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
+    p.spill = reinterpret_cast<unsigned *>(p.em + (size_t)p.B * p.T * p.RW);
+    if ((size_t)p.B * q.NW * q.W * kWave * sizeof(unsigned) > rest) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
     q.a = p;
-    const int rows_per_block = (kAlignGatherThreads / kWave) * kWideAlignGatherRows;
-    const dim3 ggrid((p.T + rows_per_block - 1) / rows_per_block, p.B), gblock(kAlignGatherThreads);
-    int rc;
-    if (q.W == 2) rc = launch<blank_align_wide_gather_kernel<2>>(ggrid, gblock, 0, s, q);
-    else if (q.W == 3) rc = launch<blank_align_wide_gather_kernel<3>>(ggrid, gblock, 0, s, q);
-    else rc = launch<blank_align_wide_gather_kernel<4>>(ggrid, gblock, 0, s, q);
-    if (rc) return rc;
-    return launch<blank_align_wide_kernel>(dim3(p.B), dim3(q.W * kWave), 0, s, q);
+    return with_constant<2, 3, 4>(q.W, [&](auto w) {
+        const int grc = launch_blank_table_gather<256 * decltype(w)::value, kWideAlignGatherRows, false>(p, s);
+        return grc ? grc : launch<blank_align_wide_kernel>(dim3(p.B), dim3(q.W * kWave), 0, s, q);
+    });
 }
 
 }  // namespace ctc

@@ -1,12 +1,10 @@
 // Per-frame state posteriors on blank-CTC lattices wider than one wave: 256 <= S <= 1023 labels, 513 <= 2S+1 <= 2047
 // states.  Included by blank_align.hip behind blank_align_wide.hpp: the arithmetic is PostChain<8>'s
 // (pre / add_store / state_max / subtract, post_lse2, kPostNeg / kPostLive), the input rules are align_sample and
-// align_label, the table is the wide gather's.  Three launches:
-//   blank_post_wide_gather_kernel<W>  the wide gather's compact table [B][T][256 W + 4] (labels j >= L -> -inf),
-//                                     blank at column 256 W, and the row's emission maximum c_t (over the blank and the
-//                                     L labels, 0 for a row without a finite emission) in the padding column 256 W + 1.
-//                                     One wave has the whole row there, so every wave of the chains reads the SAME c_t
-//                                     and no step reduces across waves.
+// align_label, the transition rule is align_skip_flag.  Three launches:
+//   blank_table_gather_kernel         the table of blank_align.hip with NL = 256 W label columns and CMAX: the row's
+//                                     emission maximum c_t in column NL + 1.  One wave has the whole row there, so
+//                                     every wave of the chains reads the SAME c_t and no step reduces across waves.
 //   blank_post_wide_chain_kernel      grid (B, 2), W = ceil((2S+1)/512) waves per workgroup: workgroup (b, 0) runs alpha
 //                                     forward, (b, 1) runs beta' backward; wave w owns states [512 w, 512 w + 512), K = 8
 //                                     per lane.  What crosses a wave goes through LDS, double-buffered by step parity, ONE
@@ -31,57 +29,6 @@ struct PostWideParams {
     int W;                           // waves per lattice row
 };
 
-// ---- launch 1: the compact emission rows and their maxima ----------------------------------------
-// blank_align_wide_gather_kernel<W> (same grid, same table) plus c_t in column NL + 1.  A kernel of its own: the best
-// path's instantiations stay as they are, instruction for instruction.
-template <int W>
-__global__ __launch_bounds__(kAlignGatherThreads) void blank_post_wide_gather_kernel(AlignWideParams q)
-{
-    constexpr int RW = align_wide_row_pitch(W), M = (RW + kWave - 1) / kWave, NL = 256 * W;
-    static_assert(kWideAlignGatherRows == kPostRows, "one wave_max4 for the rows of a wave");
-    const AlignParams &p = q.a;
-    const int b = blockIdx.y, lane = lane_id();
-    int Tb, L;
-    if (!align_sample(p, b, Tb, L)) return;
-    const int t0 = (blockIdx.x * (kAlignGatherThreads / kWave) + wave_id()) * kWideAlignGatherRows;
-    if (t0 >= Tb) return;                                         // (wave-uniform)
-    int col[M];
-#pragma unroll
-    for (int m = 0; m < M; ++m) {
-        const int j = lane + kWave * m;
-        col[m] = j < L ? align_label(p, b, j) : (j == NL ? p.blank : -1);
-    }
-    const float *__restrict__ lp = p.lp + (int64_t)b * p.sb;
-    float v[kWideAlignGatherRows][M], cm[kWideAlignGatherRows];
-#pragma unroll
-    for (int r = 0; r < kWideAlignGatherRows; ++r) {
-        const int t = min(t0 + r, Tb - 1);
-#pragma unroll
-        for (int m = 0; m < M; ++m) v[r][m] = lp[(int64_t)t * p.st + (col[m] >= 0 ? col[m] : p.blank)];
-    }
-#pragma unroll
-    for (int r = 0; r < kWideAlignGatherRows; ++r) {
-        cm[r] = -__builtin_inff();
-#pragma unroll
-        for (int m = 0; m < M; ++m) {
-            v[r][m] = col[m] >= 0 ? v[r][m] : -__builtin_inff();
-            cm[r] = fmaxf(cm[r], v[r][m]);
-        }
-    }
-    wave_max4(cm[0], cm[1], cm[2], cm[3]);
-    float *__restrict__ out = p.em + ((int64_t)b * p.T + t0) * RW;
-#pragma unroll
-    for (int r = 0; r < kWideAlignGatherRows; ++r) {
-        if (t0 + r >= Tb) break;
-        const float c = cm[r] > -__builtin_inff() ? cm[r] : 0.f;  // (a row without a finite emission: post_row_max4)
-#pragma unroll
-        for (int m = 0; m < M; ++m) {
-            const int j = lane + kWave * m;
-            if (j < RW) out[r * RW + j] = j == NL + 1 ? c : v[r][m];
-        }
-    }
-}
-
 // the emissions of one step of a wave's slice: el = the lane's four labels, bc = (blank, c_t)
 struct PostWideRow {
     float4 el;
@@ -104,7 +51,7 @@ __device__ __forceinline__ void post_wide_chain(const PostWideParams &q, int b, 
     static_assert(D % G == 0, "rescale points are compile-time positions in the unrolled body");
     static_assert(kWideAlignMaxWaves == 4, "the maxima are one 16-byte LDS read");
     const PostParams &p = q.p;
-    const int W = q.W, RW = align_wide_row_pitch(W), NSP = p.NSP, T = p.a.T;
+    const int W = q.W, RW = align_row_pitch(K * W), NSP = p.NSP, T = p.a.T;
     const int tid = threadIdx.x, w = wave_id(), lane = lane_id();
     const int s0 = w * kWideAlignSpan + lane * K, n = 2 * L + 1;
 
@@ -116,16 +63,7 @@ __device__ __forceinline__ void post_wide_chain(const PostWideParams &q, int b, 
     c.off = 0.0;
     c.coff = 0.0;
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int s = s0 + k;
-        bool sk = false;
-        // alpha: s from s-2 when l'_s is no blank and differs from l'_{s-2}; beta: s from s+2 under the same rule for s+2
-        if ((k & 1) && (FWD ? (s >= 3 && s <= 2 * L - 1) : (s + 2 <= 2 * L - 1))) {
-            const int c1 = align_label(p.a, b, (s - 1) >> 1), c2 = align_label(p.a, b, FWD ? (s - 3) >> 1 : (s + 1) >> 1);
-            sk = FWD ? (c1 != p.a.blank && c1 != c2) : (c2 != p.a.blank && c2 != c1);
-        }
-        c.skip[k] = sk;
-    }
+    for (int k = 0; k < K; ++k) c.skip[k] = align_skip_flag<FWD>(p.a, b, L, s0 + k, k);
     // the lane's labels of a row, and (blank, c_t) through a per-lane address: vector loads, counted with the rows (a
     // scalar load would be waited for with the LDS hand-off at every barrier)
     const float *em = p.a.em + (int64_t)b * T * RW + (w * kWave + lane) * (K / 2);
@@ -214,16 +152,7 @@ __device__ __forceinline__ void post_wide_chain(const PostWideParams &q, int b, 
         if (i + j < Tb) step(i + j, ring[j], j % G == 0, j % G == G - 1);    // (uniform over the workgroup)
 
     if (FWD) {
-        // alpha(2L) and alpha(2L-1) may sit in two waves (2L = 512 w: the first state of wave w, 2L-1 the last of w-1)
-        const int sa = 2 * L, sb = L > 0 ? 2 * L - 1 : 0;
-        if (sa / kWideAlignSpan == w) {
-            const float x = align_state_value<K>(c.a, sa & (kWideAlignSpan - 1));
-            if (lane == 0) s_fin[0] = x;
-        }
-        if (sb / kWideAlignSpan == w) {
-            const float x = align_state_value<K>(c.a, sb & (kWideAlignSpan - 1));
-            if (lane == 0) s_fin[1] = x;
-        }
+        wide_final_states(c.a, L, s_fin);
         __syncthreads();
         if (w == 0 && lane == 0) {                                // (off and coff are the same in every wave)
             const float v = post_lse2(s_fin[0], L > 0 ? s_fin[1] : kPostNeg);
@@ -249,45 +178,24 @@ __global__ __launch_bounds__(kWideAlignMaxWaves * kWave) void blank_post_wide_ch
 template <int W>
 static int launch_blank_post_wide_chains(PostWideParams &q, hipStream_t s)
 {
-    AlignWideParams g;
-    g.a = q.p.a;
-    g.W = W;
-    g.NW = 0;
+    static_assert(kWideAlignGatherRows == kPostRows, "the table's c_t column: one wave_max4 for the rows of a wave");
     const AlignParams &p = q.p.a;
-    const int grows = (kAlignGatherThreads / kWave) * kWideAlignGatherRows;
-    int rc = launch<blank_post_wide_gather_kernel<W>>(dim3((p.T + grows - 1) / grows, p.B), dim3(kAlignGatherThreads), 0, s, g);
-    if (rc) return rc;
-    return launch<blank_post_wide_chain_kernel>(dim3(p.B, 2), dim3(W * kWave), 0, s, q);
+    const int rc = launch_blank_table_gather<256 * W, kWideAlignGatherRows, true>(p, s);
+    return rc ? rc : launch<blank_post_wide_chain_kernel>(dim3(p.B, 2), dim3(W * kWave), 0, s, q);
 }
 
-template <int W>
-static int launch_blank_post_wide(PostWideParams &q, hipStream_t s)
-{
-    const AlignParams &p = q.p.a;
-    int rc = launch_blank_post_wide_chains<W>(q, s);
-    if (rc) return rc;
-    const int rows = (kPostThreads / kWave) * kPostRows;
-    return launch<blank_post_gamma_kernel<kWideAlignK * W>>(dim3((p.T + rows - 1) / rows, p.B), dim3(kPostThreads), 0, s, q.p);
-}
-
-// 256 <= S <= 1023 (the caller has checked); the table and the alpha' / beta' rows lie in the three lattice areas of
-// ctc_amd_workspace_bytes(CTC_AMD_BLANK, ...): (256 W + 4) + 2 * 512 W floats per (b, t) of 1536 W; nothing is written to
-// the header or behind the areas
+// the table, then the alpha' and the beta' rows: (256 W + 4) + 2 * 512 W floats per (b, t) of 1536 W
 static int blank_post_wide_layout(PostParams &pp, PostWideParams &q)
 {
     AlignParams &p = pp.a;
-    q.W = (2 * p.S + 1 + kWideAlignSpan - 1) / kWideAlignSpan;
-    const int RW = align_wide_row_pitch(q.W);
-    p.RW = RW;
+    size_t rest;
+    const int rc = blank_wide_layout(p, q.W, rest);
+    if (rc) return rc;
     pp.NSP = q.W * kWideAlignSpan;
     pp.NS = 2 * p.S + 1;
     const size_t cells = (size_t)p.B * p.T;
-    const size_t areas = 3 * cells * pp.NSP * sizeof(float);
-    if (((size_t)RW + 2 * (size_t)pp.NSP) * cells * sizeof(float) > areas ||
-        256 + areas > ctc_amd_workspace_bytes(CTC_AMD_BLANK, p.T, p.B, p.C, p.S))
-        return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
-    p.em = reinterpret_cast<float *>(reinterpret_cast<char *>(p.counter) + 256);
-    pp.al = p.em + cells * RW;
+    if (2 * cells * pp.NSP * sizeof(float) > rest) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
+    pp.al = p.em + cells * p.RW;
     pp.be = pp.al + cells * pp.NSP;
     q.p = pp;
     return 0;
@@ -298,9 +206,14 @@ static int run_blank_post_wide(PostParams &pp, hipStream_t s)
     PostWideParams q;
     const int rc = blank_post_wide_layout(pp, q);
     if (rc) return rc;
-    if (q.W == 2) return launch_blank_post_wide<2>(q, s);
-    if (q.W == 3) return launch_blank_post_wide<3>(q, s);
-    return launch_blank_post_wide<4>(q, s);
+    return with_constant<2, 3, 4>(q.W, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        const AlignParams &p = q.p.a;
+        const int crc = launch_blank_post_wide_chains<W>(q, s);
+        if (crc) return crc;
+        const int rows = (kPostThreads / kWave) * kPostRows;
+        return launch<blank_post_gamma_kernel<kWideAlignK * W>>(dim3((p.T + rows - 1) / rows, p.B), dim3(kPostThreads), 0, s, q.p);
+    });
 }
 
 }  // namespace ctc

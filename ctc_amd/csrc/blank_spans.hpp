@@ -2,10 +2,10 @@
 // (ctc_amd_blank_token_spans): where label j starts, where it ends, and the mean posterior of the frames
 // the best path gives it.  Included by blank_align.hip behind the narrow and the wide read-outs, whose launches it
 // strings together on one stream:
-//   the best path             gather + blank_align_kernel<K> (S <= 255) or the wide gather + blank_align_wide_kernel:
+//   the best path             blank_table_gather_kernel + blank_align_kernel<K> (S <= 255) or blank_align_wide_kernel:
 //                             path and score go to the caller's buffers, the back-pointers are dead afterwards
 //   the posteriors' chains    blank_post_chain_kernel<K> on the SAME table (narrow: one gather serves both stages, see
-//                             run_blank_spans) or blank_post_wide_gather_kernel<W> + blank_post_wide_chain_kernel:
+//                             run_blank_spans) or the gather again, with c_t, + blank_post_wide_chain_kernel:
 //                             alpha' / beta' rows where the back-pointers were, nll to the caller
 //   blank_post_conf_kernel<K> blank_post_gamma_kernel's grid and row arithmetic (post_row_terms, post_row_inv), but of
 //                             each row only gamma[b, t, path[b, t]] is stored: frame_conf [B,T].  gamma itself is
@@ -142,7 +142,7 @@ static int launch_blank_conf_spans(const SpanParams &q, hipStream_t s)
 
 // S <= 255.  ONE gather serves both stages: run_blank_align<K> and blank_post_layout<K> put the table at the same
 // address with the same pitch (workspace + 256, align_row_pitch(K)), both stages would fill it with
-// blank_align_gather_kernel<K> from the same AlignParams, and blank_align_kernel<K> only reads it -- its back-pointers
+// the same blank_table_gather_kernel from the same AlignParams, and blank_align_kernel<K> only reads it -- its back-pointers
 // are in LDS and, beyond, in `spill` BEHIND the table.  The alpha' rows start where `spill` started: the back-pointers
 // are dead once the path is out, and the stream orders the chains behind the walk back.
 template <int K>
@@ -161,7 +161,7 @@ static int run_blank_spans(SpanParams &q, hipStream_t s)
 }
 
 // 256 <= S <= 1023.  Two gathers: the posteriors' table carries the row maximum c_t in a padding column that the best
-// path's gather fills with -inf (blank_post_wide_gather_kernel is a kernel of its own for that reason).  The second
+// path's gather (CMAX = false) fills with -inf.  The second
 // gather rewrites the table in place; the alpha' / beta' rows then cover the best path's back-pointer words.
 static int run_blank_spans_wide(SpanParams &q, hipStream_t s)
 {
@@ -170,13 +170,11 @@ static int run_blank_spans_wide(SpanParams &q, hipStream_t s)
     PostWideParams w;
     rc = blank_post_wide_layout(q.p, w);
     if (rc) return rc;
-    if (w.W == 2) rc = launch_blank_post_wide_chains<2>(w, s);
-    else if (w.W == 3) rc = launch_blank_post_wide_chains<3>(w, s);
-    else rc = launch_blank_post_wide_chains<4>(w, s);
-    if (rc) return rc;
-    if (w.W == 2) return launch_blank_conf_spans<2 * kWideAlignK>(q, s);
-    if (w.W == 3) return launch_blank_conf_spans<3 * kWideAlignK>(q, s);
-    return launch_blank_conf_spans<4 * kWideAlignK>(q, s);
+    return with_constant<2, 3, 4>(w.W, [&](auto n) {
+        constexpr int W = decltype(n)::value;
+        const int crc = launch_blank_post_wide_chains<W>(w, s);
+        return crc ? crc : launch_blank_conf_spans<W * kWideAlignK>(q, s);
+    });
 }
 
 }  // namespace ctc

@@ -4,6 +4,7 @@
 
 #include <atomic>
 #include <cstdlib>
+#include <type_traits>
 
 #include "../../include/ctc_amd.h"
 
@@ -59,6 +60,18 @@ inline int with_logit_elem(int x_dtype, F f)
     case CTC_AMD_BF16: return f(LogitElem<__bf16>{});
     case CTC_AMD_F16: return f(LogitElem<_Float16>{});
     default: return CTC_AMD_ERR_BAD_ARGUMENT;
+    }
+}
+
+// A run-time number as a template argument: f(std::integral_constant<int, N>()) for N = n if it is one of Ns..., else
+// for the last of them.
+template <int N, int... Ns, typename F>
+inline int with_constant(int n, F f)
+{
+    if constexpr (sizeof...(Ns) == 0) {
+        return f(std::integral_constant<int, N>());
+    } else {
+        return n == N ? f(std::integral_constant<int, N>()) : with_constant<Ns...>(n, f);
     }
 }
 

@@ -607,17 +607,7 @@ static NoblankPlan noblank_plan(const NoblankQuery &q)
     return pl;
 }
 
-// Step 3: the plan's numbers as template arguments.  f(std::integral_constant<int, N>()) for N = n if it is one of
-// Ns..., else for the last of them.
-template <int N, int... Ns, typename F>
-static int with_constant(int n, F f)
-{
-    if constexpr (sizeof...(Ns) == 0) {
-        return f(std::integral_constant<int, N>());
-    } else {
-        return n == N ? f(std::integral_constant<int, N>()) : with_constant<Ns...>(n, f);
-    }
-}
+// Step 3: the plan's numbers as template arguments (with_constant, launch.hpp).
 // f(n4, n2) for the twelve row chunkings that r16_shape gives
 template <typename F>
 static int with_row_chunks(int n4, int n2, F f)
