@@ -12,7 +12,8 @@ from .functional import (CTCLoss, binary_best_path, binary_ctc_loss, binary_post
                          TokenSpans, binary_token_spans, noblank_token_spans,
                          workspace_status,
                          CollapsedTokens, collapse_frames, edit_distance, label_error_rate,
-                         BeamHypotheses, FusedBeamHypotheses, blank_beam_search, noblank_beam_search)
+                         BeamHypotheses, FusedBeamHypotheses, blank_beam_search, noblank_beam_search,
+                         blank_sequence_scores, noblank_sequence_scores)
 from .modules import BlankCTC, NoBlankBinaryCTC, NoBlankCTC  # noqa: F401
 from .producer import LSTM_cell, head_backward, head_forward, lstm_backward, lstm_cell_step, lstm_forward, lstm_series  # noqa: F401
 from .producer import lstm_bias_grad_wide, lstm_series_backward_wide, lstm_series_wide  # noqa: F401
@@ -24,4 +25,5 @@ __all__ = ["CTCLoss", "NoBlankCTC", "NoBlankBinaryCTC", "BlankCTC", "noblank_ctc
            "blank_best_path", "blank_forced_align", "blank_posteriors", "blank_token_spans", "BlankTokenSpans",
            "TokenSpans", "noblank_token_spans", "binary_token_spans",
            "CollapsedTokens", "collapse_frames", "edit_distance", "label_error_rate",
-           "BeamHypotheses", "FusedBeamHypotheses", "blank_beam_search", "noblank_beam_search"]
+           "BeamHypotheses", "FusedBeamHypotheses", "blank_beam_search", "noblank_beam_search",
+           "blank_sequence_scores", "noblank_sequence_scores"]

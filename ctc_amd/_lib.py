@@ -119,6 +119,9 @@ PROTOTYPES = {
     # ... fused with a bigram table (language model / transition grammar) and a token bonus
     "ctc_amd_beam_search_lm": (_int, [_vp, _i64, _i64, _vp, _int, _int, _int, _int, _int, _int, _int, _int,
                                       _vp, _i64, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # exact scores of given label sequences: N candidates per sample (or one set shared by the batch) in one launch
+    "ctc_amd_sequence_scores": (_int, [_vp, _i64, _i64, _vp, _int, _int, _int, _int, _vp, _int, _i64, _i64, _int,
+                                       _vp, _i64, _vp, _int, _vp, _vp]),
 }
 
 _lib = None

@@ -1120,3 +1120,106 @@ def noblank_beam_search(logits, input_lengths, beam_width=16, nbest=1, top_class
     of ``lm`` is never read.  If row C forbids every class, no hypothesis exists for T_b >= 1 (``count`` 0)."""
     return _beam_search(logits, "logits", input_lengths, beam_width, nbest, top_classes, None, max_tokens,
                         lm, lm_weight, token_bonus)
+
+
+SEQUENCE_SCORES_MAX_LABELS = 255   # ctc_amd_sequence_scores: 511 blank-lattice states, at most 8 per lane of one wave
+
+
+def _sequence_scores(x, name, input_lengths, sequences, sequence_lengths, counts, blank):
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.dtype != torch.float32:
+        raise ValueError("ctc_amd: %s must be a float32 tensor [T,B,C]" % name)
+    T, B, C = x.shape
+    if T < 1 or B < 1 or C < 1:
+        raise ValueError("ctc_amd: %s needs T >= 1, B >= 1 and C >= 1, got %s" % (name, tuple(x.shape)))
+    if blank is not None and not 0 <= int(blank) < C:
+        raise ValueError("ctc_amd: blank must lie in [0, %d), got %d" % (C, int(blank)))
+    seq = sequences
+    if not isinstance(seq, torch.Tensor) or seq.dtype not in (torch.int32, torch.int64) or seq.dim() not in (2, 3):
+        raise ValueError("ctc_amd: sequences must be an int32 or int64 tensor [B,N,L] (per sample) or [N,L] (shared by "
+                         "the batch)")
+    shared = seq.dim() == 2
+    N, L = seq.shape[-2:]
+    if not shared and seq.shape[0] != B:
+        raise ValueError("ctc_amd: sequences must have shape [%d,N,L], got %s" % (B, tuple(seq.shape)))
+    if N < 1 or L < 1:
+        raise ValueError("ctc_amd: sequences needs N >= 1 and L >= 1, got %s" % (tuple(seq.shape),))
+    sl = sequence_lengths
+    if not isinstance(sl, torch.Tensor):
+        sl = torch.as_tensor(sl)
+    if sl.dtype not in (torch.int64, torch.int32, torch.int16, torch.uint8, torch.int8) or \
+            tuple(sl.shape) != tuple(seq.shape[:-1]):
+        raise ValueError("ctc_amd: sequence_lengths must be an integer tensor %s, got %s %s"
+                         % (list(seq.shape[:-1]), sl.dtype, tuple(sl.shape)))
+    if counts is not None and (not isinstance(counts, torch.Tensor) or counts.dim() != 1 or counts.shape[0] != B or
+                               counts.dtype != torch.int32):
+        raise ValueError("ctc_amd: counts must be an int32 tensor [%d] (the `count` of a BeamHypotheses)" % B)
+    if L > SEQUENCE_SCORES_MAX_LABELS:
+        raise _lib.CtcAmdError("ctc_amd: sequence scores take sequences of at most %d labels, got L = %d"
+                               % (SEQUENCE_SCORES_MAX_LABELS, L))
+    if not x.is_cuda:
+        raise ValueError("ctc_amd: %s must be on a HIP (cuda) device -- the engine has no CPU path" % name)
+    dev = x.device
+    xs = x.detach()
+    if xs.stride(2) != 1:
+        xs = xs.contiguous()
+    il = _lengths(input_lengths, B, "input_lengths", dev, T, lo=0)
+    if seq.device != dev:
+        seq = seq.to(dev, non_blocking=True)
+    if seq.stride(-1) != 1:
+        seq = seq.contiguous()
+    if sl.device != dev or sl.dtype != torch.int64:
+        sl = sl.to(device=dev, dtype=torch.int64, non_blocking=True)
+    if sl.stride(-1) != 1:
+        sl = sl.contiguous()
+    if counts is not None:
+        counts = _placed(counts.detach(), dev)
+    scores = torch.empty((B, N), dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    with _on_device(dev):
+        rc = lib.ctc_amd_sequence_scores(xs.data_ptr(), xs.stride(0), xs.stride(1), il.data_ptr(), T, B, C,
+                                         -1 if blank is None else int(blank), seq.data_ptr(),
+                                         int(seq.dtype == torch.int64), 0 if shared else seq.stride(0), seq.stride(-2), L,
+                                         sl.data_ptr(), 0 if shared else sl.stride(0),
+                                         None if counts is None else counts.data_ptr(), N, scores.data_ptr(),
+                                         _stream_handle(dev))
+    _lib.check(rc, "ctc_amd_sequence_scores")
+    return scores
+
+
+def blank_sequence_scores(log_probs, input_lengths, sequences, sequence_lengths, counts=None, blank=0):
+    """Exact scores of given label sequences on the blank lattice -> ``scores`` [B,N] float32: ``scores[b, n]`` is the
+    natural-log probability of candidate n for sample b, summed over ALL of its alignments of the first T_b frames --
+    ``-nll`` of ``blank_ctc_loss`` on that sequence as the target, where that is finite.  All N candidates of all samples
+    in one launch: N-best rescoring (``BeamHypotheses.scores`` is only a lower bound of this value), transcript retrieval,
+    scoring hypotheses made elsewhere.  There is NO gradient: the result does not require grad.
+
+    ``log_probs`` [T,B,C] float32 normalised log-probabilities on a HIP device (the contract of ``blank_ctc_loss``), any
+    frame / batch strides (a view with another class stride is made contiguous); ``input_lengths`` [B], 0 <= T_b <= T.
+    ``sequences``: int32 or int64, either ``[B,N,L]`` with ``sequence_lengths [B,N]`` (candidates per sample; a
+    ``BeamHypotheses`` goes in as it is: ``blank_sequence_scores(lp, il, hyp.tokens, hyp.lengths, counts=hyp.count)``) or
+    ``[N,L]`` with ``sequence_lengths [N]`` (one set shared by the batch: read through a batch stride of 0, never
+    materialised B times, and the same bits as the expanded tensor gives).  Values at and behind a sequence's length are
+    never read (-1 padding is fine).  ``counts``: optional int32 [B], the candidates of each sample that exist.
+    N >= 1 is otherwise unbounded; L <= 255 labels (``CtcAmdError`` beyond); any T, any C.
+
+    Decided inside the launch, in this order: n >= counts[b]: -inf.  A length < 0 or > L (a hypothesis the beam search
+    truncated): NaN, "not scored".  A label among the first ``len`` outside [0, C) or equal to ``blank``: NaN.  T_b = 0:
+    0 for the empty sequence, else -inf.  No alignment -- fewer frames than labels + repeats, or every alignment crosses a
+    ``-inf`` input (a masked vocabulary; allowed) --: -inf, never NaN and never the loss's 1e13.  The empty sequence scores
+    the all-blank path.  NaN inputs give an unspecified value.
+
+    One launch, no scratch, no host synchronisation, capture-safe, deterministic (two calls, or a graph replay, give the
+    same bits).  Within 1e-5 max(1, |score|) of float64 also at T = 2000.  DESIGN.md 3.15."""
+    return _sequence_scores(log_probs, "log_probs", input_lengths, sequences, sequence_lengths, counts, int(blank))
+
+
+def noblank_sequence_scores(logits, input_lengths, sequences, sequence_lengths, counts=None):
+    """``blank_sequence_scores`` on the no-blank lattice: ``logits`` [T,B,C] float32 RAW logits, as for every other
+    ``noblank_*`` function -- the kernel subtracts each row's log-sum-exp itself, in fp32, once for all candidates.  The
+    lattice is the loss's: stay / advance, from the first label at frame 0 to the last at frame T_b - 1, so the score is
+    ``-nll`` of ``noblank_ctc_loss`` on that target where that is finite.  For a sequence without equal neighbours that is
+    the probability that the frames collapse to it; with equal neighbours it is what the loss's lattice gives for that
+    target (the two labels are two states), not a collapse probability.  The empty sequence has an alignment only for
+    T_b = 0 (score 0; -inf for T_b >= 1); fewer frames than labels: -inf.  A row that is ``-inf`` throughout gives an
+    unspecified value.  No gradient; everything else as there."""
+    return _sequence_scores(logits, "logits", input_lengths, sequences, sequence_lengths, counts, None)

@@ -923,6 +923,54 @@ int ctc_amd_beam_search_lm(const float *x, int64_t stride_t, int64_t stride_b, c
                            int32_t *tokens, int64_t *lengths, float *scores, float *ctc_scores, int32_t *count,
                            void *scratch, size_t scratch_bytes, void *stream);
 
+/* Scores of given label sequences: scores[b, n] = the natural-log probability of candidate n for sample b,
+ * summed over ALL of its alignments of the first T_b frames -- the exact value `scores` of ctc_amd_beam_search is a lower
+ * bound of; N-best rescoring, transcript retrieval, scoring hypotheses made elsewhere.  One launch for all N candidates
+ * of all samples: a sample's rows are brought on chip once per group of 8 candidates and every candidate's forward chain
+ * is fed from them.  No gradient, no scratch, no atomics, no waiting between workgroups (deterministic: the same inputs
+ * give the same bits), no allocation and no host synchronisation.
+ *   x          [T,B,C] fp32 at x[t * stride_t + b * stride_b + c] (strides in elements, unit class stride).  blank >= 0:
+ *              normalised log-probabilities, the contract of ctc_amd_blank_loss_grad; the lattice is torch.nn.CTCLoss's
+ *              (blanks optional, mandatory between equal neighbours) and the score is -nll of ctc_amd_blank_loss_grad on
+ *              that sequence as the target, where that is finite.  blank < 0: the no-blank lattice, x holds raw logits and
+ *              the kernel subtracts each row's log-sum-exp in fp32; transitions are stay / advance from state 0 at frame 0
+ *              to state len - 1 at frame T_b - 1 (the lattice of ctc_amd_noblank_loss_grad): for a sequence without equal
+ *              neighbours the probability that the frames collapse to it, with equal neighbours what that lattice gives
+ *              (the two labels are two states; it is not a collapse probability).
+ *   in_len     [B] int64, 0 <= T_b <= T (clamped to that range); frames t >= T_b are never read
+ *   seq        the labels of candidate n of sample b at seq[b * seq_stride_b + n * seq_stride_n + i], i < L; int32, or
+ *              int64 when seq_i64 != 0; strides in elements.  seq_stride_b = 0: one set of candidates shared by the batch
+ *              (the same bits as the set repeated per sample).  Elements at and behind a candidate's length are never
+ *              read (-1 padding is fine).
+ *   seq_len    the lengths at seq_len[b * len_stride_b + n], int64 (len_stride_b = 0: shared)
+ *   count      [B] int32 or NULL: the candidates of sample b that exist (the `count` of ctc_amd_beam_search)
+ *   scores     [B,N] fp32 out; every element is written
+ * Decided inside the launch, in this order:
+ *   n >= count[b]                                   -inf  (rows of a beam search's output that do not exist stay -inf)
+ *   len < 0 or len > L                              NaN   ("not scored": e.g. a hypothesis the beam search truncated)
+ *   a label among the first len outside [0, C), or equal to blank             NaN
+ *   T_b = 0                                         0 for len = 0, else -inf
+ *   no alignment                                    -inf, never NaN and never the losses' 1e13 sentinel: too few frames
+ *                                                   (T_b < len; blank lattice: T_b < len + repeats), or every
+ *                                                   alignment crosses a -inf input (-inf inputs are allowed: a masked
+ *                                                   vocabulary)
+ *   len = 0                                         blank lattice: the all-blank path, the sum over t < T_b of
+ *                                                   x[t, blank]; no-blank lattice: -inf for T_b >= 1
+ * NaN inputs, and a no-blank row that is -inf throughout: the value is unspecified, the launch ends.
+ * Arithmetic: log2-domain fp32 chains, renormalised every 8 frames against an exactly kept offset (the largest of the
+ * candidate's own states goes to [0, 1); register states beyond its lattice are held at -inf), so a step rounds at the size
+ * of a state's distance from the best one, not of the score: within 1e-5 max(1, |score|) of float64 at T = 2000, for scores
+ * of magnitude 10 as for 10^4.
+ * A NULL x, in_len, seq, seq_len or scores, T, B, C, N or L < 1, blank >= C: CTC_AMD_ERR_BAD_ARGUMENT; L > 255 (511
+ * blank-lattice states, 8 per lane of one wave), or more than 2^31 - 1 workgroups (B ceil(N / 8)):
+ * CTC_AMD_ERR_UNSUPPORTED_SHAPE; both before any HIP call.  Any T, any N, any C (C > 4096: the rows are not staged on chip,
+ * every chain gathers from memory -- correct and slow). */
+int ctc_amd_sequence_scores(const float *x, int64_t stride_t, int64_t stride_b, const int64_t *in_len,
+                            int T, int B, int C, int blank /* < 0: the no-blank lattice, x raw logits */,
+                            const void *seq, int seq_i64, int64_t seq_stride_b, int64_t seq_stride_n, int L,
+                            const int64_t *seq_len, int64_t len_stride_b, const int32_t *count /* or NULL */,
+                            int N, float *scores, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
