@@ -440,7 +440,8 @@ struct R16Row : R16RawRegs<sizeof(E) == 2, N4, N2> {
         if ((n & 1) == 0) m = vmax(m, e[n - 1]);
         return m;
     }
-    // the lane's sum of the raw elements (`valid_last`: the last chunk lies inside the row)
+    // the lane's sum of the raw elements (`valid_last`: the last chunk lies inside the row) -- the diagnostics-only copy of
+    // the smoothing code in noblank_km.hpp still sums this way
     __device__ __forceinline__ float sum(bool valid_last) const
     {
         float s = 0.f;
@@ -451,6 +452,21 @@ struct R16Row : R16RawRegs<sizeof(E) == 2, N4, N2> {
         }
 #pragma unroll
         for (int k = 0; k < N2; ++k) s += (k == N2 - 1 && !valid_last) ? 0.f : c[k].x + c[k].y;
+        return s;
+    }
+    // the lane's sum of the raw elements MINUS `m`, the row maximum (`valid_last`: the last chunk lies inside the row).
+    // The maximum leaves each element, not the sum: a common offset of the logits (softmax-invariant) would otherwise
+    // round the sum to its own magnitude -- logits near 3e4 at C = 158 sum to 4.7e6, ulp 0.5.
+    __device__ __forceinline__ float sum_below(float m, bool valid_last) const
+    {
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < N4; ++j) {
+            const float q = ((a[j].x - m) + (a[j].y - m)) + ((a[j].z - m) + (a[j].w - m));
+            s += ((kLast4 && j == N4 - 1) && !valid_last) ? 0.f : q;
+        }
+#pragma unroll
+        for (int k = 0; k < N2; ++k) s += (k == N2 - 1 && !valid_last) ? 0.f : (c[k].x - m) + (c[k].y - m);
         return s;
     }
     // x <- exp2(x log2e + mb), the last chunk with `mbl` instead (= mb, or -inf for a lane whose last chunk is a
@@ -892,7 +908,11 @@ __global__ __launch_bounds__(kThreads, 4) void noblank_r16_kernel(NoblankParams 
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 const float ec = (xv[s] - m) * kLog2e;
-                const float e2 = fmaxf(smooth ? p.ls_a * ec : ec, kXrMinLog2);
+                // smoothed with a = lambda - b <= 0 (lambda <= 1 / (C + 1)): a ec >= 0, and a masked label class would
+                // make it +inf or a number beyond the int exponent of a cell -- clamped from above as well (the sample is
+                // without an alignment through its row constant anyway; 0 * -inf = NaN falls to the lower clamp: no mass)
+                float e2 = fmaxf(smooth ? p.ls_a * ec : ec, kXrMinLog2);
+                if (smooth) e2 = fminf(e2, -kXrMinLog2);
                 const float fl = __builtin_floorf(e2);
                 // (an emission at the clamp -- a -inf or pad logit on a label class -- keeps the clamp's exponent and carries no mass)
                 const float pm = e2 > kXrMinLog2 ? __builtin_amdgcn_exp2f(e2 - fl) : 0.f;
@@ -924,9 +944,9 @@ __global__ __launch_bounds__(kThreads, 4) void noblank_r16_kernel(NoblankParams 
         const int t = tv[g];
         const bool live = t >= 0 && t < Tb;
         const float m = mrow[g];
-        float sx = 0.f;                                      // label smoothing: sum of the row's logits
+        float sx = 0.f;                                      // label smoothing: sum of the row's logits below their maximum
         if (smooth) {
-            sx = x.sum(col_ok);
+            sx = x.sum_below(m, col_ok);
             row16_allsum(sx);
         }
         const float mb = -m * kLog2e;
@@ -934,7 +954,13 @@ __global__ __launch_bounds__(kThreads, 4) void noblank_r16_kernel(NoblankParams 
         row16_allsum(sum);
         const float l2sum = __builtin_amdgcn_logf(sum);
         rs[g] = live ? p.grad_scale * __builtin_amdgcn_rcpf(sum) : 0.f;
-        const float cst = smooth ? __builtin_fmaf(p.ls_b, __builtin_fmaf(sx - (float)p.C * m, kLog2e, -(float)p.C * l2sum), -p.ls_a * l2sum)
+        // (a -inf logit in the row: sx = cst = -inf, the sample has no alignment -- see `Tlive` below)
+        // Smoothed: `mb` is -max log2e ROUNDED, so every exponent above was (x - max) log2e + d with d = max log2e + mb,
+        // the rounding residue of that product (an fma gives it exactly), and l2sum carries d with it: up to 2e-3 per
+        // row for logits near 3e4.  It leaves here.  (The softmax of P3 is a ratio and never saw it; the plain loss
+        // keeps its constant as it was.)
+        const float l2x = smooth ? l2sum - __builtin_fmaf(m, kLog2e, mb) : l2sum;
+        const float cst = smooth ? __builtin_fmaf(p.ls_b, __builtin_fmaf(sx, kLog2e, -(float)p.C * l2x), -p.ls_a * l2x)
                                  : -l2sum;
         cacc += live ? cst : 0.f;
     }
@@ -977,7 +1003,23 @@ __global__ __launch_bounds__(kThreads, 4) void noblank_r16_kernel(NoblankParams 
     }
     if (!has_grad && !has_gamma) return;
 
-    const int Tlive = Tb;
+    bool starved = false;
+    // Smoothed: every emission carries b sum_n lp[n], and that term lives in the row constants, not in the chains' cells.
+    // A -inf logit in a live row (constant -inf), or pad logits whose constants alone carry nll to 1e12, leave the sample
+    // without an alignment while the chains still hold mass and `tot > 0` below says nothing.  The workers add up the
+    // constants as the alpha wave does (all are there once every worker is through P1b -- nobody waits for a chain
+    // here) and treat such a sample as one without live rows: zero gradient rows, no waiting for the chains.
+    int Tlive = Tb;
+    if (smooth) {
+        int spins = 0;
+        while (*(lds_cvint *)sm.done < kPipeWorkers) {
+            if (++spins >= kSpinLimit) { starved = true; break; }
+            __builtin_amdgcn_s_sleep(2);
+        }
+        lds_order();
+        const float csum = wave_sum(lane < 4 * kPipeWorkers ? sm.cs[lane] : 0.f);
+        if (__builtin_amdgcn_readfirstlane(csum * kLn2 > -1.0e12f ? 1 : 0) == 0) Tlive = 0;   // (NaN: no alignment either)
+    }
     const float gsc = p.grad_scale;
     Row::zero_tile(trow, i16);                               // the occupancy tile starts all zero and every group leaves it so
     lds_order();
@@ -1016,7 +1058,6 @@ __global__ __launch_bounds__(kThreads, 4) void noblank_r16_kernel(NoblankParams 
         grow[g] = reinterpret_cast<E *>(p.grad) + ((int64_t)(tv[g] > 0 ? tv[g] : 0) * p.B + b) * p.C;
         asm volatile("" : "+v"(grow[g]));
     }
-    bool starved = false;
 
     // P3: middle-out, one look at the chains' progress per group
     // Every live row has the SAME total sum_l alpha_t(l) beta_t(l) (the sample's likelihood), so the exponent
@@ -1115,7 +1156,9 @@ __global__ __launch_bounds__(kThreads, 4) void noblank_r16_kernel(NoblankParams 
             E *gp = grow[g];
             // a live row without mass: no alignment exists (through the emissions alone) -- a zero row, as a dead one
             const bool mass = !live || tot > 0.f;
-            if (smooth) x.template store_grad<NT, true>(gp, trow, i16, mass ? rs[g] * (1.f - p.ls_b) : 0.f, col_ok, live && mass ? -p.ls_b * gsc : 0.f);
+            // (smoothed: `live` is false on every row of a sample whose row constants leave it without an alignment, while
+            // rs[] still holds the scale of its rows -- both terms hang on live && tot > 0)
+            if (smooth) x.template store_grad<NT, true>(gp, trow, i16, live && mass ? rs[g] * (1.f - p.ls_b) : 0.f, col_ok, live && mass ? -p.ls_b * gsc : 0.f);
             else x.template store_grad<NT, false>(gp, trow, i16, mass ? rs[g] : 0.f, col_ok, 0.f);
         }
         lds_order();

@@ -477,7 +477,13 @@ def noblank_ctc_loss(logits, targets, input_lengths, target_lengths, batch_total
     """-> (loss, nll[B]); NoBlankCTC arithmetic.
 
     ``label_smoothing=lam`` selects the emission variant sketched in comments at NoBlankCTC.py:100-107 (the
-    true class weighted lam, every other class (1 - lam) / C); None = the module as shipped."""
+    true class weighted lam, every other class (1 - lam) / C); None = the module as shipped.  lam in [0, 1]; shapes of
+    the four-rows-per-wave kernel only (C even <= 256, S <= 31, T <= 168), fp32 / bf16 / fp16 logits.  lam = 1 is the
+    plain call bit for bit.  Every logit of a frame enters every emission of that frame, e = a lp[c_l] + b sum_n lp[n]
+    with b = (1 - lam) / C, a = lam - b: a sample with a -inf logit anywhere in a live frame, or with pad logits (-1e30)
+    whose sum alone carries nll to 1e12, has no alignment -- nll >= 1e12 (possibly +inf, never NaN), all of its gradient
+    rows exactly 0, and the batch loss is the mean of the nll as reported.  lam <= 1 / (C + 1) (a <= 0) is defined on
+    finite logits only."""
     if label_smoothing is None:
         out = _fast_apply(logits, targets, input_lengths, target_lengths, batch_total, _lib.NOBLANK)
         if out is not None:

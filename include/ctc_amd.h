@@ -94,7 +94,11 @@ int ctc_amd_noblank_loss_grad(const float *x, int64_t stride_t, int64_t stride_b
  * the numpy restatement and finite differences).  Shapes: C even <= 256, S <= 31, T <= 168, 8-byte aligned
  * rows (the four-rows-per-wave kernel); others return CTC_AMD_ERR_UNSUPPORTED_SHAPE.  lambda in [0, 1].
  * Every one of the C columns counts as a class in the sum over n, so do not combine this entry with a pad column
- * (LSTM_cell(pad_classes=True): its lp = -1e30 enters every frame's emission and every sample reports nll >= 1e12). */
+ * (LSTM_cell(pad_classes=True): its lp = -1e30 enters every frame's emission and every sample reports nll >= 1e12).
+ * For the same reason a -inf logit anywhere in a live row leaves the sample without an alignment here: nll >= 1e12
+ * (+inf through such a row, never NaN) and all of its gradient rows exactly 0, as for every sample whose nll reaches
+ * 1e12.  lambda = 1 is ctc_amd_noblank_loss_grad bit for bit; lambda <= 1 / (C + 1) (a <= 0) is defined on finite
+ * logits only. */
 int ctc_amd_noblank_smoothed_loss_grad(const float *x, int64_t stride_t, int64_t stride_b,
                                        const void *labels, int labels_i64,
                                        const int64_t *in_len, const int64_t *tgt_len,

@@ -441,7 +441,9 @@ def test_eval_loop(dev, calls):
 def test_label_smoothing_on_a_padded_series_shows_in_the_loss(dev):
     """Every column counts as a class in the smoothed emission, the pad column's lp = -1e30 included (the float64 fact:
     tests/test_train_step_ref.py): behind LSTM_cell(pad_classes=True) every sample reports nll >= 1e12, the library's "no
-    alignment", and the gradients stay finite -- a caller's loss log shows the combination; it is not silently wrong"""
+    alignment", and the gradients stay finite -- a caller's loss log shows the combination; it is not silently wrong.
+    (Such a sample's rows of the loss's gradient are exactly 0, as for every sample without an alignment -- asserted in
+    tests/test_smoothing_gpu.py; they were (1 - b) softmax - a occupancy - b before that rule reached the smoothed loss.)"""
     import ctc_amd
     name = "ref33_pad"
     case, batch = R.CASES[name], R.reference(name)["batch"]
