@@ -1096,169 +1096,196 @@ __global__ __launch_bounds__(kBinThreads) void binary_pipe_kernel(BinaryParams p
     stamp(p, 7);
 }
 
-// pitch of the label-row images the MFMA kernels read: >= C (+K padding), PD = 2 (mod 32): conflict-free MFMA
-// fragment reads
-static int binary_image_pitch(int C)
+// pitch of an LDS image whose rows MFMA fragment reads walk: >= C rounded up to `unit` columns (K padding), and
+// = rem (mod 32).  The D and label-row images of binary_pipe_kernel and binary_mfma_kernel: unit 4, rem 2 -- conflict-free
+// 4-byte fragment reads.  binary_flow_kernel's D and fp32 target images: unit 16, rem 4 -- the 16-byte fragment reads
+// D[16m + (lane & 15)][.. + 4 or 8 (lane >> 4) ..] of sixteen lanes fall on sixteen different groups of four banks.
+static int binary_image_pitch(int C, int unit, int rem)
 {
-    int PD = (C + 3) / 4 * 4 + 2;
-    while (PD % 32 != 2) PD += 2;
+    int PD = (C + unit - 1) / unit * unit + rem;
+    while (PD % 32 != rem) PD += rem;
     return PD;
-}
-
-template <bool WT, bool GAMMA = false, typename E = float>
-static int launch_binary_pipe_wt(int ch, size_t smem, hipStream_t s, const BinaryParams &p, int PD)
-{
-    const dim3 grid(p.B), block(kBinThreads);
-    switch (ch) {
-        case 1: return launch<binary_pipe_kernel<1, WT, GAMMA, E>>(grid, block, smem, s, p, PD);
-        case 2: return launch<binary_pipe_kernel<2, WT, GAMMA, E>>(grid, block, smem, s, p, PD);
-        case 3: return launch<binary_pipe_kernel<3, WT, GAMMA, E>>(grid, block, smem, s, p, PD);
-        default: return launch<binary_pipe_kernel<4, WT, GAMMA, E>>(grid, block, smem, s, p, PD);
-    }
-}
-
-static int launch_binary_pipe(int ch, size_t smem, hipStream_t s, const BinaryParams &p, int PD)
-{
-    const bool wt = (size_t)8 * p.T * p.B * p.C <= ((size_t)230 << 20);   // logits + gradient within the memory-side cache
-    return wt ? launch_binary_pipe_wt<true>(ch, smem, s, p, PD) : launch_binary_pipe_wt<false>(ch, smem, s, p, PD);
 }
 
 #include "binary_flow.hpp"
 
-template <int K>
-static int launch_binary_mfma(int ch, size_t smem, hipStream_t s, const BinaryParams &p, int Tpad, int PD)
+// ---- host side of the entry points: parameters, then a plan, then a launch -------------------------
+
+// Forced kernel choices and the debug stop of the diagnostics build (launch.hpp: the product library reads none of them).
+struct BinarySwitches {
+    bool valu, no_pipe, no_flow;
+    int stop;                   // BinaryParams::stop
+};
+static const BinarySwitches &binary_switches()
 {
-    const dim3 grid(p.B), block(kBinThreads);
-    const bool wt = (size_t)8 * p.T * p.B * p.C <= ((size_t)230 << 20);   // logits + gradient within the memory-side cache
-#define CTC_BIN_CASE(N)                                                                                        \
-    case N: return wt ? launch<binary_mfma_kernel<K, N, true>>(grid, block, smem, s, p, Tpad, PD)               \
-                      : launch<binary_mfma_kernel<K, N, false>>(grid, block, smem, s, p, Tpad, PD);
-    switch (ch) {
-        CTC_BIN_CASE(1) CTC_BIN_CASE(2) CTC_BIN_CASE(3)
-        default: return wt ? launch<binary_mfma_kernel<K, 4, true>>(grid, block, smem, s, p, Tpad, PD)
-                           : launch<binary_mfma_kernel<K, 4, false>>(grid, block, smem, s, p, Tpad, PD);
+    static const BinarySwitches sw = {diag_env("CTC_AMD_BINARY_VALU") != 0, diag_env("CTC_AMD_BINARY_NOPIPE") != 0,
+                                      diag_env("CTC_AMD_BINARY_NOFLOW") != 0, diag_env("CTC_AMD_DEBUG_STOP")};
+    return sw;
+}
+
+// Step 1: what the kernels take, from an entry point's arguments.  `gamma` set: the posteriors call (no gradient, scales
+// and switches of 0), whose batch sum of the in-launch reduction lands in a spare workspace word.  Only a negative stop
+// is passed on.  SP and CP belong to the plan (binary_launch): the fused kernel takes the unpadded SP.
+static int binary_params(BinaryParams &p, const void *x, int64_t stride_t, int64_t stride_b, const float *y,
+                         const int64_t *in_len, const int64_t *tgt_len, int T, int B, int C, int S, float loss_scale,
+                         float grad_scale, float *nll, float *loss, float *grad, float *gamma, void *workspace,
+                         const BinarySwitches &sw)
+{
+    if (!x || !y || !in_len || !tgt_len || !nll || !(loss || gamma) || !workspace) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (T < 1 || B < 1 || C < 1 || S < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
+    p.x = static_cast<const float *>(x);                     // (elements of the kernel's E: the kernels cast it back)
+    p.st = stride_t; p.sb = stride_b; p.y = y;
+    p.in_len = in_len; p.tgt_len = tgt_len;
+    p.T = T; p.B = B; p.C = C; p.S = S;
+    p.stop = sw.stop < 0 ? sw.stop : 0;
+    p.loss_scale = loss_scale; p.grad_scale = grad_scale;
+    p.nll = nll; p.loss = gamma ? reinterpret_cast<float *>(static_cast<char *>(workspace) + 32) : loss;
+    p.grad = gamma ? nullptr : grad; p.gamma = gamma;
+    p.counter = static_cast<unsigned *>(workspace);
+    return 0;
+}
+
+// Step 2: which kernel takes a call.  Everything the choice depends on (dtype, of x, is the launch's: no rule reads it) ...
+struct BinaryQuery {
+    int T, B, C, S, dtype;
+    bool want_gamma;
+    BinarySwitches sw;
+};
+// ... and the choice: the template selectors of the family's kernel (K states per lane, ch 64-column chunks of a row, wt
+// write-through gradient stores), BinaryParams::SP, the kernel's own arguments (Tpad: T in whole emission tiles, pd: the
+// pitch of its LDS images), grid, dynamic LDS.  What a family does not take is 0.
+enum BinaryFamily { kBinaryUnsupported = 0, kBinaryFlow, kBinaryPipe, kBinaryMfma, kBinaryFused };
+struct BinaryPlan {
+    int family, K, SP, ch, wt, Tpad, pd, grid;
+    size_t lds;
+};
+static int binary_row_pitch(int C) { return C | 1; }         // BinaryParams::CP, odd: conflict-free column walks
+
+static BinaryPlan binary_plan(const BinaryQuery &q)
+{
+    // S <= 256.  The posteriors fall out of the gradient phase of the streamed and the pipelined kernel: shapes of the
+    // pipelined kernel only, refused before anything else; always write-through; no diagnostic switch reaches them.
+    const auto [K, SP] = lane_states(q.S);
+    if (K > 4 || (q.want_gamma && (q.S > kWave || q.T > kPipeMaxT || q.C > 256))) return BinaryPlan{};
+    const BinarySwitches sw = q.want_gamma ? BinarySwitches{} : q.sw;
+    // fast path: MFMA contractions, rows resident (T <= 160, C <= 256, images fit in LDS)
+    if (q.T <= (K == 1 ? kPipeMaxT : kBinRows * kBinWaves) && q.C <= 256 && !sw.valu) {
+        BinaryPlan pl = {};
+        pl.K = K; pl.grid = q.B;
+        pl.SP = (SP + 3) / 4 * 4;                            // K padding of the gamma . Y product (a multiple of K <= 4 too)
+        pl.ch = (q.C + kWave - 1) / kWave;
+        pl.wt = q.want_gamma || within_memory_side_cache(8, q.T, q.B, q.C);   // logits + gradient
+        const bool workers = K == 1 && !sw.no_pipe;          // the two kernels of scan waves and workers
+        if (workers && !sw.no_flow && q.T <= kFlowMaxT && pl.ch <= 3) {   // (four column chunks: 4 registers over the budget)
+            pl.pd = binary_image_pitch(q.C, 16, 4);          // the streamed kernel (binary_flow.hpp) has its own image pitch
+            pl.lds = binary_flow_smem_bytes(q.T, pl.SP, pl.pd, q.C);
+            if (pl.lds <= kMaxLds) { pl.family = kBinaryFlow; return pl; }
+        }
+        pl.pd = binary_image_pitch(q.C, 4, 2);
+        pl.lds = binary_pipe_smem_bytes(q.T, pl.SP, pl.pd);
+        if (workers && pl.lds <= kMaxLds) { pl.family = kBinaryPipe; return pl; }
+        if (q.want_gamma) return BinaryPlan{};               // (no other kernel has the posteriors)
+        pl.Tpad = (q.T + 15) / 16 * 16;
+        pl.lds = binary_mfma_smem_bytes(q.T, pl.Tpad, pl.SP, pl.pd);
+        if (pl.lds <= kMaxLds && q.T <= kBinRows * kBinWaves) { pl.family = kBinaryMfma; return pl; }
     }
-#undef CTC_BIN_CASE
+    BinaryPlan pl = {};                                      // the VALU kernel: the unpadded SP, no write-through form
+    pl.family = kBinaryFused; pl.K = K; pl.SP = SP; pl.grid = q.B;
+    pl.lds = binary_smem_bytes(q.T, SP, q.S, binary_row_pitch(q.C));
+    return pl.lds <= kMaxLds ? pl : BinaryPlan{};
+}
+
+// Step 3: the plan's numbers as template arguments (with_constant, with_logit_elem: launch.hpp).
+static int binary_launch(const BinaryPlan &pl, int dtype, BinaryParams &p, hipStream_t s)
+{
+    const dim3 grid(pl.grid), block(kBinThreads);
+    p.SP = pl.SP; p.CP = binary_row_pitch(p.C);
+    // the streamed / pipelined kernel <CH, WT, GAMMA, E>: the loss on fp32 logits, the posteriors on the three element types
+    auto workers = [&](auto wt, auto gamma, auto elem) {
+        constexpr bool WT = decltype(wt)::value != 0, GAMMA = decltype(gamma)::value;
+        using E = typename decltype(elem)::type;
+        if (pl.family == kBinaryFlow)   // (a with_constant list ends in its fallthrough: binary_plan gives this kernel ch <= 3 only)
+            return with_constant<1, 2, 3>(pl.ch, [&](auto ch) {
+                return launch<binary_flow_kernel<decltype(ch)::value, WT, GAMMA, E>>(grid, block, pl.lds, s, p, pl.pd);
+            });
+        return with_constant<1, 2, 3, 4>(pl.ch, [&](auto ch) {
+            return launch<binary_pipe_kernel<decltype(ch)::value, WT, GAMMA, E>>(grid, block, pl.lds, s, p, pl.pd);
+        });
+    };
+    switch (pl.family) {
+        case kBinaryFlow:
+        case kBinaryPipe:
+            if (p.gamma) return with_logit_elem(dtype, [&](auto elem) { return workers(std::true_type(), std::true_type(), elem); });
+            return with_constant<0, 1>(pl.wt, [&](auto wt) { return workers(wt, std::false_type(), LogitElem<float>()); });
+        case kBinaryMfma:
+            return with_constant<1, 2, 4>(pl.K, [&](auto k) {
+                return with_constant<1, 2, 3, 4>(pl.ch, [&](auto ch) {
+                    return with_constant<0, 1>(pl.wt, [&](auto wt) {
+                        return launch<binary_mfma_kernel<decltype(k)::value, decltype(ch)::value, decltype(wt)::value != 0>>(
+                            grid, block, pl.lds, s, p, pl.Tpad, pl.pd);
+                    });
+                });
+            });
+        case kBinaryFused:
+            return with_constant<1, 2, 4>(pl.K, [&](auto k) {
+                return launch<binary_fused_kernel<decltype(k)::value>>(grid, block, pl.lds, s, p);
+            });
+        default: return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
+    }
 }
 
 }  // namespace ctc
 
 using namespace ctc;
 
-extern "C" int ctc_amd_binary_loss_grad(const float *x, int64_t stride_t, int64_t stride_b,
-                                        const float *y,
-                                        const int64_t *in_len, const int64_t *tgt_len,
-                                        int T, int B, int C, int S,
-                                        float loss_scale, float grad_scale,
-                                        float *nll, float *loss, float *grad,
+extern "C" int ctc_amd_binary_loss_grad(const float *x, int64_t stride_t, int64_t stride_b, const float *y,
+                                        const int64_t *in_len, const int64_t *tgt_len, int T, int B, int C, int S,
+                                        float loss_scale, float grad_scale, float *nll, float *loss, float *grad,
                                         void *workspace, void *stream)
 {
-    if (!x || !y || !in_len || !tgt_len || !nll || !loss || !workspace) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (T < 1 || B < 1 || C < 1 || S < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
-    const auto [K, SP] = lane_states(S);
-    if (K > 4) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
+    const BinarySwitches &sw = binary_switches();
     BinaryParams p;
-    p.x = x; p.st = stride_t; p.sb = stride_b; p.y = y;
-    p.in_len = in_len; p.tgt_len = tgt_len;
-    p.T = T; p.B = B; p.C = C; p.S = S;
-    p.SP = SP;
-    p.CP = C | 1;                                            // odd pitch: conflict-free column walks
-    p.loss_scale = loss_scale; p.grad_scale = grad_scale;
-    p.nll = nll; p.loss = loss; p.grad = grad; p.gamma = nullptr;
-    p.counter = static_cast<unsigned *>(workspace);
-    static const int debug_stop = diag_env("CTC_AMD_DEBUG_STOP");
-    static const bool binary_valu = diag_env("CTC_AMD_BINARY_VALU") != 0;
-    p.stop = debug_stop < 0 ? debug_stop : 0;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // fast path: MFMA contractions, rows resident (T <= 160, C <= 256, images fit in LDS)
-    if (T <= (K == 1 ? kPipeMaxT : kBinRows * kBinWaves) && C <= 256 && !binary_valu) {
-        BinaryParams q = p;
-        q.SP = (p.SP + 3) / 4 * 4;                           // K padding of the gamma . Y product
-        if (q.SP % K) q.SP = (q.SP + 4 * K - 1) / (4 * K) * (4 * K);
-        const int Tpad = (T + 15) / 16 * 16;
-        const int PD = binary_image_pitch(C);
-        const size_t need = binary_mfma_smem_bytes(T, Tpad, q.SP, PD);
-        const int ch = (C + kWave - 1) / kWave;
-        static const bool no_pipe = diag_env("CTC_AMD_BINARY_NOPIPE") != 0;
-        static const bool no_flow = diag_env("CTC_AMD_BINARY_NOFLOW") != 0;
-        if (K == 1 && !no_pipe && !no_flow && T <= kFlowMaxT && ch <= 3) {   // (four column chunks: 4 registers over the budget)   // the streamed kernel (binary_flow.hpp) has its own image pitch
-            const int PF = binary_flow_pitch(C);
-            const size_t fb = binary_flow_smem_bytes(T, q.SP, PF, C);
-            if (fb <= kMaxLds) return launch_binary_flow(ch, fb, s, q, PF);
-        }
-        if (K == 1 && !no_pipe && binary_pipe_smem_bytes(T, q.SP, PD) <= kMaxLds)
-            return launch_binary_pipe(ch, binary_pipe_smem_bytes(T, q.SP, PD), s, q, PD);
-        if (need <= kMaxLds && T <= kBinRows * kBinWaves) {
-            switch (K) {
-                case 1: return launch_binary_mfma<1>(ch, need, s, q, Tpad, PD);
-                case 2: return launch_binary_mfma<2>(ch, need, s, q, Tpad, PD);
-                default: return launch_binary_mfma<4>(ch, need, s, q, Tpad, PD);
-            }
-        }
-    }
-    const size_t smem = binary_smem_bytes(T, p.SP, S, p.CP);
-    if (smem > kMaxLds) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
-    const dim3 grid(B), block(kBinThreads);
-    switch (K) {
-        case 1: return launch<binary_fused_kernel<1>>(grid, block, smem, s, p);
-        case 2: return launch<binary_fused_kernel<2>>(grid, block, smem, s, p);
-        default: return launch<binary_fused_kernel<4>>(grid, block, smem, s, p);
-    }
+    if (const int rc = binary_params(p, x, stride_t, stride_b, y, in_len, tgt_len, T, B, C, S, loss_scale, grad_scale, nll,
+                                     loss, grad, nullptr, workspace, sw))
+        return rc;
+    return binary_launch(binary_plan({T, B, C, S, CTC_AMD_F32, false, sw}), CTC_AMD_F32, p, static_cast<hipStream_t>(stream));
 }
 
-
 // Per-step posteriors of the binary lattice: gamma[b,t,l] = P(label row l at step t | x, targets), the
-// quantity the loss gradient contracts with the target rows -- it falls out of the pipelined kernel's gradient phase.
-// Shapes of that kernel only (S <= 64, T <= 168, C <= 256, images within LDS); others: CTC_AMD_ERR_UNSUPPORTED_SHAPE.
-static int binary_posteriors_entry(const void *x, int x_dtype, int64_t stride_t, int64_t stride_b, const float *y,
-                                   const int64_t *in_len, const int64_t *tgt_len, int T, int B, int C, int S,
-                                   float *nll, float *gamma, void *workspace, void *stream)
+// quantity the loss gradient contracts with the target rows, on logits of x_dtype (a 2-byte element is read as it lies
+// and widened exactly).  Shapes of the streamed and the pipelined kernel only (S <= 64, T <= 168, C <= 256, images within
+// LDS); others: CTC_AMD_ERR_UNSUPPORTED_SHAPE.  No diagnostic switch is read.
+extern "C" int ctc_amd_binary_posteriors_typed(const void *x, int x_dtype, int64_t stride_t, int64_t stride_b, const float *y,
+                                               const int64_t *in_len, const int64_t *tgt_len, int T, int B, int C, int S,
+                                               float *nll, float *gamma, void *workspace, void *stream)
 {
     if (x_dtype != CTC_AMD_F32 && x_dtype != CTC_AMD_BF16 && x_dtype != CTC_AMD_F16) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (!x || !y || !in_len || !tgt_len || !nll || !gamma || !workspace) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (T < 1 || B < 1 || C < 1 || S < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (S > kWave || T > kPipeMaxT || C > 256) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
-    BinaryParams q;
-    q.x = static_cast<const float *>(x);                      // (elements of the kernel's E: the kernels cast it back)
-    q.st = stride_t; q.sb = stride_b; q.y = y;
-    q.in_len = in_len; q.tgt_len = tgt_len;
-    q.T = T; q.B = B; q.C = C; q.S = S;
-    q.SP = (S + 3) / 4 * 4;
-    q.CP = C | 1;
-    q.loss_scale = 0.f; q.grad_scale = 0.f;
-    q.nll = nll; q.grad = nullptr; q.gamma = gamma;
-    q.counter = static_cast<unsigned *>(workspace);
-    q.loss = reinterpret_cast<float *>(static_cast<char *>(workspace) + 32);   // the batch sum lands in a spare header word
-    q.stop = 0;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int ch = (C + kWave - 1) / kWave;
-    return with_logit_elem(x_dtype, [&](auto elem) {
-        using E = typename decltype(elem)::type;
-        if (T <= kFlowMaxT && ch <= 3) {                      // the streamed kernel, cut off after the posteriors
-            const int PF = binary_flow_pitch(C);
-            const size_t fb = binary_flow_smem_bytes(T, q.SP, PF, C);
-            if (fb <= kMaxLds) return launch_binary_flow_wt<true, true, E>(ch, fb, s, q, PF);
-        }
-        const int PD = binary_image_pitch(C);
-        const size_t smem = binary_pipe_smem_bytes(T, q.SP, PD);
-        if (smem > kMaxLds) return (int)CTC_AMD_ERR_UNSUPPORTED_SHAPE;
-        return launch_binary_pipe_wt<true, true, E>(ch, smem, s, q, PD);
-    });
+    BinaryParams p;
+    if (const int rc = binary_params(p, x, stride_t, stride_b, y, in_len, tgt_len, T, B, C, S, 0.f, 0.f, nll, nullptr, nullptr,
+                                     gamma, workspace, BinarySwitches{}))   // (no loss pointer: a null gamma is refused there)
+        return rc;
+    return binary_launch(binary_plan({T, B, C, S, x_dtype, true, BinarySwitches{}}), x_dtype, p, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int ctc_amd_binary_posteriors(const float *x, int64_t stride_t, int64_t stride_b, const float *y,
                                          const int64_t *in_len, const int64_t *tgt_len, int T, int B, int C, int S,
                                          float *nll, float *gamma, void *workspace, void *stream)
 {
-    return binary_posteriors_entry(x, CTC_AMD_F32, stride_t, stride_b, y, in_len, tgt_len, T, B, C, S, nll, gamma, workspace,
-                                   stream);
+    return ctc_amd_binary_posteriors_typed(x, CTC_AMD_F32, stride_t, stride_b, y, in_len, tgt_len, T, B, C, S, nll, gamma,
+                                           workspace, stream);
 }
 
-// The same on logits of x_dtype (CTC_AMD_F32: the entry above): a 2-byte element is read as it lies and widened exactly.
-extern "C" int ctc_amd_binary_posteriors_typed(const void *x, int x_dtype, int64_t stride_t, int64_t stride_b, const float *y,
-                                               const int64_t *in_len, const int64_t *tgt_len, int T, int B, int C, int S,
-                                               float *nll, float *gamma, void *workspace, void *stream)
+#ifdef CTC_AMD_DIAGNOSTICS
+// Diagnostic entry point (tests/test_binary_plan.py), not part of include/ctc_amd.h: binary_plan() for a call with these
+// properties, no device touched.  switches: bit 0 CTC_AMD_BINARY_VALU, 1 _NOPIPE, 2 _NOFLOW.
+// out[0..8] = family (BinaryFamily), K, SP, ch, wt, Tpad, pd, grid, LDS bytes.
+extern "C" int ctc_amd_debug_binary_plan(int T, int B, int C, int S, int dtype, int want_gamma, int switches, int64_t *out)
 {
-    return binary_posteriors_entry(x, x_dtype, stride_t, stride_b, y, in_len, tgt_len, T, B, C, S, nll, gamma, workspace,
-                                   stream);
+    if (!out || T < 1 || B < 1 || C < 1 || S < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
+    const BinaryPlan pl = binary_plan({T, B, C, S, dtype, want_gamma != 0,
+                                       {(switches & 1) != 0, (switches & 2) != 0, (switches & 4) != 0, 0}});
+    const int64_t v[9] = {pl.family, pl.K, pl.SP, pl.ch, pl.wt, pl.Tpad, pl.pd, pl.grid, (int64_t)pl.lds};
+    for (int i = 0; i < 9; ++i) out[i] = v[i];
+    return 0;
 }
+#endif

@@ -81,16 +81,6 @@ static size_t binary_flow_smem_bytes(int T, int SP, int PD, int C)
     return ((size_t)(3 * T + 2 * kPrefetch) * SP + kFlowFlags + ((T + 7) & ~3) + 64 + flow_y_floats(SP, C, PD) + (size_t)(T + 1) * PD) * 4;
 }
 
-// pitch of the D image (and of the fp32 target image): >= the K extent padded to 32, and = 4 (mod 32) -- the 16-byte
-// fragment reads D[16m + (lane & 15)][.. + 4 or 8 (lane >> 4) ..] of sixteen lanes then fall on sixteen different groups
-// of four banks
-static int binary_flow_pitch(int C)
-{
-    int PD = (C + 15) / 16 * 16 + 4;
-    while (PD % 32 != 4) PD += 4;
-    return PD;
-}
-
 // f = t0 + t1 + t2 exactly, each term a bf16 (8 significant bits); eight floats -> three packed operands of the bf16 MFMA
 __device__ __forceinline__ void split3_bf16(const float (&f)[8], u32x4 &t0, u32x4 &t1, u32x4 &t2)
 {
@@ -835,22 +825,4 @@ __global__ __launch_bounds__(kBinThreads) void binary_flow_kernel(BinaryParams p
         }
     }
     stamp(p, 7);
-}
-
-template <bool WT, bool GAMMA, typename E = float>
-static int launch_binary_flow_wt(int ch, size_t smem, hipStream_t s, const BinaryParams &p, int PD)
-{
-    const dim3 grid(p.B), block(kBinThreads);
-    switch (ch) {
-        case 1: return launch<binary_flow_kernel<1, WT, GAMMA, E>>(grid, block, smem, s, p, PD);
-        case 2: return launch<binary_flow_kernel<2, WT, GAMMA, E>>(grid, block, smem, s, p, PD);
-        case 3: return launch<binary_flow_kernel<3, WT, GAMMA, E>>(grid, block, smem, s, p, PD);
-        default: return launch<binary_flow_kernel<4, WT, GAMMA, E>>(grid, block, smem, s, p, PD);
-    }
-}
-
-static int launch_binary_flow(int ch, size_t smem, hipStream_t s, const BinaryParams &p, int PD)
-{
-    const bool wt = (size_t)8 * p.T * p.B * p.C <= ((size_t)230 << 20);   // logits + gradient within the memory-side cache
-    return wt ? launch_binary_flow_wt<true, false>(ch, smem, s, p, PD) : launch_binary_flow_wt<false, false>(ch, smem, s, p, PD);
 }

@@ -14,6 +14,10 @@ constexpr size_t kMaxLds = 160 * 1024;        // LDS per CU on gfx950
 constexpr size_t kDefaultDynLds = 64 * 1024;  // above this the attribute must be raised
 constexpr int kMaxDevices = 64;               // per-device caches below are indexed by the HIP device ordinal
 
+// Do the [T][B][C] logits and their gradient, `bytes` per element for the two together, stay within the memory-side
+// cache (256 MB)?  Then the gradient is stored write-through; beyond it, with non-temporal stores.
+inline bool within_memory_side_cache(size_t bytes, int T, int B, int C) { return bytes * T * B * C <= ((size_t)230 << 20); }
+
 // ordinal of the calling thread's current device, or -1 (then nothing is cached)
 inline int current_device()
 {

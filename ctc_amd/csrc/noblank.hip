@@ -564,8 +564,8 @@ static NoblankPlan noblank_plan(const NoblankQuery &q)
         pl.n4 = n4; pl.n2 = n2;
         pl.lds = r16_smem_bytes(q.T, z.SP, q.C);
         if (q.want_gamma) { pl.family = kNoblankR16; return pl; }
-        // logits + gradient beyond the memory-side cache (256 MB): non-temporal gradient stores
-        pl.nt = (size_t)2 * esz * q.T * q.B * q.C > ((size_t)230 << 20);
+        // logits + gradient beyond the memory-side cache: non-temporal gradient stores
+        pl.nt = !within_memory_side_cache(2 * esz, q.T, q.B, q.C);
 #ifdef CTC_AMD_DIAGNOSTICS
         // the chains split over exponent and mantissa waves (noblank_km.hpp) wherever its arrays fit and the number of
         // lattice paths leaves two mantissas room in fp32

@@ -66,3 +66,25 @@ def noblank_plan_entry():
         assert rc == 0, (T, B, C, S, dtype, st, sb, x_low, grad_low, want_grad, want_gamma, smooth, cus, sw)
         return dict(zip(NOBLANK_PLAN_FIELDS, out))
     return call
+
+
+BINARY_PLAN_FIELDS = ("family", "K", "SP", "ch", "wt", "Tpad", "pd", "grid", "lds")
+BINARY_PLAN_FAMILIES = ("unsupported", "flow", "pipe", "mfma", "fused")
+
+
+def binary_plan_entry():
+    """`ctc_amd_debug_binary_plan` of the diagnostics build (built on first use; no GPU needed), bound once for the tests
+    that ask which kernel a binary call gets -> call(T, B, C, S, dtype, want_gamma, sw) -> {field: value} of
+    BINARY_PLAN_FIELDS"""
+    import ctypes
+    from ctc_amd import build
+    fn = ctypes.CDLL(build.build_diag()).ctc_amd_debug_binary_plan
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_int64)]
+    out = (ctypes.c_int64 * len(BINARY_PLAN_FIELDS))()
+
+    def call(T, B, C, S, dtype, want_gamma, sw):
+        rc = fn(T, B, C, S, dtype, int(want_gamma), sw, out)
+        assert rc == 0, (T, B, C, S, dtype, want_gamma, sw)
+        return dict(zip(BINARY_PLAN_FIELDS, out))
+    return call

@@ -48,7 +48,8 @@ NOBLANK_FAMILY = {"xr_oddc": "xr", "xr_s40": "xr", "pipelined": "pipelined"}    
 NOBLANK_LOSS = [p for p in NOBLANK_SHAPES if p != "spans_k4"]
 R16 = [p for p in NOBLANK_LOSS if p.startswith("r16")]
 
-# binary: ctc_amd_binary_loss_grad (ctc_amd/csrc/binary.hip) restated in binary_kernel() below
+# binary: the kernel is the one binary_plan() names (ctc_amd/csrc/binary.hip; tests/test_binary_plan.py restates the rules
+# and asks the plan about every name here, tests/test_lattice_inputs_ref.py asks it too)
 BINARY_SHAPES = {
     "flow": (40, 2, 30, 12),            # streamed: S <= 64, T <= 160, C <= 192, its arrays within LDS
     "flow_c158": (40, 2, 158, 20),      # streamed, three column chunks
@@ -79,37 +80,6 @@ WRONGPEAK_K = {"r16_t168": 10.0, "pipelined": 10.0, "fused_t": 4.0, "glb": 4.0, 
 # 6e-6, and flow and valu_t keep x 4)
 BINARY_WRONGPEAK_K = {"pipe_t": 2.0, "flow_c158": 2.0, "mfma_k2": 2.0, "mfma_k4": 2.0, "valu_c": 2.0}
 KINDS = "abcde"                          # the samples of a masked no-blank batch, b % 5 (make_case)
-
-
-def binary_kernel(T, C, S):
-    """which kernel ctc_amd_binary_loss_grad launches by default, its conditions in its own order"""
-    K = 1 if S <= 64 else 2 if S <= 128 else 4
-    assert S <= 256
-    lds, pre = 160 * 1024, 4
-    if T <= (168 if K == 1 else 160) and C <= 256:
-        SP = (S + K - 1) // K * K
-        SP = (SP + 3) // 4 * 4
-        if SP % K:
-            SP = (SP + 4 * K - 1) // (4 * K) * (4 * K)
-        Tpad, ch = (T + 15) // 16 * 16, (C + 63) // 64
-        PD = (C + 3) // 4 * 4 + 2
-        while PD % 32 != 2:
-            PD += 2
-        if K == 1 and T <= 160 and ch <= 3:
-            PF = (C + 15) // 16 * 16 + 4
-            while PF % 32 != 4:
-                PF += 4
-            halfs = (SP + 1) * ((C + 31) // 32 * 32 + 8)             # the bf16 target image behind the fp32 one
-            images = ((SP * PF + 3) & ~3) + (((halfs + 1) // 2 + 3) & ~3)
-            if ((3 * T + 2 * pre) * SP + 64 + ((T + 7) & ~3) + 64 + images + (T + 1) * PF) * 4 <= lds:
-                return "flow"
-        if K == 1 and ((3 * T + 2 * pre) * SP + 32 + ((T + 3) & ~3) + 64 + SP * PD + T * PD) * 4 <= lds:
-            return "pipe"
-        if T <= 160 and ((3 * T + 2 * pre) * SP + 8 + Tpad + SP * PD + Tpad * PD) * 4 <= lds:
-            return "mfma%d" % K
-    SPv, CP = (S + K - 1) // K * K, C | 1
-    assert ((3 * T + 2 * pre) * SPv + 8 + S * CP + 16 * CP) * 4 <= lds
-    return "valu%d" % K
 
 
 def plain_bound(family, B):

@@ -8,12 +8,12 @@ failure here is the reduction's, not the lattice's; the lattice at the new batch
 sample that the test chooses (tests/batch_sum_ref.py; checked against the float64 oracle in tests/test_batch_sum_ref.py).
 
 Call sites (ctc_amd/csrc) by shape (T, C, S); tests/test_batch_sum_ref.py asserts the no-blank rows against the plan
-function, the binary rows follow ctc_amd_binary_loss_grad's selection (K = 1: streamed for T <= 160 and C <= 192, else
-pipelined for T <= 168 and C <= 256; K > 1: MFMA; C > 256: fused).  Nothing asserts the binary rows (the library has no
-plan entry for them): they depend on kFlowMaxT = 160 (binary_flow.hpp) and its three column chunks of 64, on
-kPipeMaxT = 168 and kBinRows * kBinWaves = 160 (binary.hip), on lane_states() (K = 2 from S = 65), on the C <= 256 test of
-the fast path and on each kernel's LDS need staying within kMaxLds at these shapes -- a change of one of them can move a
-row to another kernel, and this table has to follow:
+function, the binary rows follow binary_plan() (K = 1: streamed for T <= 160 and C <= 192, else pipelined for T <= 168
+and C <= 256; K > 1: MFMA; C > 256: fused) and tests/test_binary_plan.py asserts them against it at every batch size
+below: they depend on kFlowMaxT = 160 (binary_flow.hpp) and its three column chunks of 64, on kPipeMaxT = 168 and
+kBinRows * kBinWaves = 160 (binary.hip), on lane_states() (K = 2 from S = 65), on the C <= 256 test of the fast path and
+on each kernel's LDS need staying within kMaxLds at these shapes -- a change of one of them can move a row to another
+kernel, that test then fails, and this table has to follow:
 
     no-blank  (8, 8, 2)      noblank_r16.hpp, one sample per workgroup (B <= 512, and every forward-only call)
                              noblank_r16.hpp persistent (B > 512 with a gradient): one workgroup publishes many samples

@@ -8,8 +8,9 @@ import pytest
 
 from tests.lattice_inputs_ref import (BINARY_KERNEL, BINARY_SHAPES, CAP, KINDS, LOSS_PATHS, NOBLANK_FAMILY, NOBLANK_LOSS,
                                       NLL_RTOL, NOBLANK_SHAPES, PAD_LOGIT, PATH_SHAPES, POSTERIOR_SHAPES, R16, REGIMES, SHAPES,
-                                      binary_kernel, port64, reference, ties_closed_form)
-from tests.helpers import np_
+                                      port64, reference, ties_closed_form)
+from tests.helpers import binary_plan_entry, np_
+from tests.test_binary_plan import kernel_name
 from tests.test_noblank_plan import BF16, CUS, F32, FAMILIES, FIELDS, PS_PAIRS, Query
 
 CASES = [(f, p, r) for f in SHAPES for p in SHAPES[f] for r in REGIMES]
@@ -187,7 +188,7 @@ def test_two_byte_logits_get_r16(plan, path):
     assert plan(Query(*NOBLANK_SHAPES[path], dtype=BF16))["family"] == "r16"
 
 
-def test_posteriors_and_read_out_shapes(plan):
+def test_posteriors_and_read_out_shapes(plan, binary_plan):
     fam = [plan(Query(*NOBLANK_SHAPES[p], want_gamma=True))["family"] for p in POSTERIOR_SHAPES["noblank"]]
     assert fam == ["r16", "fused"]
     for family in SHAPES:                                     # the read-outs: one, two and four states per lane
@@ -197,11 +198,17 @@ def test_posteriors_and_read_out_shapes(plan):
         T, _, C, S = BINARY_SHAPES[p]
         assert S <= 64 and T <= 168 and C <= 256
     assert [BINARY_KERNEL[p] for p in POSTERIOR_SHAPES["binary"]] == ["flow", "pipe"]
+    assert [binary_plan(*BINARY_SHAPES[p], want_gamma=True) for p in POSTERIOR_SHAPES["binary"]] == ["flow", "pipe"]
+
+
+@pytest.fixture(scope="module")
+def binary_plan():
+    entry = binary_plan_entry()
+    return lambda T, B, C, S, want_gamma=False: kernel_name(entry(T, B, C, S, F32, want_gamma, 0))
 
 
 @pytest.mark.parametrize("path", list(BINARY_SHAPES))
-def test_binary_loss_shape_gets_the_kernel_its_name_says(path):
-    """binary_kernel() restates the conditions of ctc_amd_binary_loss_grad (there is no plan entry for the binary loss)"""
-    T, _, C, S = BINARY_SHAPES[path]
-    assert binary_kernel(T, C, S) == BINARY_KERNEL[path]
+def test_binary_loss_shape_gets_the_kernel_its_name_says(binary_plan, path):
+    """binary_plan() of ctc_amd/csrc/binary.hip, asked through the diagnostics build (tests/test_binary_plan.py)"""
+    assert binary_plan(*BINARY_SHAPES[path]) == BINARY_KERNEL[path]
     assert {BINARY_KERNEL[p] for p in BINARY_SHAPES} == {"flow", "pipe", "mfma2", "mfma4", "valu1"}
