@@ -1,7 +1,9 @@
 // The HEAD of the producer for batches beyond one workgroup's 256 rows: ctc_amd_head_forward_wide and
 // ctc_amd_head_backward_wide.  Included at the end of producer.hip (HeadParams, head_dot / head_linear / head_invstd /
 // head_bn_y / head_bn_relu / head_column_total, HeadBwdRowsParams, the layout and the products / reduce launches of the head's
-// backward are that file's, unchanged: every rounding of an element is the narrow path's own).
+// backward are that file's, unchanged: every rounding of an element is the narrow path's own).  So is the host code the two
+// widths share: head_forward_params (the forward entries' checks and HeadParams), head_shape_ok (one shape rule, the bound on B
+// its argument), head_backward_enqueue (the whole backward entry but the rows launch), scratch_base / scratch_up.
 //
 // BatchNorm's batch statistics are taken over the B rows of ONE frame, and B rows no longer fit one workgroup, so the sums over
 // a frame's rows cross workgroups -- at a kernel boundary, never inside a launch:
@@ -37,18 +39,7 @@ inline void head_wide_groups(int C, int &N, int &NG)
     N = (CT + NG - 1) / NG;
 }
 
-// what the entries take of (T, B, K, C): the narrow entries' rule with the batch bound lifted
-inline bool head_wide_shape_ok(int T, int B, int K, int C)
-{
-    if (B > kHeadWideMaxBatch || (K & 15) != 0) return false;
-    const int64_t R = (int64_t)T * B;
-    if (R > kHeadBwdMaxRows) return false;
-    int S, chunk;
-    head_bwd_splits(R, S, chunk);
-    const int64_t CT = (C + 15) / 16, KQ = (K / 16 + 3) / 4;
-    const int64_t tasks = CT * KQ * S + ((R + 15) / 16) * KQ + (3 * 16 * CT + 63) / 64;
-    return CT <= 65535 && tasks <= kHeadBwdMaxTasks;
-}
+// (what the entries take of (T, B, K, C): head_shape_ok, the narrow entries' rule, with kHeadWideMaxBatch for the bound on B)
 
 struct HeadWideLayout {                                      // byte offsets into the (aligned) scratch of the forward
     size_t lin, psum, total;
@@ -57,13 +48,12 @@ struct HeadWideLayout {                                      // byte offsets int
 
 inline HeadWideLayout head_wide_layout(int T, int B, int C)
 {
-    auto up = [](size_t v) { return (v + kHeadBwdAlign - 1) / kHeadBwdAlign * kHeadBwdAlign; };
     HeadWideLayout L;
     L.CP = 16 * ((C + 15) / 16);
     L.NB = (B + kHeadWideRows - 1) / kHeadWideRows;
     L.lin = 0;
-    L.psum = up((size_t)T * B * C * sizeof(float));
-    L.total = L.psum + up((size_t)T * L.NB * L.CP * sizeof(float));
+    L.psum = scratch_up((size_t)T * B * C * sizeof(float));
+    L.total = L.psum + scratch_up((size_t)T * L.NB * L.CP * sizeof(float));
     return L;
 }
 
@@ -257,7 +247,7 @@ inline int head_wide_launch_product(const HeadParams &p, float *psum, const Head
 
 extern "C" size_t ctc_amd_head_forward_wide_scratch_bytes(int T, int B, int K, int C)
 {
-    if (T < 1 || B < 1 || K < 1 || C < 1 || !ctc::head_wide_shape_ok(T, B, K, C)) return 0;
+    if (T < 1 || B < 1 || K < 1 || C < 1 || !ctc::head_shape_ok(T, B, K, C, ctc::kHeadWideMaxBatch)) return 0;
     return ctc::head_wide_layout(T, B, C).total + ctc::kHeadBwdAlign;             // (the entry aligns the pointer itself)
 }
 
@@ -271,32 +261,22 @@ extern "C" int ctc_amd_head_forward_wide_typed(const void *feat, int feat_dtype,
                                                float *linear_out, float *save_mean, float *save_var, float *save_invstd,
                                                void *scratch, size_t scratch_bytes, void *stream)
 {
-    if (feat_dtype != CTC_AMD_F32 && feat_dtype != CTC_AMD_BF16 && feat_dtype != CTC_AMD_F16) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (!feat || !weight || !bias || !bn_weight || !bn_bias || !out || !scratch) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (T < 1 || B < 1 || K < 1 || C < 1 || (running_mean == nullptr) != (running_var == nullptr)) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (out_stride_b < C) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (running_mean == nullptr && B < 2) return CTC_AMD_ERR_BAD_ARGUMENT;       // (torch raises too: one value per channel)
-    if (scratch_bytes < ctc_amd_head_forward_wide_scratch_bytes(T, B, K, C)) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (!ctc::head_wide_shape_ok(T, B, K, C) || !ctc::head_feat_aligned(feat, feat_dtype, feat_stride_t, feat_stride_b) ||
-        (reinterpret_cast<uintptr_t>(weight) & 15) != 0)
-        return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
+    ctc::HeadParams p;
+    int rc = ctc::head_forward_params(p, feat, feat_dtype, feat_stride_t, feat_stride_b, weight, bias, bn_weight, bn_bias,
+                                      running_mean, running_var, eps, mask, T, B, K, C, out, out_stride_t, out_stride_b,
+                                      linear_out, save_mean, save_var, save_invstd);
+    if (rc == CTC_AMD_ERR_BAD_ARGUMENT) return rc;
+    if (!scratch || scratch_bytes < ctc_amd_head_forward_wide_scratch_bytes(T, B, K, C)) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (rc || !ctc::head_shape_ok(T, B, K, C, ctc::kHeadWideMaxBatch)) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
     const ctc::HeadWideLayout L = ctc::head_wide_layout(T, B, C);
-    char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(scratch) + ctc::kHeadBwdAlign - 1) /
-                                          ctc::kHeadBwdAlign * ctc::kHeadBwdAlign);
+    char *base = ctc::scratch_base(scratch);
     float *psum = reinterpret_cast<float *>(base + L.psum);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool train = running_mean == nullptr;
-    ctc::HeadParams p;
-    p.feat = feat; p.fst = feat_stride_t; p.fsb = feat_stride_b;
-    p.w = weight; p.bias = bias; p.gamma = bn_weight; p.beta = bn_bias;
-    p.rmean = running_mean; p.rvar = running_var; p.mask = mask; p.eps = eps;
-    p.T = T; p.B = B; p.K = K; p.C = C;
-    p.out = out; p.ost = out_stride_t; p.osb = out_stride_b;
-    p.lin = (train && !linear_out) ? reinterpret_cast<float *>(base + L.lin) : linear_out;
-    p.smean = save_mean; p.svar = save_var; p.sinv = save_invstd;
+    if (train && !linear_out) p.lin = reinterpret_cast<float *>(base + L.lin);   // the statistics launch reads it
     int N, NG;
     ctc::head_wide_groups(C, N, NG);
-    int rc = ctc::head_with_elem(feat_dtype, [&](auto e) {
+    rc = ctc::with_logit_elem(feat_dtype, [&](auto e) {
         using E = typename decltype(e)::type;
         return N == 1   ? ctc::head_wide_launch_product<1, E>(p, psum, L, NG, st)
                : N == 2 ? ctc::head_wide_launch_product<2, E>(p, psum, L, NG, st)
@@ -322,8 +302,7 @@ extern "C" int ctc_amd_head_forward_wide(const float *feat, int64_t feat_stride_
 
 extern "C" size_t ctc_amd_head_backward_wide_scratch_bytes(int T, int B, int K, int C)
 {
-    if (T < 1 || B < 1 || K < 1 || C < 1 || !ctc::head_wide_shape_ok(T, B, K, C)) return 0;
-    return ctc::head_bwd_layout(T, B, K, C).total + ctc::kHeadBwdAlign;           // (the entry aligns the pointer itself)
+    return ctc::head_bwd_scratch_bytes(T, B, K, C, ctc::kHeadWideMaxBatch);
 }
 
 // ctc_amd_head_backward(_typed) for any batch up to kHeadWideMaxBatch: the walking row pass, then the narrow entry's products and
@@ -340,55 +319,13 @@ extern "C" int ctc_amd_head_backward_wide_typed(const float *d_out, int64_t dout
                                                 float *d_weight, float *d_bias, float *d_bn_weight, float *d_bn_bias,
                                                 void *scratch, size_t scratch_bytes, void *stream)
 {
-    if (feat_dtype != CTC_AMD_F32 && feat_dtype != CTC_AMD_BF16 && feat_dtype != CTC_AMD_F16) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (!d_out || !feat || !weight || !bn_weight || !bn_bias || !linear_out) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (!d_weight || !d_bias || !d_bn_weight || !d_bn_bias || !scratch) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (T < 1 || B < 1 || K < 1 || C < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
-    const bool train = save_mean && save_invstd && !running_mean && !running_var;
-    const bool eval = running_mean && running_var && !save_mean && !save_invstd;
-    if (!train && !eval) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (train && B < 2) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (dout_stride_b < C) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (d_feat && dfeat_stride_b < K) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (scratch_bytes < ctc_amd_head_backward_wide_scratch_bytes(T, B, K, C)) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (!ctc::head_wide_shape_ok(T, B, K, C) || !ctc::head_feat_aligned(feat, feat_dtype, feat_stride_t, feat_stride_b) ||
-        (reinterpret_cast<uintptr_t>(weight) & 15) != 0 || (d_feat && !ctc::head_dfeat_aligned(d_feat, feat_dtype)))
-        return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
-    const ctc::HeadBwdLayout L = ctc::head_bwd_layout(T, B, K, C);
-    char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(scratch) + ctc::kHeadBwdAlign - 1) /
-                                          ctc::kHeadBwdAlign * ctc::kHeadBwdAlign);
-    float *dlin = reinterpret_cast<float *>(base + L.dlin), *part = reinterpret_cast<float *>(base + L.part);
-    float *wpart = reinterpret_cast<float *>(base + L.wpart);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-
-    ctc::HeadBwdRowsParams r;
-    r.dout = d_out; r.dst = dout_stride_t; r.dsb = dout_stride_b;
-    r.lin = linear_out; r.gamma = bn_weight; r.beta = bn_bias;
-    r.smean = save_mean; r.sinv = save_invstd; r.rmean = running_mean; r.rvar = running_var;
-    r.mask = mask; r.eps = eps;
-    r.T = T; r.B = B; r.C = C; r.CP = L.CP;
-    r.dlin = dlin; r.part = part;
-    int rc = launch<ctc::head_wide_bwd_rows_kernel>(dim3(T, L.CP / 16), dim3(ctc::head_wide_block(B)), 0, st, r);
-    if (rc) return rc;
-
-    ctc::HeadBwdProdParams q;
-    q.dlin = dlin; q.part = part;
-    q.feat = feat; q.fst = feat_stride_t; q.fsb = feat_stride_b; q.w = weight;
-    q.T = T; q.B = B; q.K = K; q.C = C; q.CP = L.CP;
-    q.R = T * B; q.S = L.S; q.chunk = L.chunk;
-    q.dw = L.S > 1 ? wpart : d_weight;
-    q.dfeat = d_feat; q.gst = dfeat_stride_t; q.gsb = dfeat_stride_b;
-    q.dbias = d_bias; q.dgamma = d_bn_weight; q.dbeta = d_bn_bias;
-    const int64_t KQ = (K / 16 + 3) / 4;
-    q.nW = (int64_t)(L.CP / 16) * KQ * L.S;
-    q.nF = d_feat ? (((int64_t)q.R + 15) / 16) * KQ : 0;
-    q.nTail = (3 * (int64_t)L.CP + 63) / 64;
-    const int64_t tasks = q.nW + q.nF + q.nTail;
-    rc = ctc::head_bwd_launch_products(feat_dtype, tasks, st, q);
-    if (rc || L.S == 1) return rc;
-    const int64_t n = (int64_t)C * K;
-    return launch<ctc::head_bwd_reduce_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                                               (const float *)wpart, d_weight, n, L.S);
+    auto rows = [](dim3 grid, hipStream_t st, const ctc::HeadBwdRowsParams &r) {
+        return launch<ctc::head_wide_bwd_rows_kernel>(grid, dim3(ctc::head_wide_block(r.B)), 0, st, r);
+    };
+    return ctc::head_backward_enqueue(ctc::kHeadWideMaxBatch, rows, d_out, dout_stride_t, dout_stride_b, feat, feat_dtype,
+                                      feat_stride_t, feat_stride_b, weight, bn_weight, bn_bias, linear_out, save_mean, save_invstd,
+                                      running_mean, running_var, eps, mask, T, B, K, C, d_feat, dfeat_stride_t, dfeat_stride_b,
+                                      d_weight, d_bias, d_bn_weight, d_bn_bias, scratch, scratch_bytes, stream);
 }
 
 extern "C" int ctc_amd_head_backward_wide(const float *d_out, int64_t dout_stride_t, int64_t dout_stride_b,

@@ -1,6 +1,6 @@
 // The recurrence of LSTM_cell beyond the reference's class counts: 1 <= I, H <= kWideMax = 160, which takes
-// the benchmark's C = 158.  Included at the end of producer.hip (sigmoid_f, LstmSeriesParams, LstmSeriesBwdParams, the
-// scratch alignment and the row bound of the head's backward are that file's).
+// the benchmark's C = 158.  Included at the end of producer.hip (sigmoid_f, LstmSeriesParams, LstmSeriesBwdParams and their
+// fillers series_params / series_bwd_params, scratch_base / scratch_up and the row bound of the head's backward are that file's).
 //
 // [W_ih | W_hh] at H = 158 is 800 KB: neither the LDS (160 KiB) nor a workgroup's registers hold it, so the narrow kernels'
 // "gate row in registers for the whole launch" does not carry over.  The weights stay in L2 and are STREAMED every frame;
@@ -40,12 +40,11 @@ inline bool lstm_wide_shape_ok(int T, int B, int I, int H)
 
 inline LstmWideLayout lstm_wide_layout(int T, int B, int I, int H)
 {
-    auto up = [](size_t v) { return (v + kHeadBwdAlign - 1) / kHeadBwdAlign * kHeadBwdAlign; };
     LstmWideLayout L;
     const size_t R = (size_t)T * (size_t)B, G = 4 * (size_t)H;
     L.wt = 0;
-    L.xpre = up(((size_t)I + H) * G * sizeof(float));
-    L.total = L.xpre + up(R * G * sizeof(float));
+    L.xpre = scratch_up(((size_t)I + H) * G * sizeof(float));
+    L.total = L.xpre + scratch_up(R * G * sizeof(float));
     return L;
 }
 
@@ -316,8 +315,7 @@ extern "C" int ctc_amd_lstm_series_wide(const float *x, const float *h0, const f
     if (scratch_bytes < ctc_amd_lstm_series_wide_scratch_bytes(T, B, I, H)) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (!ctc::lstm_wide_shape_ok(T, B, I, H)) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
     const ctc::LstmWideLayout L = ctc::lstm_wide_layout(T, B, I, H);
-    char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(scratch) + ctc::kHeadBwdAlign - 1) /
-                                          ctc::kHeadBwdAlign * ctc::kHeadBwdAlign);
+    char *base = ctc::scratch_base(scratch);
     float *wt = reinterpret_cast<float *>(base + L.wt), *xpre = reinterpret_cast<float *>(base + L.xpre);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int G = 4 * H;
@@ -330,12 +328,8 @@ extern "C" int ctc_amd_lstm_series_wide(const float *x, const float *h0, const f
                                              0, st, xp);
     if (rc) return rc;
     ctc::LstmWideParams q;
-    ctc::LstmSeriesParams &p = q.s;
-    p.x = x; p.h0 = h0; p.c0 = c0; p.w_ih = w_ih; p.w_hh = w_hh; p.b_ih = b_ih; p.b_hh = b_hh;
-    p.T = T; p.B = B; p.I = I; p.H = H;
-    p.series = series; p.series_stride_t = series_stride_t; p.series_stride_b = series_stride_b;
-    p.series_cols = series_cols; p.pad_value = pad_value;
-    p.gates = gates_out; p.cells = cells_out; p.h_out = h_out; p.c_out = c_out;
+    q.s = ctc::series_params(x, h0, c0, w_ih, w_hh, b_ih, b_hh, T, B, I, H, series, series_stride_t, series_stride_b, series_cols,
+                             pad_value, gates_out, cells_out, h_out, c_out);
     q.wht = wt + (size_t)I * G; q.xpre = xpre;
     const size_t smem = ((size_t)ctc::kWideSamples * H + (size_t)ctc::kWideSamples * G) * sizeof(float);
     return launch<ctc::lstm_series_wide_kernel>(dim3((unsigned)((B + ctc::kWideSamples - 1) / ctc::kWideSamples)),
@@ -350,11 +344,8 @@ extern "C" int ctc_amd_lstm_series_backward_wide(const float *d_series, int64_t 
     if (!d_series || !gates || !cells || !w_hh || !dpre_out || !dh0_out || !dc0_out) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (T < 1 || B < 1 || H < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (H > ctc::kWideMax) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
-    ctc::LstmSeriesBwdParams p;
-    p.d_series = d_series; p.ds_stride_t = ds_stride_t; p.ds_stride_b = ds_stride_b;
-    p.gates = gates; p.cells = cells; p.w_hh = w_hh;
-    p.T = T; p.B = B; p.H = H;
-    p.dpre = dpre_out; p.dh0 = dh0_out; p.dc0 = dc0_out;
+    const ctc::LstmSeriesBwdParams p = ctc::series_bwd_params(d_series, ds_stride_t, ds_stride_b, gates, cells, w_hh, T, B, H,
+                                                              dpre_out, dh0_out, dc0_out);
     const int G = 4 * H;
     const size_t smem = ((size_t)ctc::kWideSamples * G + (size_t)ctc::kWideGates * ctc::kWideSamples * H) * sizeof(float);
     return launch<ctc::lstm_series_bwd_wide_kernel>(dim3((unsigned)((B + ctc::kWideSamples - 1) / ctc::kWideSamples)),

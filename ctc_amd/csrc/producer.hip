@@ -114,6 +114,17 @@ struct LstmSeriesParams {
     float *h_out, *c_out;                                    // optional final state [B][H]
 };
 
+// the parameter block of every forward recurrence (narrow, wide, fused), in the order of the entries' argument lists
+inline LstmSeriesParams series_params(const float *x, const float *h0, const float *c0,
+                                      const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,
+                                      int T, int B, int I, int H,
+                                      float *series, int64_t series_stride_t, int64_t series_stride_b, int series_cols, float pad_value,
+                                      float *gates, float *cells, float *h_out, float *c_out)
+{
+    return LstmSeriesParams{x, h0, c0, w_ih, w_hh, b_ih, b_hh, T, B, I, H, series, series_stride_t, series_stride_b,
+                            series_cols, pad_value, gates, cells, h_out, c_out};
+}
+
 // What a thread of the recurrence owns, and where the workgroup's staging lies in LDS (lstm_series_kernel and
 // lstm_forward_kernel: one layout, one prologue, one frame body -- the same fma chains in both, bit for bit).
 struct SeriesLane {
@@ -268,6 +279,14 @@ struct LstmSeriesBwdParams {
     float *dpre, *dh0, *dc0;                                 // [T][B][4H], [B][H], [B][H]
 };
 
+// the parameter block of both backward recurrences (narrow, wide), in the order of the entries' argument lists
+inline LstmSeriesBwdParams series_bwd_params(const float *d_series, int64_t ds_stride_t, int64_t ds_stride_b,
+                                             const float *gates, const float *cells, const float *w_hh,
+                                             int T, int B, int H, float *dpre, float *dh0, float *dc0)
+{
+    return LstmSeriesBwdParams{d_series, ds_stride_t, ds_stride_b, gates, cells, w_hh, T, B, H, dpre, dh0, dc0};
+}
+
 __global__ __launch_bounds__(kLstmThreads) void lstm_series_bwd_kernel(LstmSeriesBwdParams p)
 {
     extern __shared__ float4 bwd_smem[];
@@ -355,12 +374,8 @@ extern "C" int ctc_amd_lstm_series(const float *x, const float *h0, const float 
     if (series_cols < H || series_stride_b < series_cols) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (I + H > kSeriesK || 4 * H > kLstmThreads || kSeriesSamples * I > kLstmThreads || kSeriesSamples * H > kLstmThreads)
         return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
-    LstmSeriesParams p;
-    p.x = x; p.h0 = h0; p.c0 = c0; p.w_ih = w_ih; p.w_hh = w_hh; p.b_ih = b_ih; p.b_hh = b_hh;
-    p.T = T; p.B = B; p.I = I; p.H = H;
-    p.series = series; p.series_stride_t = series_stride_t; p.series_stride_b = series_stride_b;
-    p.series_cols = series_cols; p.pad_value = pad_value;
-    p.gates = gates_out; p.cells = cells_out; p.h_out = h_out; p.c_out = c_out;
+    const LstmSeriesParams p = series_params(x, h0, c0, w_ih, w_hh, b_ih, b_hh, T, B, I, H, series, series_stride_t,
+                                             series_stride_b, series_cols, pad_value, gates_out, cells_out, h_out, c_out);
     const size_t smem = series_smem_floats(I, H) * sizeof(float);
     return launch<lstm_series_kernel>(dim3((B + kSeriesSamples - 1) / kSeriesSamples), dim3(kLstmThreads), smem,
                                       static_cast<hipStream_t>(stream), p);
@@ -390,17 +405,10 @@ extern "C" int ctc_amd_lstm_cell_step(const float *x, const float *h, const floa
 
 // The enqueue of lstm_series_bwd_kernel, shared by ctc_amd_lstm_series_backward and ctc_amd_lstm_backward (the callers have
 // checked the arguments): one launch on `stream`.
-static int enqueue_series_backward(const float *d_series, int64_t ds_stride_t, int64_t ds_stride_b,
-                                   const float *gates, const float *cells, const float *w_hh,
-                                   int T, int B, int H, float *dpre_out, float *dh0_out, float *dc0_out, hipStream_t stream)
+static int enqueue_series_backward(const LstmSeriesBwdParams &p, hipStream_t stream)
 {
-    LstmSeriesBwdParams p;
-    p.d_series = d_series; p.ds_stride_t = ds_stride_t; p.ds_stride_b = ds_stride_b;
-    p.gates = gates; p.cells = cells; p.w_hh = w_hh;
-    p.T = T; p.B = B; p.H = H;
-    p.dpre = dpre_out; p.dh0 = dh0_out; p.dc0 = dc0_out;
-    const size_t smem = (size_t)2 * kSeriesSamples * 4 * H * sizeof(float);
-    return launch<lstm_series_bwd_kernel>(dim3((B + kSeriesSamples - 1) / kSeriesSamples), dim3(kLstmThreads), smem, stream, p);
+    const size_t smem = (size_t)2 * kSeriesSamples * 4 * p.H * sizeof(float);
+    return launch<lstm_series_bwd_kernel>(dim3((p.B + kSeriesSamples - 1) / kSeriesSamples), dim3(kLstmThreads), smem, stream, p);
 }
 
 // The backward recurrence of ctc_amd_lstm_series (same sizes): from the upstream gradient of v_series and the state the
@@ -413,7 +421,8 @@ extern "C" int ctc_amd_lstm_series_backward(const float *d_series, int64_t ds_st
     if (!d_series || !gates || !cells || !w_hh || !dpre_out || !dh0_out || !dc0_out) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (T < 1 || B < 1 || H < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (4 * H > kSeriesG || kSeriesSamples * H > kLstmThreads) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
-    return enqueue_series_backward(d_series, ds_stride_t, ds_stride_b, gates, cells, w_hh, T, B, H, dpre_out, dh0_out, dc0_out,
+    return enqueue_series_backward(series_bwd_params(d_series, ds_stride_t, ds_stride_b, gates, cells, w_hh, T, B, H, dpre_out,
+                                                     dh0_out, dc0_out),
                                    static_cast<hipStream_t>(stream));
 }
 
@@ -430,6 +439,8 @@ extern "C" int ctc_amd_lstm_series_backward(const float *d_series, int64_t ds_st
 // over the T frames, applied by the caller).  Eval mode: the running statistics.  Dropout is a mask tensor the caller
 // hands in (already scaled by 1 / (1 - p)): the random stream stays torch's.
 namespace ctc {
+
+constexpr int kHeadMaxBatch = 256;                           // B beyond this: the wide entries (head_wide.hpp)
 
 struct HeadParams {
     const void *feat;                                        // [T][B][K] of the kernel's element type E (strides in elements)
@@ -470,24 +481,41 @@ __device__ __forceinline__ head_f4 head_feat4(const E *p)
     }
 }
 
-// feat_dtype of the typed entries -> E
-template <typename E> struct HeadElem { using type = E; };
-template <typename F>
-inline int head_with_elem(int feat_dtype, F f)
-{
-    switch (feat_dtype) {
-    case CTC_AMD_F32: return f(HeadElem<float>{});
-    case CTC_AMD_BF16: return f(HeadElem<__bf16>{});
-    case CTC_AMD_F16: return f(HeadElem<_Float16>{});
-    default: return CTC_AMD_ERR_BAD_ARGUMENT;
-    }
-}
+// (feat_dtype of the typed entries -> E: with_logit_elem of launch.hpp)
 
-// what the entries ask of the feature operand: 16-byte loads of fp32 rows, 8-byte loads of 2-byte rows (strides in elements)
-inline bool head_feat_aligned(const void *feat, int feat_dtype, int64_t stride_t, int64_t stride_b)
+// What every head entry, forward and backward, asks of its two matrix-core operands: 16-byte loads of fp32 feature rows, 8-byte
+// loads of 2-byte rows (strides in elements), 16-byte loads of the weight rows, K a multiple of 16.
+inline bool head_operands_ok(const void *feat, int feat_dtype, int64_t stride_t, int64_t stride_b, const float *weight, int K)
 {
     const uintptr_t mask = feat_dtype == CTC_AMD_F32 ? 15 : 7;
-    return (stride_b & 3) == 0 && (stride_t & 3) == 0 && (reinterpret_cast<uintptr_t>(feat) & mask) == 0;
+    return (K & 15) == 0 && (stride_b & 3) == 0 && (stride_t & 3) == 0 && (reinterpret_cast<uintptr_t>(feat) & mask) == 0 &&
+           (reinterpret_cast<uintptr_t>(weight) & 15) == 0;
+}
+
+inline bool head_dtype_ok(int feat_dtype) { return feat_dtype == CTC_AMD_F32 || feat_dtype == CTC_AMD_BF16 || feat_dtype == CTC_AMD_F16; }
+
+// The arguments the three forward entries share (ctc_amd_head_forward_typed, ctc_amd_head_forward_wide_typed,
+// ctc_amd_lstm_forward_typed) -> CTC_AMD_ERR_BAD_ARGUMENT, or `p` filled and the operands' answer: 0 or
+// CTC_AMD_ERR_UNSUPPORTED_SHAPE.  A bad argument wins over the shape, so the caller runs its own argument checks before it acts on
+// the second answer, and adds what is its own to the shape: the bound on B, the scratch, the recurrence's sizes.
+inline int head_forward_params(HeadParams &p, const void *feat, int feat_dtype, int64_t feat_stride_t, int64_t feat_stride_b,
+                               const float *weight, const float *bias, const float *bn_weight, const float *bn_bias,
+                               const float *running_mean, const float *running_var, float eps, const float *mask,
+                               int T, int B, int K, int C, float *out, int64_t out_stride_t, int64_t out_stride_b,
+                               float *linear_out, float *save_mean, float *save_var, float *save_invstd)
+{
+    if (!head_dtype_ok(feat_dtype)) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (!feat || !weight || !bias || !bn_weight || !bn_bias || !out) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (T < 1 || B < 1 || K < 1 || C < 1 || (running_mean == nullptr) != (running_var == nullptr)) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (out_stride_b < C) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (running_mean == nullptr && B < 2) return CTC_AMD_ERR_BAD_ARGUMENT;       // (torch raises too: one value per channel)
+    p.feat = feat; p.fst = feat_stride_t; p.fsb = feat_stride_b;
+    p.w = weight; p.bias = bias; p.gamma = bn_weight; p.beta = bn_bias;
+    p.rmean = running_mean; p.rvar = running_var; p.mask = mask; p.eps = eps;
+    p.T = T; p.B = B; p.K = K; p.C = C;
+    p.out = out; p.ost = out_stride_t; p.osb = out_stride_b;
+    p.lin = linear_out; p.smean = save_mean; p.svar = save_var; p.sinv = save_invstd;
+    return head_operands_ok(feat, feat_dtype, feat_stride_t, feat_stride_b, weight, K) ? 0 : CTC_AMD_ERR_UNSUPPORTED_SHAPE;
 }
 
 // The Linear product of one tile of 16 rows with N tiles of 16 columns (head_kernel: N = 1; lstm_forward_kernel: every
@@ -621,27 +649,16 @@ extern "C" int ctc_amd_head_forward_typed(const void *feat, int feat_dtype, int6
                                           float *out, int64_t out_stride_t, int64_t out_stride_b,
                                           float *linear_out, float *save_mean, float *save_var, float *save_invstd, void *stream)
 {
-    if (feat_dtype != CTC_AMD_F32 && feat_dtype != CTC_AMD_BF16 && feat_dtype != CTC_AMD_F16) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (!feat || !weight || !bias || !bn_weight || !bn_bias || !out) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (T < 1 || B < 1 || K < 1 || C < 1 || (running_mean == nullptr) != (running_var == nullptr)) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (out_stride_b < C) return CTC_AMD_ERR_BAD_ARGUMENT;
-    // one workgroup holds the B rows of a frame (BatchNorm's statistics); 16-byte operand loads (8-byte: a 2-byte feat)
-    if (B > 256 || (K & 15) != 0 || !ctc::head_feat_aligned(feat, feat_dtype, feat_stride_t, feat_stride_b) ||
-        (reinterpret_cast<uintptr_t>(weight) & 15) != 0)
-        return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
-    if (running_mean == nullptr && B < 2) return CTC_AMD_ERR_BAD_ARGUMENT;       // (torch raises too: one value per channel)
     ctc::HeadParams p;
-    p.feat = feat; p.fst = feat_stride_t; p.fsb = feat_stride_b;
-    p.w = weight; p.bias = bias; p.gamma = bn_weight; p.beta = bn_bias;
-    p.rmean = running_mean; p.rvar = running_var; p.mask = mask; p.eps = eps;
-    p.T = T; p.B = B; p.K = K; p.C = C;
-    p.out = out; p.ost = out_stride_t; p.osb = out_stride_b;
-    p.lin = linear_out; p.smean = save_mean; p.svar = save_var; p.sinv = save_invstd;
-    const int NW = (B + 15) / 16;
-    return ctc::head_with_elem(feat_dtype, [&](auto e) {
+    const int rc = ctc::head_forward_params(p, feat, feat_dtype, feat_stride_t, feat_stride_b, weight, bias, bn_weight, bn_bias,
+                                            running_mean, running_var, eps, mask, T, B, K, C, out, out_stride_t, out_stride_b,
+                                            linear_out, save_mean, save_var, save_invstd);
+    if (rc == CTC_AMD_ERR_BAD_ARGUMENT) return rc;
+    // one workgroup holds the B rows of a frame (BatchNorm's statistics)
+    if (rc || B > ctc::kHeadMaxBatch) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
+    return ctc::with_logit_elem(feat_dtype, [&](auto e) {
         using E = typename decltype(e)::type;
-        hipLaunchKernelGGL(ctc::head_kernel<E>, dim3(T, (C + 15) / 16), dim3(64 * NW), 0, static_cast<hipStream_t>(stream), p);
-        return (int)hipGetLastError();
+        return launch<ctc::head_kernel<E>>(dim3(T, (C + 15) / 16), dim3(64 * ((B + 15) / 16)), 0, static_cast<hipStream_t>(stream), p);
     });
 }
 
@@ -752,29 +769,22 @@ extern "C" int ctc_amd_lstm_forward_typed(const void *feat, int feat_dtype, int6
                                           float *series, int64_t series_stride_t, int64_t series_stride_b, int series_cols,
                                           float pad_value, float *h_out, float *c_out, void *stream)
 {
-    if (feat_dtype != CTC_AMD_F32 && feat_dtype != CTC_AMD_BF16 && feat_dtype != CTC_AMD_F16) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (!feat || !weight || !bias || !bn_weight || !bn_bias || !running_mean || !running_var) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (!h0 || !c0 || !w_ih || !w_hh || !b_ih || !b_hh || !series) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (T < 1 || B < 1 || K < 1 || C < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
+    ctc::LstmForwardParams q{};
+    // the head of the launch: no mask, nothing saved, and its "out" is the LDS slice -- the series stands in for the checks
+    const int rc = ctc::head_forward_params(q.h, feat, feat_dtype, feat_stride_t, feat_stride_b, weight, bias, bn_weight, bn_bias,
+                                            running_mean, running_var, eps, nullptr, T, B, K, C, series, series_stride_t,
+                                            series_stride_b, nullptr, nullptr, nullptr, nullptr);
+    if (rc == CTC_AMD_ERR_BAD_ARGUMENT) return rc;
+    if (!running_mean || !h0 || !c0 || !w_ih || !w_hh || !b_ih || !b_hh) return CTC_AMD_ERR_BAD_ARGUMENT;        // eval mode only
     if (series_cols < C || series_stride_b < series_cols) return CTC_AMD_ERR_BAD_ARGUMENT;
-    // the recurrence's sizes (I = H = C) and the head's 16-byte operand loads (8-byte: a 2-byte feat)
-    if (2 * C > kSeriesK || 4 * C > kLstmThreads || (K & 15) != 0 ||
-        !ctc::head_feat_aligned(feat, feat_dtype, feat_stride_t, feat_stride_b) || (reinterpret_cast<uintptr_t>(weight) & 15) != 0)
-        return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
+    // the recurrence's sizes (I = H = C)
+    if (rc || 2 * C > kSeriesK || 4 * C > kLstmThreads) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
     // the workgroup's slice of the head's output, [T][4][C], next to the recurrence's staging
     const size_t smem = (series_smem_floats(C, C) + (size_t)kSeriesSamples * (size_t)T * (size_t)C) * sizeof(float);
     if (smem > kMaxLds) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
-    ctc::LstmForwardParams q{};
-    q.h.feat = feat; q.h.fst = feat_stride_t; q.h.fsb = feat_stride_b;
-    q.h.w = weight; q.h.bias = bias; q.h.gamma = bn_weight; q.h.beta = bn_bias;
-    q.h.rmean = running_mean; q.h.rvar = running_var; q.h.eps = eps;
-    q.h.T = T; q.h.B = B; q.h.K = K; q.h.C = C;
-    q.s.h0 = h0; q.s.c0 = c0; q.s.w_ih = w_ih; q.s.w_hh = w_hh; q.s.b_ih = b_ih; q.s.b_hh = b_hh;
-    q.s.T = T; q.s.B = B; q.s.I = C; q.s.H = C;
-    q.s.series = series; q.s.series_stride_t = series_stride_t; q.s.series_stride_b = series_stride_b;
-    q.s.series_cols = series_cols; q.s.pad_value = pad_value;
-    q.s.h_out = h_out; q.s.c_out = c_out;
-    return ctc::head_with_elem(feat_dtype, [&](auto e) {
+    q.s = ctc::series_params(nullptr, h0, c0, w_ih, w_hh, b_ih, b_hh, T, B, C, C, series, series_stride_t, series_stride_b,
+                             series_cols, pad_value, nullptr, nullptr, h_out, c_out);
+    return ctc::with_logit_elem(feat_dtype, [&](auto e) {
         using E = typename decltype(e)::type;
         return launch<lstm_forward_kernel<E>>(dim3((B + kSeriesSamples - 1) / kSeriesSamples), dim3(kLstmThreads), smem,
                                               static_cast<hipStream_t>(stream), q);
@@ -832,9 +842,17 @@ struct HeadBwdLayout {                                       // byte offsets int
     int CP, S, chunk;
 };
 
-inline bool head_bwd_shape_ok(int T, int B, int K, int C)
+// The scratch of every producer entry that takes one: the pieces start on kHeadBwdAlign boundaries of the pointer rounded up (so
+// a query answers its layout's total + kHeadBwdAlign).
+inline size_t scratch_up(size_t v) { return (v + kHeadBwdAlign - 1) / kHeadBwdAlign * kHeadBwdAlign; }
+inline char *scratch_base(void *scratch) { return reinterpret_cast<char *>(scratch_up(reinterpret_cast<uintptr_t>(scratch))); }
+
+// What the head's backward entries, the wide forward entry and their scratch queries take of (T, B, K, C): B up to `max_batch`
+// (kHeadMaxBatch: a frame in one workgroup; kHeadWideMaxBatch: head_wide.hpp), K a multiple of 16, row and task counts inside
+// the launches' index range.
+inline bool head_shape_ok(int T, int B, int K, int C, int max_batch)
 {
-    if (B > 256 || (K & 15) != 0) return false;
+    if (B > max_batch || (K & 15) != 0) return false;
     const int64_t R = (int64_t)T * B;
     if (R > kHeadBwdMaxRows) return false;
     int S, chunk;
@@ -846,16 +864,22 @@ inline bool head_bwd_shape_ok(int T, int B, int K, int C)
 
 inline HeadBwdLayout head_bwd_layout(int T, int B, int K, int C)
 {
-    auto up = [](size_t v) { return (v + kHeadBwdAlign - 1) / kHeadBwdAlign * kHeadBwdAlign; };
     HeadBwdLayout L;
     const size_t R = (size_t)T * (size_t)B;
     L.CP = 16 * ((C + 15) / 16);
     head_bwd_splits((int64_t)R, L.S, L.chunk);
     L.dlin = 0;
-    L.part = up(R * L.CP * sizeof(float));
-    L.wpart = L.part + up((size_t)3 * T * L.CP * sizeof(float));
-    L.total = L.wpart + (L.S > 1 ? up((size_t)L.S * C * K * sizeof(float)) : 0);
+    L.part = scratch_up(R * L.CP * sizeof(float));
+    L.wpart = L.part + scratch_up((size_t)3 * T * L.CP * sizeof(float));
+    L.total = L.wpart + (L.S > 1 ? scratch_up((size_t)L.S * C * K * sizeof(float)) : 0);
     return L;
+}
+
+// the answer of both scratch queries of the head's backward (0: the shape is not one the entry takes)
+inline size_t head_bwd_scratch_bytes(int T, int B, int K, int C, int max_batch)
+{
+    if (T < 1 || B < 1 || K < 1 || C < 1 || !head_shape_ok(T, B, K, C, max_batch)) return 0;
+    return head_bwd_layout(T, B, K, C).total + kHeadBwdAlign;
 }
 
 struct HeadBwdRowsParams {
@@ -1072,30 +1096,82 @@ __global__ __launch_bounds__(256) void head_bwd_reduce_kernel(const float *wpart
 
 }  // namespace ctc
 
-extern "C" size_t ctc_amd_head_backward_scratch_bytes(int T, int B, int K, int C)
-{
-    if (T < 1 || B < 1 || K < 1 || C < 1 || !ctc::head_bwd_shape_ok(T, B, K, C)) return 0;
-    return ctc::head_bwd_layout(T, B, K, C).total + ctc::kHeadBwdAlign;           // (the entry aligns the pointer itself)
-}
-
 namespace ctc {
 
-// d_feat of a 2-byte element type: 2-byte aligned (written with 2-byte stores); fp32 as the untyped entries take it
-inline bool head_dfeat_aligned(const void *d_feat, int feat_dtype)
+// The backward of the head behind both *_typed entries (the untyped ones forward to those with CTC_AMD_F32): the checks, the
+// scratch carve-up, both parameter blocks, the task count and the products and reduce launches.  What differs comes from the
+// caller: the bound on B and the rows launch, rows(grid, stream, r) -- head_bwd_rows_kernel with a frame in one workgroup or
+// head_wide_bwd_rows_kernel walking the frame's row blocks.
+template <typename Rows>
+inline int head_backward_enqueue(int max_batch, Rows rows, const float *d_out, int64_t dout_stride_t, int64_t dout_stride_b,
+                                 const void *feat, int feat_dtype, int64_t feat_stride_t, int64_t feat_stride_b,
+                                 const float *weight, const float *bn_weight, const float *bn_bias, const float *linear_out,
+                                 const float *save_mean, const float *save_invstd,
+                                 const float *running_mean, const float *running_var, float eps, const float *mask,
+                                 int T, int B, int K, int C, void *d_feat, int64_t dfeat_stride_t, int64_t dfeat_stride_b,
+                                 float *d_weight, float *d_bias, float *d_bn_weight, float *d_bn_bias,
+                                 void *scratch, size_t scratch_bytes, void *stream)
 {
-    return feat_dtype == CTC_AMD_F32 || (reinterpret_cast<uintptr_t>(d_feat) & 1) == 0;
-}
+    if (!head_dtype_ok(feat_dtype)) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (!d_out || !feat || !weight || !bn_weight || !bn_bias || !linear_out) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (!d_weight || !d_bias || !d_bn_weight || !d_bn_bias || !scratch) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (T < 1 || B < 1 || K < 1 || C < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
+    const bool train = save_mean && save_invstd && !running_mean && !running_var;
+    const bool eval = running_mean && running_var && !save_mean && !save_invstd;
+    if (!train && !eval) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (train && B < 2) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (dout_stride_b < C) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (d_feat && dfeat_stride_b < K) return CTC_AMD_ERR_BAD_ARGUMENT;
+    if (scratch_bytes < head_bwd_scratch_bytes(T, B, K, C, max_batch)) return CTC_AMD_ERR_BAD_ARGUMENT;
+    // what the forward entry refuses, row counts beyond the launches' index range, and d_feat of a 2-byte element type off its
+    // 2-byte boundary (written with 2-byte stores; fp32 as the untyped entries take it)
+    if (!head_shape_ok(T, B, K, C, max_batch) || !head_operands_ok(feat, feat_dtype, feat_stride_t, feat_stride_b, weight, K) ||
+        (d_feat && feat_dtype != CTC_AMD_F32 && (reinterpret_cast<uintptr_t>(d_feat) & 1) != 0))
+        return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
+    const HeadBwdLayout L = head_bwd_layout(T, B, K, C);
+    char *base = scratch_base(scratch);
+    float *dlin = reinterpret_cast<float *>(base + L.dlin), *part = reinterpret_cast<float *>(base + L.part);
+    float *wpart = reinterpret_cast<float *>(base + L.wpart);
+    hipStream_t st = static_cast<hipStream_t>(stream);
 
-// the products launch of the head's backward on the element type of feat and d_feat
-inline int head_bwd_launch_products(int feat_dtype, int64_t tasks, hipStream_t st, const HeadBwdProdParams &q)
-{
-    return head_with_elem(feat_dtype, [&](auto e) {
+    HeadBwdRowsParams r;
+    r.dout = d_out; r.dst = dout_stride_t; r.dsb = dout_stride_b;
+    r.lin = linear_out; r.gamma = bn_weight; r.beta = bn_bias;
+    r.smean = save_mean; r.sinv = save_invstd; r.rmean = running_mean; r.rvar = running_var;
+    r.mask = mask; r.eps = eps;
+    r.T = T; r.B = B; r.C = C; r.CP = L.CP;
+    r.dlin = dlin; r.part = part;
+    int rc = rows(dim3(T, L.CP / 16), st, r);
+    if (rc) return rc;
+
+    HeadBwdProdParams q;
+    q.dlin = dlin; q.part = part;
+    q.feat = feat; q.fst = feat_stride_t; q.fsb = feat_stride_b; q.w = weight;
+    q.T = T; q.B = B; q.K = K; q.C = C; q.CP = L.CP;
+    q.R = T * B; q.S = L.S; q.chunk = L.chunk;
+    q.dw = L.S > 1 ? wpart : d_weight;
+    q.dfeat = d_feat; q.gst = dfeat_stride_t; q.gsb = dfeat_stride_b;
+    q.dbias = d_bias; q.dgamma = d_bn_weight; q.dbeta = d_bn_bias;
+    const int64_t KQ = (K / 16 + 3) / 4;
+    q.nW = (int64_t)(L.CP / 16) * KQ * L.S;
+    q.nF = d_feat ? (((int64_t)q.R + 15) / 16) * KQ : 0;
+    q.nTail = (3 * (int64_t)L.CP + 63) / 64;
+    const int64_t tasks = q.nW + q.nF + q.nTail;
+    rc = with_logit_elem(feat_dtype, [&](auto e) {          // the element type of feat and d_feat
         using E = typename decltype(e)::type;
         return launch<head_bwd_products_kernel<E>>(dim3((unsigned)((tasks + 3) / 4)), dim3(256), 0, st, q);
     });
+    if (rc || L.S == 1) return rc;
+    const int64_t n = (int64_t)C * K;
+    return launch<head_bwd_reduce_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float *)wpart, d_weight, n, L.S);
 }
 
 }  // namespace ctc
+
+extern "C" size_t ctc_amd_head_backward_scratch_bytes(int T, int B, int K, int C)
+{
+    return ctc::head_bwd_scratch_bytes(T, B, K, C, ctc::kHeadMaxBatch);
+}
 
 extern "C" int ctc_amd_head_backward_typed(const float *d_out, int64_t dout_stride_t, int64_t dout_stride_b,
                                            const void *feat, int feat_dtype, int64_t feat_stride_t, int64_t feat_stride_b,
@@ -1109,56 +1185,13 @@ extern "C" int ctc_amd_head_backward_typed(const float *d_out, int64_t dout_stri
                                            float *d_weight, float *d_bias, float *d_bn_weight, float *d_bn_bias,
                                            void *scratch, size_t scratch_bytes, void *stream)
 {
-    if (feat_dtype != CTC_AMD_F32 && feat_dtype != CTC_AMD_BF16 && feat_dtype != CTC_AMD_F16) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (!d_out || !feat || !weight || !bn_weight || !bn_bias || !linear_out) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (!d_weight || !d_bias || !d_bn_weight || !d_bn_bias || !scratch) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (T < 1 || B < 1 || K < 1 || C < 1) return CTC_AMD_ERR_BAD_ARGUMENT;
-    const bool train = save_mean && save_invstd && !running_mean && !running_var;
-    const bool eval = running_mean && running_var && !save_mean && !save_invstd;
-    if (!train && !eval) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (train && B < 2) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (dout_stride_b < C) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (d_feat && dfeat_stride_b < K) return CTC_AMD_ERR_BAD_ARGUMENT;
-    if (scratch_bytes < ctc_amd_head_backward_scratch_bytes(T, B, K, C)) return CTC_AMD_ERR_BAD_ARGUMENT;
-    // what ctc_amd_head_forward(_typed) refuses, and row counts beyond the launches' index range
-    if (!ctc::head_bwd_shape_ok(T, B, K, C) || !ctc::head_feat_aligned(feat, feat_dtype, feat_stride_t, feat_stride_b) ||
-        (reinterpret_cast<uintptr_t>(weight) & 15) != 0 || (d_feat && !ctc::head_dfeat_aligned(d_feat, feat_dtype)))
-        return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
-    const ctc::HeadBwdLayout L = ctc::head_bwd_layout(T, B, K, C);
-    char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(scratch) + ctc::kHeadBwdAlign - 1) /
-                                          ctc::kHeadBwdAlign * ctc::kHeadBwdAlign);
-    float *dlin = reinterpret_cast<float *>(base + L.dlin), *part = reinterpret_cast<float *>(base + L.part);
-    float *wpart = reinterpret_cast<float *>(base + L.wpart);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-
-    ctc::HeadBwdRowsParams r;
-    r.dout = d_out; r.dst = dout_stride_t; r.dsb = dout_stride_b;
-    r.lin = linear_out; r.gamma = bn_weight; r.beta = bn_bias;
-    r.smean = save_mean; r.sinv = save_invstd; r.rmean = running_mean; r.rvar = running_var;
-    r.mask = mask; r.eps = eps;
-    r.T = T; r.B = B; r.C = C; r.CP = L.CP;
-    r.dlin = dlin; r.part = part;
-    int rc = launch<ctc::head_bwd_rows_kernel>(dim3(T, L.CP / 16), dim3(64 * ((B + 15) / 16)), 0, st, r);
-    if (rc) return rc;
-
-    ctc::HeadBwdProdParams q;
-    q.dlin = dlin; q.part = part;
-    q.feat = feat; q.fst = feat_stride_t; q.fsb = feat_stride_b; q.w = weight;
-    q.T = T; q.B = B; q.K = K; q.C = C; q.CP = L.CP;
-    q.R = T * B; q.S = L.S; q.chunk = L.chunk;
-    q.dw = L.S > 1 ? wpart : d_weight;
-    q.dfeat = d_feat; q.gst = dfeat_stride_t; q.gsb = dfeat_stride_b;
-    q.dbias = d_bias; q.dgamma = d_bn_weight; q.dbeta = d_bn_bias;
-    const int64_t KQ = (K / 16 + 3) / 4;
-    q.nW = (int64_t)(L.CP / 16) * KQ * L.S;
-    q.nF = d_feat ? (((int64_t)q.R + 15) / 16) * KQ : 0;
-    q.nTail = (3 * (int64_t)L.CP + 63) / 64;
-    const int64_t tasks = q.nW + q.nF + q.nTail;
-    rc = ctc::head_bwd_launch_products(feat_dtype, tasks, st, q);
-    if (rc || L.S == 1) return rc;
-    const int64_t n = (int64_t)C * K;
-    return launch<ctc::head_bwd_reduce_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                                               (const float *)wpart, d_weight, n, L.S);
+    auto rows = [](dim3 grid, hipStream_t st, const ctc::HeadBwdRowsParams &r) {
+        return launch<ctc::head_bwd_rows_kernel>(grid, dim3(64 * ((r.B + 15) / 16)), 0, st, r);
+    };
+    return ctc::head_backward_enqueue(ctc::kHeadMaxBatch, rows, d_out, dout_stride_t, dout_stride_b, feat, feat_dtype,
+                                      feat_stride_t, feat_stride_b, weight, bn_weight, bn_bias, linear_out, save_mean, save_invstd,
+                                      running_mean, running_var, eps, mask, T, B, K, C, d_feat, dfeat_stride_t, dfeat_stride_b,
+                                      d_weight, d_bias, d_bn_weight, d_bn_bias, scratch, scratch_bytes, stream);
 }
 
 extern "C" int ctc_amd_head_backward(const float *d_out, int64_t dout_stride_t, int64_t dout_stride_b,
@@ -1209,14 +1242,13 @@ inline bool lstm_bwd_shape_ok(int T, int B, int I, int H)
 
 inline LstmBwdLayout lstm_bwd_layout(int T, int B, int I, int H)
 {
-    auto up = [](size_t v) { return (v + kHeadBwdAlign - 1) / kHeadBwdAlign * kHeadBwdAlign; };
     LstmBwdLayout L;
     const size_t R = (size_t)T * (size_t)B;
     head_bwd_splits((int64_t)R, L.S, L.chunk);
     L.ntot = (int64_t)4 * H * (I + H + 1);
     L.dpre = 0;
-    L.wpart = up(R * 4 * H * sizeof(float));
-    L.total = L.wpart + (L.S > 1 ? up((size_t)L.S * (size_t)L.ntot * sizeof(float)) : 0);
+    L.wpart = scratch_up(R * 4 * H * sizeof(float));
+    L.total = L.wpart + (L.S > 1 ? scratch_up((size_t)L.S * (size_t)L.ntot * sizeof(float)) : 0);
     return L;
 }
 
@@ -1414,12 +1446,11 @@ extern "C" int ctc_amd_lstm_backward(const float *d_series, int64_t ds_stride_t,
     // what ctc_amd_lstm_series refuses (the saved gates and cells can only come from it), and row counts beyond the index range
     if (!ctc::lstm_bwd_shape_ok(T, B, I, H)) return CTC_AMD_ERR_UNSUPPORTED_SHAPE;
     const ctc::LstmBwdLayout L = ctc::lstm_bwd_layout(T, B, I, H);
-    char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(scratch) + ctc::kHeadBwdAlign - 1) /
-                                          ctc::kHeadBwdAlign * ctc::kHeadBwdAlign);
+    char *base = ctc::scratch_base(scratch);
     float *dpre = reinterpret_cast<float *>(base + L.dpre), *wpart = reinterpret_cast<float *>(base + L.wpart);
     hipStream_t st = static_cast<hipStream_t>(stream);
 
-    int rc = enqueue_series_backward(d_series, ds_stride_t, ds_stride_b, gates, cells, w_hh, T, B, H, dpre, dh0, dc0, st);
+    int rc = enqueue_series_backward(series_bwd_params(d_series, ds_stride_t, ds_stride_b, gates, cells, w_hh, T, B, H, dpre, dh0, dc0), st);
     if (rc) return rc;
 
     const int G = 4 * H;

@@ -69,6 +69,41 @@ class BasicModule(nn.Module):
 _LOWP_FEAT = {torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
 
 
+def _f32c(t):
+    """``t`` itself when it is fp32 and contiguous, else cast and copied"""
+    return t if (t.dtype is torch.float32 and t.is_contiguous()) else t.float().contiguous()
+
+
+def _rows(t, pitch=False):
+    """``t`` [T,B,n] itself when the entry can address its rows -- fp32, unit stride over the last dimension and, with ``pitch``,
+    a row pitch of at least the width -- else cast and copied"""
+    ok = t.dtype is torch.float32 and t.stride(2) == 1 and (not pitch or t.stride(1) >= t.shape[2])
+    return t if ok else t.float().contiguous()
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _answer(rc, name, refusal_is_none=True):
+    """what an entry's return code means to the caller: True, False for UNSUPPORTED_SHAPE (the public functions return None
+    then), ``CtcAmdError`` for everything else"""
+    if rc == _lib.ERR_UNSUPPORTED_SHAPE and refusal_is_none:
+        return False
+    if rc:
+        _lib.check(rc, name)
+    return True
+
+
+def _scratch(query, dev, *shape):
+    """the scratch of one call, (buffer, bytes) as ``query`` sizes it, or None when the entry does not take the shape (the
+    query answers 0 for positive sizes).  One ``torch.empty`` per call: ``head_backward`` says why."""
+    nbytes = getattr(_lib.load(), query)(*shape)
+    if nbytes == 0 and min(shape) >= 1:
+        return None
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev), nbytes
+
+
 def _feat_call(name, feat, pre, post):
     """One head entry on ``feat`` [T,B,K] -> (return code, whether the typed entry ran).  ``pre`` / ``post``: the arguments in
     front of and behind (feat, its strides); ``post`` is a function of that flag (the backward entries write d_feat in feat's
@@ -83,7 +118,7 @@ def _feat_call(name, feat, pre, post):
         rc = getattr(lib, name + "_typed")(*pre, feat.data_ptr(), code, feat.stride(0), feat.stride(1), *post(True))
         if rc != _lib.ERR_UNSUPPORTED_SHAPE:
             return rc, True
-    f = feat if (feat.dtype is torch.float32 and feat.stride(2) == 1) else feat.float().contiguous()
+    f = _rows(feat)
     return getattr(lib, name)(*pre, f.data_ptr(), f.stride(0), f.stride(1), *post(False)), False
 
 
@@ -95,6 +130,67 @@ def _dfeat_as(d_feat, feat):
     return d_feat.to(feat.dtype)
 
 
+def _head_forward(name, query, feat, weight, bias, bn_weight, bn_bias, running_mean, running_var, eps, mask, want_backward_state):
+    """``head_forward`` (``query`` None) and ``head_forward_wide`` (``query``: the entry's scratch query): the entry ``name``"""
+    F._require_hip(feat, "feat")
+    T, B, K = feat.shape
+    C = weight.shape[0]
+    dev = feat.device
+    prm = [_f32c(t) for t in (weight, bias, bn_weight, bn_bias)]
+    rm = rv = None
+    if running_mean is not None:
+        rm, rv = _f32c(running_mean), _f32c(running_var)
+    mk = None if mask is None else _f32c(mask)
+    tail = ()                                                # (scratch, scratch_bytes) of the wide entry
+    if query is not None:
+        scratch = _scratch(query, dev, T, B, K, C)
+        if scratch is None:
+            return None
+        tail = (scratch[0].data_ptr(), scratch[1])
+    f32 = torch.float32
+    out = torch.empty((T, B, C), dtype=f32, device=dev)
+    train = rm is None
+    lin = torch.empty((T, B, C), dtype=f32, device=dev) if want_backward_state else None
+    mean = torch.empty((T, C), dtype=f32, device=dev) if train else None
+    var = torch.empty((T, C), dtype=f32, device=dev) if train else None
+    inv = torch.empty((T, C), dtype=f32, device=dev) if train else None
+    with F._on_device(dev):
+        rc, _ = _feat_call(name, feat, (), lambda typed: (
+            *(t.data_ptr() for t in prm), _ptr(rm), _ptr(rv), float(eps), _ptr(mk), T, B, K, C, out.data_ptr(), out.stride(0),
+            out.stride(1), _ptr(lin), _ptr(mean), _ptr(var), _ptr(inv), *tail, F._stream_handle(dev)))
+    return (out, lin, mean, var, inv) if _answer(rc, name) else None
+
+
+def _head_backward(name, d_out, feat, weight, bn_weight, bn_bias, lin, mean, invstd, running_mean, running_var, eps, mask,
+                   need_dfeat):
+    """``head_backward`` and ``head_backward_wide``: the entry ``name`` behind its scratch query"""
+    F._require_hip(d_out, "d_out")
+    F._require_hip(feat, "feat")
+    T, B, K = feat.shape
+    C = weight.shape[0]
+    dev = feat.device
+    f32 = torch.float32
+    do = _rows(d_out)
+    w, g, be, ln, mn, iv, rm, rv, mk = (None if t is None else _f32c(t) for t in (weight, bn_weight, bn_bias, lin, mean, invstd,
+                                                                                  running_mean, running_var, mask))
+    scratch = _scratch(name + "_scratch_bytes", dev, T, B, K, C)
+    if scratch is None:
+        return None
+    d_weight = torch.empty((C, K), dtype=f32, device=dev)
+    d_bias, d_gamma, d_beta = (torch.empty(C, dtype=f32, device=dev) for _ in range(3))
+    d_feat = [None]
+
+    def behind_feat(typed):                                  # d_feat: feat's element type from the typed entry, fp32 from the other
+        if need_dfeat:
+            d_feat[0] = torch.empty((T, B, K), dtype=feat.dtype if typed else f32, device=dev)
+        return (w.data_ptr(), g.data_ptr(), be.data_ptr(), ln.data_ptr(), _ptr(mn), _ptr(iv), _ptr(rm), _ptr(rv), float(eps),
+                _ptr(mk), T, B, K, C, _ptr(d_feat[0]), B * K if need_dfeat else 0, K if need_dfeat else 0, d_weight.data_ptr(),
+                d_bias.data_ptr(), d_gamma.data_ptr(), d_beta.data_ptr(), scratch[0].data_ptr(), scratch[1], F._stream_handle(dev))
+    with F._on_device(dev):
+        rc, _ = _feat_call(name, feat, (do.data_ptr(), do.stride(0), do.stride(1)), behind_feat)
+    return (_dfeat_as(d_feat[0], feat), d_weight, d_bias, d_gamma, d_beta) if _answer(rc, name) else None
+
+
 def head_forward(feat, weight, bias, bn_weight, bn_bias, running_mean=None, running_var=None, eps=1e-5, mask=None,
                  want_backward_state=False):
     """``dropout(relu(batchnorm(feat[t] @ weight.T + bias)))`` for every frame t in ONE launch (``ctc_amd_head_forward``)
@@ -103,32 +199,8 @@ def head_forward(feat, weight, bias, bn_weight, bn_bias, running_mean=None, runn
     both None: the statistics of each frame's batch.  ``mask``: [T,B,C], already scaled by 1 / (1 - p).  A bf16 / fp16 ``feat``
     is read as it lies (``ctc_amd_head_forward_typed``, see ``_feat_call``): every result is fp32 and bit for bit that of
     ``feat.float()``."""
-    F._require_hip(feat, "feat")
-    T, B, K = feat.shape
-    C = weight.shape[0]
-    dev = feat.device
-    prm = [t if (t.dtype is torch.float32 and t.is_contiguous()) else t.float().contiguous()
-           for t in (weight, bias, bn_weight, bn_bias)]
-    rm = rv = None
-    if running_mean is not None:
-        rm, rv = running_mean.float().contiguous(), running_var.float().contiguous()
-    mk = None if mask is None else (mask if (mask.dtype is torch.float32 and mask.is_contiguous()) else mask.float().contiguous())
-    out = torch.empty((T, B, C), dtype=torch.float32, device=dev)
-    train = rm is None
-    lin = torch.empty((T, B, C), dtype=torch.float32, device=dev) if want_backward_state else None
-    mean = torch.empty((T, C), dtype=torch.float32, device=dev) if train else None
-    var = torch.empty((T, C), dtype=torch.float32, device=dev) if train else None
-    inv = torch.empty((T, C), dtype=torch.float32, device=dev) if train else None
-    ptr = lambda t: None if t is None else t.data_ptr()
-    with F._on_device(dev):
-        rc, _ = _feat_call("ctc_amd_head_forward", feat, (), lambda typed: (
-            *(t.data_ptr() for t in prm), ptr(rm), ptr(rv), float(eps), ptr(mk), T, B, K, C, out.data_ptr(), out.stride(0),
-            out.stride(1), ptr(lin), ptr(mean), ptr(var), ptr(inv), F._stream_handle(dev)))
-    if rc == _lib.ERR_UNSUPPORTED_SHAPE:
-        return None
-    if rc:
-        _lib.check(rc, "ctc_amd_head_forward")
-    return out, lin, mean, var, inv
+    return _head_forward("ctc_amd_head_forward", None, feat, weight, bias, bn_weight, bn_bias, running_mean, running_var, eps,
+                         mask, want_backward_state)
 
 
 def head_backward(d_out, feat, weight, bn_weight, bn_bias, lin, mean=None, invstd=None, running_mean=None, running_var=None,
@@ -147,39 +219,8 @@ def head_backward(d_out, feat, weight, bn_weight, bn_bias, lin, mean=None, invst
     per call, not a cached buffer: torch's caching allocator hands the same block back without a device call once the shape has
     been seen, the stream ordering of the block is torch's own business that way, and under ``torch.cuda.graph`` capture the
     block comes from the graph's private pool, which a buffer cached outside the capture could not promise."""
-    F._require_hip(d_out, "d_out")
-    F._require_hip(feat, "feat")
-    T, B, K = feat.shape
-    C = weight.shape[0]
-    dev = feat.device
-    f32 = torch.float32
-    do = d_out if (d_out.dtype is f32 and d_out.stride(2) == 1) else d_out.float().contiguous()
-    cont = lambda t: None if t is None else (t if (t.dtype is f32 and t.is_contiguous()) else t.float().contiguous())   # noqa: E731
-    w, g, be, ln, mn, iv, rm, rv, mk = (cont(t) for t in (weight, bn_weight, bn_bias, lin, mean, invstd, running_mean,
-                                                           running_var, mask))
-    lib = _lib.load()
-    nbytes = lib.ctc_amd_head_backward_scratch_bytes(T, B, K, C)
-    if nbytes == 0 and min(T, B, K, C) >= 1:
-        return None
-    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    d_weight = torch.empty((C, K), dtype=f32, device=dev)
-    d_bias, d_gamma, d_beta = (torch.empty(C, dtype=f32, device=dev) for _ in range(3))
-    ptr = lambda t: None if t is None else t.data_ptr()     # noqa: E731
-    d_feat = [None]
-
-    def behind_feat(typed):                                  # d_feat: feat's element type from the typed entry, fp32 from the other
-        if need_dfeat:
-            d_feat[0] = torch.empty((T, B, K), dtype=feat.dtype if typed else f32, device=dev)
-        return (w.data_ptr(), g.data_ptr(), be.data_ptr(), ln.data_ptr(), ptr(mn), ptr(iv), ptr(rm), ptr(rv), float(eps), ptr(mk),
-                T, B, K, C, ptr(d_feat[0]), B * K if need_dfeat else 0, K if need_dfeat else 0, d_weight.data_ptr(),
-                d_bias.data_ptr(), d_gamma.data_ptr(), d_beta.data_ptr(), scratch.data_ptr(), nbytes, F._stream_handle(dev))
-    with F._on_device(dev):
-        rc, _ = _feat_call("ctc_amd_head_backward", feat, (do.data_ptr(), do.stride(0), do.stride(1)), behind_feat)
-    if rc == _lib.ERR_UNSUPPORTED_SHAPE:
-        return None
-    if rc:
-        _lib.check(rc, "ctc_amd_head_backward")
-    return _dfeat_as(d_feat[0], feat), d_weight, d_bias, d_gamma, d_beta
+    return _head_backward("ctc_amd_head_backward", d_out, feat, weight, bn_weight, bn_bias, lin, mean, invstd, running_mean,
+                          running_var, eps, mask, need_dfeat)
 
 
 def head_forward_wide(feat, weight, bias, bn_weight, bn_bias, running_mean=None, running_var=None, eps=1e-5, mask=None,
@@ -190,37 +231,8 @@ def head_forward_wide(feat, weight, bias, bn_weight, bn_bias, running_mean=None,
     not take the shape (K not a multiple of 16, unaligned rows, T B > 2^22 rows, B > 65536).  The Linear output and all of eval
     mode are bit for bit the narrow entry's.  A bf16 / fp16 ``feat`` is read as it lies (``ctc_amd_head_forward_wide_typed``), as in
     ``head_forward``.  The scratch is one ``torch.empty`` per call, as ``head_backward`` explains."""
-    F._require_hip(feat, "feat")
-    T, B, K = feat.shape
-    C = weight.shape[0]
-    dev = feat.device
-    prm = [t if (t.dtype is torch.float32 and t.is_contiguous()) else t.float().contiguous()
-           for t in (weight, bias, bn_weight, bn_bias)]
-    rm = rv = None
-    if running_mean is not None:
-        rm, rv = running_mean.float().contiguous(), running_var.float().contiguous()
-    mk = None if mask is None else (mask if (mask.dtype is torch.float32 and mask.is_contiguous()) else mask.float().contiguous())
-    lib = _lib.load()
-    nbytes = lib.ctc_amd_head_forward_wide_scratch_bytes(T, B, K, C)
-    if nbytes == 0 and min(T, B, K, C) >= 1:
-        return None
-    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    out = torch.empty((T, B, C), dtype=torch.float32, device=dev)
-    train = rm is None
-    lin = torch.empty((T, B, C), dtype=torch.float32, device=dev) if want_backward_state else None
-    mean = torch.empty((T, C), dtype=torch.float32, device=dev) if train else None
-    var = torch.empty((T, C), dtype=torch.float32, device=dev) if train else None
-    inv = torch.empty((T, C), dtype=torch.float32, device=dev) if train else None
-    ptr = lambda t: None if t is None else t.data_ptr()     # noqa: E731
-    with F._on_device(dev):
-        rc, _ = _feat_call("ctc_amd_head_forward_wide", feat, (), lambda typed: (
-            *(t.data_ptr() for t in prm), ptr(rm), ptr(rv), float(eps), ptr(mk), T, B, K, C, out.data_ptr(), out.stride(0),
-            out.stride(1), ptr(lin), ptr(mean), ptr(var), ptr(inv), scratch.data_ptr(), nbytes, F._stream_handle(dev)))
-    if rc == _lib.ERR_UNSUPPORTED_SHAPE:
-        return None
-    if rc:
-        _lib.check(rc, "ctc_amd_head_forward_wide")
-    return out, lin, mean, var, inv
+    return _head_forward("ctc_amd_head_forward_wide", "ctc_amd_head_forward_wide_scratch_bytes", feat, weight, bias, bn_weight,
+                         bn_bias, running_mean, running_var, eps, mask, want_backward_state)
 
 
 def head_backward_wide(d_out, feat, weight, bn_weight, bn_bias, lin, mean=None, invstd=None, running_mean=None, running_var=None,
@@ -231,39 +243,8 @@ def head_backward_wide(d_out, feat, weight, bn_weight, bn_bias, lin, mean=None, 
     ``head_forward_wide`` refuses).  Deterministic.  A bf16 / fp16 ``feat`` is read as it lies (``ctc_amd_head_backward_wide_typed``)
     and ``d_feat`` comes back in ``feat``'s dtype, as in ``head_backward``.  The scratch is one ``torch.empty`` per call, as
     ``head_backward`` explains."""
-    F._require_hip(d_out, "d_out")
-    F._require_hip(feat, "feat")
-    T, B, K = feat.shape
-    C = weight.shape[0]
-    dev = feat.device
-    f32 = torch.float32
-    do = d_out if (d_out.dtype is f32 and d_out.stride(2) == 1) else d_out.float().contiguous()
-    cont = lambda t: None if t is None else (t if (t.dtype is f32 and t.is_contiguous()) else t.float().contiguous())   # noqa: E731
-    w, g, be, ln, mn, iv, rm, rv, mk = (cont(t) for t in (weight, bn_weight, bn_bias, lin, mean, invstd, running_mean,
-                                                           running_var, mask))
-    lib = _lib.load()
-    nbytes = lib.ctc_amd_head_backward_wide_scratch_bytes(T, B, K, C)
-    if nbytes == 0 and min(T, B, K, C) >= 1:
-        return None
-    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    d_weight = torch.empty((C, K), dtype=f32, device=dev)
-    d_bias, d_gamma, d_beta = (torch.empty(C, dtype=f32, device=dev) for _ in range(3))
-    ptr = lambda t: None if t is None else t.data_ptr()     # noqa: E731
-    d_feat = [None]
-
-    def behind_feat(typed):                                  # d_feat: feat's element type from the typed entry, fp32 from the other
-        if need_dfeat:
-            d_feat[0] = torch.empty((T, B, K), dtype=feat.dtype if typed else f32, device=dev)
-        return (w.data_ptr(), g.data_ptr(), be.data_ptr(), ln.data_ptr(), ptr(mn), ptr(iv), ptr(rm), ptr(rv), float(eps), ptr(mk),
-                T, B, K, C, ptr(d_feat[0]), B * K if need_dfeat else 0, K if need_dfeat else 0, d_weight.data_ptr(),
-                d_bias.data_ptr(), d_gamma.data_ptr(), d_beta.data_ptr(), scratch.data_ptr(), nbytes, F._stream_handle(dev))
-    with F._on_device(dev):
-        rc, _ = _feat_call("ctc_amd_head_backward_wide", feat, (do.data_ptr(), do.stride(0), do.stride(1)), behind_feat)
-    if rc == _lib.ERR_UNSUPPORTED_SHAPE:
-        return None
-    if rc:
-        _lib.check(rc, "ctc_amd_head_backward_wide")
-    return _dfeat_as(d_feat[0], feat), d_weight, d_bias, d_gamma, d_beta
+    return _head_backward("ctc_amd_head_backward_wide", d_out, feat, weight, bn_weight, bn_bias, lin, mean, invstd, running_mean,
+                          running_var, eps, mask, need_dfeat)
 
 
 def _head_backward_torch(d_out, feat, weight, gamma, beta, lin, mean, inv, mask, train, need_dfeat):
@@ -323,16 +304,11 @@ class _HeadFn(torch.autograd.Function):
         feat, weight, gamma, beta, lin, mean, inv, mask, rmean, rvar = ctx.saved_tensors
         T, B, _ = lin.shape
         need_dfeat = ctx.needs_input_grad[0]
+        bwd, gate = (head_backward_wide, HEAD_WIDE_BACKWARD_MAX_ROWS) if ctx.wide else (head_backward, HEAD_BACKWARD_MAX_ROWS)
         res = None
-        if ctx.wide:
-            if T * B <= HEAD_WIDE_BACKWARD_MAX_ROWS:
-                stats = (mean, inv, None, None) if ctx.train else (None, None, rmean, rvar)
-                res = head_backward_wide(d_out, feat, weight, gamma, beta, lin, *stats, ctx.eps, mask, need_dfeat)
-        elif T * B <= HEAD_BACKWARD_MAX_ROWS:
-            if ctx.train:
-                res = head_backward(d_out, feat, weight, gamma, beta, lin, mean, inv, None, None, ctx.eps, mask, need_dfeat)
-            else:
-                res = head_backward(d_out, feat, weight, gamma, beta, lin, None, None, rmean, rvar, ctx.eps, mask, need_dfeat)
+        if T * B <= gate:
+            stats = (mean, inv, None, None) if ctx.train else (None, None, rmean, rvar)
+            res = bwd(d_out, feat, weight, gamma, beta, lin, *stats, ctx.eps, mask, need_dfeat)
         if res is None:
             res = _head_backward_torch(d_out, feat, weight, gamma, beta, lin, mean, inv, mask, ctx.train, need_dfeat)
         return tuple(res) + (None, None, None, None)
@@ -345,8 +321,7 @@ def lstm_cell_step(x, h, c, w_ih, w_hh, b_ih, b_hh, series_row=None, pad_value=P
     B, I = x.shape
     H = h.shape[1]
     dev = x.device
-    args = [t if (t.dtype is torch.float32 and t.is_contiguous()) else t.float().contiguous()
-            for t in (x, h, c, w_ih, w_hh, b_ih, b_hh)]
+    args = [_f32c(t) for t in (x, h, c, w_ih, w_hh, b_ih, b_hh)]
     h_out = torch.empty((B, H), dtype=torch.float32, device=dev)
     c_out = torch.empty((B, H), dtype=torch.float32, device=dev)
     gates = torch.empty((B, 4 * H), dtype=torch.float32, device=dev) if want_gates else None
@@ -358,58 +333,66 @@ def lstm_cell_step(x, h, c, w_ih, w_hh, b_ih, b_hh, series_row=None, pad_value=P
         sp, ss, sc = series_row.data_ptr(), series_row.stride(0), series_row.shape[1]
     with F._on_device(dev):
         rc = _lib.load().ctc_amd_lstm_cell_step(*(t.data_ptr() for t in args), B, I, H, h_out.data_ptr(), c_out.data_ptr(),
-                                                gates.data_ptr() if want_gates else None, sp, ss, sc, float(pad_value),
-                                                F._stream_handle(dev))
-    if rc:
-        _lib.check(rc, "ctc_amd_lstm_cell_step")
+                                                _ptr(gates), sp, ss, sc, float(pad_value), F._stream_handle(dev))
+    _answer(rc, "ctc_amd_lstm_cell_step", refusal_is_none=False)
     return h_out, c_out, gates
+
+
+def _series_forward(name, query, v_all, h0, c0, w_ih, w_hh, b_ih, b_hh, cols, pad_value, want_backward_state):
+    """``lstm_series`` (``query`` None) and ``lstm_series_wide`` (``query``: the entry's scratch query): the entry ``name``"""
+    F._require_hip(v_all, "v_all")
+    T, B, I = v_all.shape
+    H = h0.shape[1]
+    cols = H if cols is None else int(cols)
+    dev = v_all.device
+    args = [_f32c(t) for t in (v_all, h0, c0, w_ih, w_hh, b_ih, b_hh)]
+    tail = ()                                                # (scratch, scratch_bytes) of the wide entry
+    if query is not None:
+        scratch = _scratch(query, dev, T, B, I, H)
+        if scratch is None:
+            return None
+        tail = (scratch[0].data_ptr(), scratch[1])
+    f32 = torch.float32
+    series = torch.empty((T, B, cols), dtype=f32, device=dev)
+    gates = torch.empty((T, B, 4 * H), dtype=f32, device=dev) if want_backward_state else None
+    cells = torch.empty((T + 1, B, H), dtype=f32, device=dev) if want_backward_state else None
+    with F._on_device(dev):
+        rc = getattr(_lib.load(), name)(*(t.data_ptr() for t in args), T, B, I, H, series.data_ptr(), series.stride(0),
+                                        series.stride(1), cols, float(pad_value), _ptr(gates), _ptr(cells), None, None, *tail,
+                                        F._stream_handle(dev))
+    return (series, gates, cells) if _answer(rc, name) else None
+
+
+def _series_backward(name, refusal_is_none, d_series, gates, cells, w_hh):
+    """``lstm_series_backward`` (a shape the entry refuses raises: its forward refused it first) and
+    ``lstm_series_backward_wide`` (None): the entry ``name``"""
+    F._require_hip(d_series, "d_series")
+    T, B, G = gates.shape
+    H = G // 4
+    dev = gates.device
+    f32 = torch.float32
+    ds = _rows(d_series)
+    g, c, w = (_f32c(t) for t in (gates, cells, w_hh))
+    dpre = torch.empty((T, B, G), dtype=f32, device=dev)
+    dh0 = torch.empty((B, H), dtype=f32, device=dev)
+    dc0 = torch.empty((B, H), dtype=f32, device=dev)
+    with F._on_device(dev):
+        rc = getattr(_lib.load(), name)(ds.data_ptr(), ds.stride(0), ds.stride(1), g.data_ptr(), c.data_ptr(), w.data_ptr(), T, B, H,
+                                        dpre.data_ptr(), dh0.data_ptr(), dc0.data_ptr(), F._stream_handle(dev))
+    return (dpre, dh0, dc0) if _answer(rc, name, refusal_is_none) else None
 
 
 def lstm_series(v_all, h0, c0, w_ih, w_hh, b_ih, b_hh, cols=None, pad_value=PAD_LOGIT, want_backward_state=False):
     """All T LSTMCell steps in ONE launch (``ctc_amd_lstm_series``; the reference's class counts, I + H <= 80) ->
     (v_series [T,B,cols], gates [T,B,4H] | None, cells [T+1,B,H] | None), or None when the size is not one the launch
     takes (step frame by frame with ``lstm_cell_step`` then)."""
-    F._require_hip(v_all, "v_all")
-    T, B, I = v_all.shape
-    H = h0.shape[1]
-    cols = H if cols is None else int(cols)
-    dev = v_all.device
-    args = [t if (t.dtype is torch.float32 and t.is_contiguous()) else t.float().contiguous()
-            for t in (v_all, h0, c0, w_ih, w_hh, b_ih, b_hh)]
-    series = torch.empty((T, B, cols), dtype=torch.float32, device=dev)
-    gates = torch.empty((T, B, 4 * H), dtype=torch.float32, device=dev) if want_backward_state else None
-    cells = torch.empty((T + 1, B, H), dtype=torch.float32, device=dev) if want_backward_state else None
-    with F._on_device(dev):
-        rc = _lib.load().ctc_amd_lstm_series(*(t.data_ptr() for t in args), T, B, I, H, series.data_ptr(), series.stride(0),
-                                             series.stride(1), cols, float(pad_value),
-                                             gates.data_ptr() if want_backward_state else None,
-                                             cells.data_ptr() if want_backward_state else None, None, None, F._stream_handle(dev))
-    if rc == _lib.ERR_UNSUPPORTED_SHAPE:
-        return None
-    if rc:
-        _lib.check(rc, "ctc_amd_lstm_series")
-    return series, gates, cells
+    return _series_forward("ctc_amd_lstm_series", None, v_all, h0, c0, w_ih, w_hh, b_ih, b_hh, cols, pad_value, want_backward_state)
 
 
 def lstm_series_backward(d_series, gates, cells, w_hh):
     """The backward recurrence of ``lstm_series`` in one launch (``ctc_amd_lstm_series_backward``) ->
     (dpre [T,B,4H], dh0 [B,H], dc0 [B,H]); ``d_series`` [T,B,>=H]: the upstream gradient of v_series."""
-    F._require_hip(d_series, "d_series")
-    T, B, G = gates.shape
-    H = G // 4
-    dev = gates.device
-    ds = d_series if (d_series.dtype is torch.float32 and d_series.stride(2) == 1) else d_series.float().contiguous()
-    w = w_hh if (w_hh.dtype is torch.float32 and w_hh.is_contiguous()) else w_hh.float().contiguous()
-    dpre = torch.empty((T, B, G), dtype=torch.float32, device=dev)
-    dh0 = torch.empty((B, H), dtype=torch.float32, device=dev)
-    dc0 = torch.empty((B, H), dtype=torch.float32, device=dev)
-    with F._on_device(dev):
-        rc = _lib.load().ctc_amd_lstm_series_backward(ds.data_ptr(), ds.stride(0), ds.stride(1), gates.data_ptr(), cells.data_ptr(),
-                                                      w.data_ptr(), T, B, H, dpre.data_ptr(), dh0.data_ptr(), dc0.data_ptr(),
-                                                      F._stream_handle(dev))
-    if rc:
-        _lib.check(rc, "ctc_amd_lstm_series_backward")
-    return dpre, dh0, dc0
+    return _series_backward("ctc_amd_lstm_series_backward", False, d_series, gates, cells, w_hh)
 
 
 def lstm_series_wide(v_all, h0, c0, w_ih, w_hh, b_ih, b_hh, cols=None, pad_value=PAD_LOGIT, want_backward_state=False):
@@ -418,56 +401,14 @@ def lstm_series_wide(v_all, h0, c0, w_ih, w_hh, b_ih, b_hh, cols=None, pad_value
     ``lstm_cell_step`` give, or None when the entry does not take the shape (I or H > 160, T B > 2^22 rows).  The scratch (the
     transposed weights, the x part of every row's pre-activations [T B, 4H]) is one ``torch.empty`` per call, for
     ``head_backward``'s reasons."""
-    F._require_hip(v_all, "v_all")
-    T, B, I = v_all.shape
-    H = h0.shape[1]
-    cols = H if cols is None else int(cols)
-    dev = v_all.device
-    args = [t if (t.dtype is torch.float32 and t.is_contiguous()) else t.float().contiguous()
-            for t in (v_all, h0, c0, w_ih, w_hh, b_ih, b_hh)]
-    lib = _lib.load()
-    nbytes = lib.ctc_amd_lstm_series_wide_scratch_bytes(T, B, I, H)
-    if nbytes == 0 and min(T, B, I, H) >= 1:
-        return None
-    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    series = torch.empty((T, B, cols), dtype=torch.float32, device=dev)
-    gates = torch.empty((T, B, 4 * H), dtype=torch.float32, device=dev) if want_backward_state else None
-    cells = torch.empty((T + 1, B, H), dtype=torch.float32, device=dev) if want_backward_state else None
-    with F._on_device(dev):
-        rc = lib.ctc_amd_lstm_series_wide(*(t.data_ptr() for t in args), T, B, I, H, series.data_ptr(), series.stride(0),
-                                          series.stride(1), cols, float(pad_value),
-                                          gates.data_ptr() if want_backward_state else None,
-                                          cells.data_ptr() if want_backward_state else None, None, None,
-                                          scratch.data_ptr(), nbytes, F._stream_handle(dev))
-    if rc == _lib.ERR_UNSUPPORTED_SHAPE:
-        return None
-    if rc:
-        _lib.check(rc, "ctc_amd_lstm_series_wide")
-    return series, gates, cells
+    return _series_forward("ctc_amd_lstm_series_wide", "ctc_amd_lstm_series_wide_scratch_bytes", v_all, h0, c0, w_ih, w_hh, b_ih,
+                           b_hh, cols, pad_value, want_backward_state)
 
 
 def lstm_series_backward_wide(d_series, gates, cells, w_hh):
     """``lstm_series_backward`` for every 1 <= H <= 160 (``ctc_amd_lstm_series_backward_wide``, one launch, deterministic) ->
     (dpre [T,B,4H], dh0 [B,H], dc0 [B,H]), or None when the entry does not take the shape (H > 160)."""
-    F._require_hip(d_series, "d_series")
-    T, B, G = gates.shape
-    H = G // 4
-    dev = gates.device
-    f32 = torch.float32
-    ds = d_series if (d_series.dtype is f32 and d_series.stride(2) == 1) else d_series.float().contiguous()
-    g, c, w = (t if (t.dtype is f32 and t.is_contiguous()) else t.float().contiguous() for t in (gates, cells, w_hh))
-    dpre = torch.empty((T, B, G), dtype=f32, device=dev)
-    dh0 = torch.empty((B, H), dtype=f32, device=dev)
-    dc0 = torch.empty((B, H), dtype=f32, device=dev)
-    with F._on_device(dev):
-        rc = _lib.load().ctc_amd_lstm_series_backward_wide(ds.data_ptr(), ds.stride(0), ds.stride(1), g.data_ptr(), c.data_ptr(),
-                                                           w.data_ptr(), T, B, H, dpre.data_ptr(), dh0.data_ptr(), dc0.data_ptr(),
-                                                           F._stream_handle(dev))
-    if rc == _lib.ERR_UNSUPPORTED_SHAPE:
-        return None
-    if rc:
-        _lib.check(rc, "ctc_amd_lstm_series_backward_wide")
-    return dpre, dh0, dc0
+    return _series_backward("ctc_amd_lstm_series_backward_wide", True, d_series, gates, cells, w_hh)
 
 
 def lstm_bias_grad_wide(dpre):
@@ -476,14 +417,13 @@ def lstm_bias_grad_wide(dpre):
     tensors with the same values."""
     F._require_hip(dpre, "dpre")
     G = dpre.shape[-1]
-    d = dpre if (dpre.dtype is torch.float32 and dpre.is_contiguous()) else dpre.float().contiguous()
+    d = _f32c(dpre)
     rows = d.numel() // G
     d_b_ih, d_b_hh = (torch.empty(G, dtype=torch.float32, device=d.device) for _ in range(2))
     with F._on_device(d.device):
         rc = _lib.load().ctc_amd_lstm_bias_grad_wide(d.data_ptr(), rows, G // 4, d_b_ih.data_ptr(), d_b_hh.data_ptr(),
                                                      F._stream_handle(d.device))
-    if rc:
-        _lib.check(rc, "ctc_amd_lstm_bias_grad_wide")
+    _answer(rc, "ctc_amd_lstm_bias_grad_wide", refusal_is_none=False)
     return d_b_ih, d_b_hh
 
 
@@ -504,32 +444,23 @@ def lstm_backward(d_series, gates, cells, v_all, h0, series, w_ih, w_hh, need_dx
     f32 = torch.float32
     # rows the entry can address: unit stride over the columns and a row pitch of at least the width (autograd hands a
     # broadcast upstream gradient over with pitch 0, e.g. behind series.sum(1): that one is copied)
-    rows = lambda t: t if (t.dtype is f32 and t.stride(2) == 1 and t.stride(1) >= t.shape[2]) else t.float().contiguous()   # noqa: E731
-    cont = lambda t: t if (t.dtype is f32 and t.is_contiguous()) else t.float().contiguous()          # noqa: E731
-    ds, x, sr = rows(d_series), rows(v_all), rows(series)
-    g, c, h, wi, wh = (cont(t) for t in (gates, cells, h0, w_ih, w_hh))
-    lib = _lib.load()
-    nbytes = lib.ctc_amd_lstm_backward_scratch_bytes(T, B, I, H)
-    if nbytes == 0 and min(T, B, I, H) >= 1:
+    ds, x, sr = (_rows(t, pitch=True) for t in (d_series, v_all, series))
+    g, c, h, wi, wh = (_f32c(t) for t in (gates, cells, h0, w_ih, w_hh))
+    scratch = _scratch("ctc_amd_lstm_backward_scratch_bytes", dev, T, B, I, H)
+    if scratch is None:
         return None
-    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
     d_x = torch.empty((T, B, I), dtype=f32, device=dev) if need_dx else None
     dh0, dc0 = (torch.empty((B, H), dtype=f32, device=dev) for _ in range(2))
     d_w_ih = torch.empty((4 * H, I), dtype=f32, device=dev)
     d_w_hh = torch.empty((4 * H, H), dtype=f32, device=dev)
     d_b_ih, d_b_hh = (torch.empty(4 * H, dtype=f32, device=dev) for _ in range(2))
     with F._on_device(dev):
-        rc = lib.ctc_amd_lstm_backward(ds.data_ptr(), ds.stride(0), ds.stride(1), g.data_ptr(), c.data_ptr(),
-                                       x.data_ptr(), x.stride(0), x.stride(1), h.data_ptr(),
-                                       sr.data_ptr(), sr.stride(0), sr.stride(1), wi.data_ptr(), wh.data_ptr(), T, B, I, H,
-                                       d_x.data_ptr() if need_dx else None, B * I if need_dx else 0, I if need_dx else 0,
-                                       dh0.data_ptr(), dc0.data_ptr(), d_w_ih.data_ptr(), d_w_hh.data_ptr(),
-                                       d_b_ih.data_ptr(), d_b_hh.data_ptr(), scratch.data_ptr(), nbytes, F._stream_handle(dev))
-    if rc == _lib.ERR_UNSUPPORTED_SHAPE:
-        return None
-    if rc:
-        _lib.check(rc, "ctc_amd_lstm_backward")
-    return d_x, dh0, dc0, d_w_ih, d_w_hh, d_b_ih, d_b_hh
+        rc = _lib.load().ctc_amd_lstm_backward(
+            ds.data_ptr(), ds.stride(0), ds.stride(1), g.data_ptr(), c.data_ptr(), x.data_ptr(), x.stride(0), x.stride(1),
+            h.data_ptr(), sr.data_ptr(), sr.stride(0), sr.stride(1), wi.data_ptr(), wh.data_ptr(), T, B, I, H,
+            _ptr(d_x), B * I if need_dx else 0, I if need_dx else 0, dh0.data_ptr(), dc0.data_ptr(), d_w_ih.data_ptr(),
+            d_w_hh.data_ptr(), d_b_ih.data_ptr(), d_b_hh.data_ptr(), scratch[0].data_ptr(), scratch[1], F._stream_handle(dev))
+    return (d_x, dh0, dc0, d_w_ih, d_w_hh, d_b_ih, d_b_hh) if _answer(rc, "ctc_amd_lstm_backward") else None
 
 
 def _series_backward_torch(d_series, v_all, w_ih, w_hh, hs, cs, gs, H, recurrence=lstm_series_backward, bias_grad=None):
@@ -559,20 +490,14 @@ def lstm_forward(feat, weight, bias, bn_weight, bn_bias, running_mean, running_v
     C = weight.shape[0]
     cols = C if cols is None else int(cols)
     dev = feat.device
-    args = [t if (t.dtype is torch.float32 and t.is_contiguous()) else t.float().contiguous()
-            for t in (weight, bias, bn_weight, bn_bias, running_mean, running_var)]
-    cell = [t if (t.dtype is torch.float32 and t.is_contiguous()) else t.float().contiguous()
-            for t in (h0, c0, w_ih, w_hh, b_ih, b_hh)]
+    args = [_f32c(t) for t in (weight, bias, bn_weight, bn_bias, running_mean, running_var)]
+    cell = [_f32c(t) for t in (h0, c0, w_ih, w_hh, b_ih, b_hh)]
     series = torch.empty((T, B, cols), dtype=torch.float32, device=dev)
     with F._on_device(dev):
         rc, _ = _feat_call("ctc_amd_lstm_forward", feat, (), lambda typed: (
             *(t.data_ptr() for t in args), float(eps), *(t.data_ptr() for t in cell), T, B, K, C, series.data_ptr(),
             series.stride(0), series.stride(1), cols, float(pad_value), None, None, F._stream_handle(dev)))
-    if rc == _lib.ERR_UNSUPPORTED_SHAPE:
-        return None
-    if rc:
-        _lib.check(rc, "ctc_amd_lstm_forward")
-    return series
+    return series if _answer(rc, "ctc_amd_lstm_forward") else None
 
 
 # LSTM_cell.forward in eval mode takes the one-launch path up to this many head rows per workgroup (4 T: a workgroup does the

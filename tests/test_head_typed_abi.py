@@ -140,6 +140,22 @@ def test_f32_is_the_untyped_entry(lib, name):
         assert got == _call(lib, name, F32, untyped=True, **kw) and got in (BAD_ARGUMENT, UNSUPPORTED_SHAPE), kw
 
 
+@pytest.mark.parametrize("dtype", [F32, BF16, F16])
+def test_narrow_forward_one_row_in_train_mode_wins_over_the_shape(lib, dtype):
+    """train mode needs two rows per frame: a bad argument, answered before the shape as in every sibling (the wide forward, both
+    backward entries) -- B = 1 with K = 24, B = 1 with a misaligned feat"""
+    name = "ctc_amd_head_forward_typed"
+    assert _call(lib, name, dtype, B=1) == BAD_ARGUMENT
+    assert _call(lib, name, dtype, B=1, K=24) == BAD_ARGUMENT
+    assert _call(lib, name, dtype, B=1, feat=P + 4) == BAD_ARGUMENT
+    if dtype == F32:
+        assert _call(lib, name, dtype, B=1, K=24, untyped=True) == BAD_ARGUMENT
+        assert _call(lib, name, dtype, B=1, feat=P + 4, untyped=True) == BAD_ARGUMENT
+    # eval mode takes a single row, so there the shape answers
+    assert _call(lib, name, dtype, B=1, K=24, eval_mode=True) == UNSUPPORTED_SHAPE
+    assert _call(lib, name, dtype, B=1, feat=P + 4, eval_mode=True) == UNSUPPORTED_SHAPE
+
+
 def test_no_cpu_path_for_two_byte_features():
     import torch
     import ctc_amd

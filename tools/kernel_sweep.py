@@ -89,7 +89,7 @@ def reduce(out):
     col = lambda r, prefix: "x".join(r[k] for k in sorted(r) if k.startswith(prefix))
     print("# kernel | grid | workgroup | LDS bytes")
     for r in rows:
-        if "ctc::" in r["Kernel_Name"]:
+        if "ctc::" in r["Kernel_Name"] or "_ZN3ctc" in r["Kernel_Name"]:     # (the profiler leaves __bf16 instantiations mangled)
             print("%s | %s | %s | %s" % (r["Kernel_Name"], col(r, "Grid_Size"), col(r, "Workgroup_Size"), col(r, "LDS")))
 
 
