@@ -115,7 +115,8 @@ def host_ext_is_current():
     src = os.path.join(CSRC, "autograd_ext.cpp")
     if not (os.path.exists(HOST_EXT_SO) and os.path.exists(HOST_EXT_STAMP)):
         return False
-    if os.path.getmtime(HOST_EXT_SO) < os.path.getmtime(src):
+    header = os.path.join(HERE, "..", "include", "ctc_amd.h")   # (its prototypes are asserted against at compile time)
+    if os.path.getmtime(HOST_EXT_SO) < max(os.path.getmtime(src), os.path.getmtime(header)):
         return False
     return open(HOST_EXT_STAMP).read().strip() == torch.__version__
 
@@ -131,6 +132,7 @@ def build_host_ext(verbose=False):
     from torch.utils import cpp_extension
     os.makedirs(HOST_EXT_DIR, exist_ok=True)
     cpp_extension.load(name="ctc_amd_autograd_ext", sources=[src], build_directory=HOST_EXT_DIR, extra_cflags=["-O2"],
+                       extra_include_paths=[os.path.join(HERE, "..", "include")],
                        with_cuda=False, verbose=verbose, is_python_module=False)
     with open(HOST_EXT_STAMP, "w") as f:
         f.write(torch.__version__)

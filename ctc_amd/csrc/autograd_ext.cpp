@@ -10,7 +10,10 @@
 // lengths int64 [B] on that device and contiguous.
 #include <torch/extension.h>
 
+#include <type_traits>
 #include <vector>
+
+#include "ctc_amd.h"                                         // declarations only: nothing here links against the library
 
 namespace {
 
@@ -19,6 +22,11 @@ typedef int (*noblank_fn)(const float *, int64_t, int64_t, const void *, int, co
 typedef int (*binary_fn)(const float *, int64_t, int64_t, const float *, const int64_t *, const int64_t *, int, int, int, int,
                          float, float, float *, float *, float *, void *, void *);
 typedef int (*scale_fn)(float *, const float *, size_t, void *);
+// the typedefs above are a hand-written copy of three prototypes of include/ctc_amd.h, fed by raw addresses: a drift
+// (an int where the header says int64_t) must not compile
+static_assert(std::is_same<noblank_fn, decltype(&ctc_amd_noblank_loss_grad)>::value, "noblank_fn is not ctc_amd_noblank_loss_grad");
+static_assert(std::is_same<binary_fn, decltype(&ctc_amd_binary_loss_grad)>::value, "binary_fn is not ctc_amd_binary_loss_grad");
+static_assert(std::is_same<scale_fn, decltype(&ctc_amd_scale_grad)>::value, "scale_fn is not ctc_amd_scale_grad");
 
 struct Abi {
     noblank_fn noblank = nullptr;

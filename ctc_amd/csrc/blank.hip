@@ -326,9 +326,12 @@ __device__ __forceinline__ void blank_state_flags(const BlankParams &p, int b, i
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         const int s = s0 + k;
-        // alpha: from s-2 when l'_s is a label differing from l'_{s-2};  beta: from s+2 likewise
+        // alpha: from s-2 when l'_s is a label differing from l'_{s-2};  beta: from s+2 likewise.  The state ENTERED must
+        // not carry the blank's class (only a bad label clamped by blank_classes can): the rule of align_skip_flag, so
+        // that the loss and the read-outs keep one lattice on such a target too
         const int s2 = FWD ? s - 2 : s + 2;
-        skip[k] = (s & 1) && s2 >= 0 && s2 < n && cls[s] != cls[s2];
+        const int into = FWD ? s : s2;
+        skip[k] = (s & 1) && s2 >= 0 && s2 < n && cls[s] != cls[s2] && cls[into] != p.blank;
     }
 }
 
@@ -1038,8 +1041,9 @@ __device__ __forceinline__ void blank_row_emit(const BlankParams &p, int t, int 
     const float inv = 1.0f / ssum;
 #pragma unroll
     for (int k = 0; k < K; ++k) gam[s0 + k] = v[k] * inv;            // wave-local LDS, in order
-    // occupancy per class: blank from the reduction, labels folded along the repeat chain
-    if (lane == 0) occ[p.blank] = blank_part * inv;
+    // occupancy per class: labels folded along the repeat chain, then the blank from the reduction -- ADDED to its
+    // entry (0 between rows: the same bits on a valid target): a bad label that blank_classes clamped onto the blank's
+    // class has left its states' share there, and both belong to that column
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         if (tb.first[k]) {                                    // label states only; repeats are chained
@@ -1048,6 +1052,7 @@ __device__ __forceinline__ void blank_row_emit(const BlankParams &p, int t, int 
             occ[tb.cls[k]] = tot;
         }
     }
+    if (lane == 0) occ[p.blank] += blank_part * inv;         // (same wave: LDS keeps program order)
     blank_row_dense<VEC4>(p, t, b, xr, occ, p.grad_scale / (float)(L > 1 ? L : 1));
     // un-set only what this row touched
     if (lane == 0) occ[p.blank] = 0.f;

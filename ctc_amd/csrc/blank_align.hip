@@ -712,8 +712,8 @@ __global__ __launch_bounds__(2 * kWave) void blank_post_chain_kernel(PostParams 
 {
     const int b = blockIdx.x;
     int Tb, L;
-    if (!align_sample(p.a, b, Tb, L)) {                          // lengths out of contract: NaN, gamma rows 0
-        if (threadIdx.x == 0) p.nll[b] = __builtin_nanf("");
+    if (!align_sample(p.a, b, Tb, L)) {                          // lengths outside the tensor: no alignment (+inf, gamma rows 0),
+        if (threadIdx.x == 0) p.nll[b] = __builtin_inff();       // as ctc_amd_blank_loss_grad reports such a sample
         return;
     }
     if (wave_id() == 0) post_chain<K, true>(p, b, Tb, L);
@@ -754,7 +754,7 @@ __global__ __launch_bounds__(kPostThreads) void blank_post_gamma_kernel(PostPara
     if (t0 >= T) return;
     int Tb, L;
     const bool ok = align_sample(p.a, b, Tb, L);
-    const bool feasible = ok && p.nll[b] < __builtin_inff();     // (+inf: no alignment; NaN: bad lengths)
+    const bool feasible = ok && p.nll[b] < __builtin_inff();     // (+inf: no alignment, bad lengths included)
     const int n = 2 * L + 1;
     const int64_t r0 = (int64_t)b * T + t0;
     const float *al = p.al + r0 * p.NSP, *be = p.be + r0 * p.NSP;

@@ -166,8 +166,8 @@ __global__ __launch_bounds__(kWideAlignMaxWaves * kWave) void blank_post_wide_ch
 {
     const int b = blockIdx.x;
     int Tb, L;
-    if (!align_sample(q.p.a, b, Tb, L)) {                        // lengths out of contract: NaN, gamma rows 0
-        if (blockIdx.y == 0 && threadIdx.x == 0) q.p.nll[b] = __builtin_nanf("");
+    if (!align_sample(q.p.a, b, Tb, L)) {                        // lengths outside the tensor: no alignment (+inf, gamma rows 0)
+        if (blockIdx.y == 0 && threadIdx.x == 0) q.p.nll[b] = __builtin_inff();
         return;                                                   // (uniform over the workgroup)
     }
     if (blockIdx.y == 0) post_wide_chain<true>(q, b, Tb, L);

@@ -39,7 +39,7 @@ __global__ __launch_bounds__(kPostThreads) void blank_post_conf_kernel(PostParam
     if (t0 >= T) return;
     int Tb, L;
     const bool ok = align_sample(p.a, b, Tb, L);
-    const bool feasible = ok && p.nll[b] < __builtin_inff();     // (+inf: no alignment; NaN: bad lengths)
+    const bool feasible = ok && p.nll[b] < __builtin_inff();     // (+inf: no alignment, bad lengths included)
     const int n = 2 * L + 1;
     const int64_t r0 = (int64_t)b * T + t0;
     int st[kPostRows];                                            // the path's states of the four rows (wave-uniform)

@@ -288,8 +288,8 @@ __global__ __launch_bounds__(kGradWaves * kWave) void blank_wide_grad_kernel(Bla
         for (int q = 0; q < W; ++q)
 #pragma unroll
             for (int k = 0; k < K; ++k) gam[q * kWideSpan + lane * K + k] = v[q][k] * inv;   // wave-local LDS, in order
-        // occupancy per class: blank from the reduction, labels folded along the repeat chain
-        if (lane == 0) occ[p.blank] = blank_part * inv;
+        // occupancy per class: labels folded along the repeat chain, then the blank from the reduction, added to its
+        // entry as in blank_row_emit (a bad label clamped onto the blank's class has left its share there)
 #pragma unroll
         for (int q = 0; q < W; ++q) {
 #pragma unroll
@@ -303,6 +303,7 @@ __global__ __launch_bounds__(kGradWaves * kWave) void blank_wide_grad_kernel(Bla
                 }
             }
         }
+        if (lane == 0) occ[p.blank] += blank_part * inv;
         blank_row_dense<VEC4>(p, t, b, xr, occ, p.grad_scale / (float)(L > 1 ? L : 1));
         // un-set only what this row touched
         if (lane == 0) occ[p.blank] = 0.f;

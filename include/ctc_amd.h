@@ -19,6 +19,35 @@
  *    (ctc_amd_workspace_status), bytes [44,48) the gate word (ctc_amd_collective_gate);
  *  - return value: 0 on success, a hipError_t (> 0) from the launch, or one of the
  *    negative CTC_AMD_ERR_* codes; ctc_amd_error_string() describes any of them.
+ *
+ * Lengths and labels outside their range (every loss and every lattice read-out below; the library cannot check
+ * device-resident values without a synchronisation, so every kernel guards itself; tests/test_bad_inputs_gpu.py):
+ *  - lengths are compared as full int64 values.  A sample whose in_len is outside [1, T] or whose tgt_len is outside
+ *    [1, S] (blank lattice: [0, S]) -- 0, negative, beyond the tensor, or a value beyond 32 bits whose low word would
+ *    be valid -- is a sample WITHOUT AN ALIGNMENT, exactly like one that is too short (T_b < L_b): nothing of it is
+ *    read beyond its lengths and labels, and it reports
+ *      loss entries     nll >= 1e12 (blank lattice: +inf), never NaN; all T gradient rows exactly 0
+ *      best paths       path -1 on all T frames, score -inf
+ *      posteriors       nll >= 1e12 (blank lattice: +inf), never NaN; all T rows of gamma exactly 0
+ *      token spans      nll +inf, path -1, score -inf, frame_conf 0, start / end -1, conf 0
+ *    The other samples of the batch are not affected: they get, bit for bit, what they get beside a sample that is merely
+ *    too short.  `loss` is the documented function of the nll the launch returned (so +inf with a blank-lattice
+ *    sample of this kind in the batch, and a mean dominated by 1e13 on the other two).
+ *    One difference, deliberate: ctc_amd_blank_loss_grad alone takes in_len = 0 -- with tgt_len = 0 that is the empty
+ *    alignment of an empty target, nll = 0 (as torch); with tgt_len >= 1 no alignment.  The blank read-outs, which have
+ *    no frame to report on, treat in_len = 0 like every other value outside [1, T].
+ *  - labels are read by their LOW 32 BITS (an int64 label of 2^32 + k is class k), entries at l >= tgt_len[b] never.
+ *    Inside tgt_len[b] a class outside [0, C) is made a class by the lattice's own rule:
+ *      no-blank lattice  modulo C, negative values wrapping as a Python index does (-1 is class C - 1, C is class 0):
+ *                        what the reference's lp[:, :, label] does for the negative ones
+ *      blank lattice     clamped to [0, C - 1].  A clamp can land on the blank's class; such a label state emits the
+ *                        blank's log-prob, is never entered by the skip edge (s - 2 -> s), and its occupancy goes to
+ *                        the blank's column of the gradient -- one rule for the loss and the read-outs.  (torch would
+ *                        read out of bounds, and for a target equal to the blank keeps the skip edge.)
+ *    Either way the sample is computed as if the caller had passed those classes; nothing is flagged.
+ *  - the Python layer (ctc_amd/) validates lengths it can see without a synchronisation (host tensors, lists) and
+ *    raises ValueError before any launch; CTC_AMD_VALIDATE=1 extends that to device-resident lengths, at the cost
+ *    of a synchronisation per call.  Labels are never validated.
  */
 #ifndef CTC_AMD_H
 #define CTC_AMD_H
@@ -57,6 +86,8 @@ size_t ctc_amd_workspace_bytes(int variant, int T, int B, int C, int S);
  *   labels   [B,S] class indices, int32 (labels_i64 = 0) or int64 (= 1); entries at
  *            l >= tgt_len[b] are never dereferenced (the dataset pads with -1)
  *   in_len   [B] int64, 1 <= T_b <= T        tgt_len [B] int64, 1 <= L_b <= S
+ *            (a sample with a length outside these ranges has no alignment; labels outside [0, C) are taken modulo C:
+ *            Conventions, "Lengths and labels outside their range")
  *   nll      [B]  out: -alpha[T_b-1, L_b-1]  (1e13 when no alignment exists)
  *   loss     [1]  out: loss_scale * sum_b nll[b]   (loss_scale = 1/B for the
  *            reference's batch mean :139-140; 1/B_global on a batch shard).  The sum is taken
@@ -133,6 +164,7 @@ int ctc_amd_noblank_loss_grad_typed(const void *x, int x_dtype, int64_t stride_t
  * except   y [B,S,C] fp32 multi-hot / soft targets in [0,1], contiguous;
  * emission = -BCELoss(sigmoid(x[t,b,:]), y[b,l,:]) (:112,:88, logs clamped at -100);
  * grad = grad_scale/C * (sigmoid(x) - sum_l gamma_t(l) y[b,l,c]).
+ * A sample with a length outside [1, T] / [1, S]: no alignment, nll >= 1e12, gradient rows 0 (Conventions).
  */
 int ctc_amd_binary_loss_grad(const float *x, int64_t stride_t, int64_t stride_b,
                              const float *y,
@@ -145,6 +177,9 @@ int ctc_amd_binary_loss_grad(const float *x, int64_t stride_t, int64_t stride_b,
 /* torch.nn.CTCLoss(blank, reduction='mean', zero_infinity=False) as used at
  * models/layers/AsyncTFCriterion.py:198,319-321 (padded [B,S] targets).
  *   log_probs [T,B,C] fp32, already normalised; targets [B,S] int32/int64
+ *   in_len [B] int64, 0 <= T_b <= T; tgt_len [B] int64, 0 <= L_b <= S.  A length outside these ranges: no alignment
+ *         (nll = +inf, gradient rows 0); targets outside [0, C) inside L_b are clamped to [0, C-1], and one that lands
+ *         on the blank's class is never skipped into (Conventions, "Lengths and labels outside their range")
  *   nll   [B]  out: un-normalised negative log-likelihood (+inf if infeasible)
  *   loss  [1]  out: loss_scale * sum_b nll[b] / max(L_b,1)
  *   grad  [T,B,C] out or NULL: (exp(lp) - occupancy) * grad_scale / max(L_b,1)
@@ -239,6 +274,8 @@ int ctc_amd_scale_grad_typed(void *grad, int dtype, const float *grad_out, size_
  *   path  [B,T] int32 out: label position l_t of the best alignment for t < T_b,
  *         -1 for t >= T_b or when no alignment exists
  *   score [B]   out: log-probability of that alignment
+ * Lengths outside [1, T] / [1, S]: no alignment (path -1 on all T frames, score -inf); labels outside [0, C): modulo C
+ * (Conventions).
  */
 int ctc_amd_noblank_best_path(const float *x, int64_t stride_t, int64_t stride_b,
                               const void *labels, int labels_i64,
@@ -249,7 +286,8 @@ int ctc_amd_noblank_best_path(const float *x, int64_t stride_t, int64_t stride_b
 
 /* The same on the lattice of the binary variant (SURVEY 8f-1 for NoBlankBinaryCTC): y [B,S,C] float label rows;
  * cell (t, l) costs -nn.BCELoss()(sigmoid(x[t,b,:]), y[b,l,:]) (NoBlankBinaryCTC.py:112,:88,:146).  path [B,T] (label-row
- * positions, -1 behind T_b or when no alignment exists), score [B] its log-probability. */
+ * positions, -1 behind T_b or when no alignment exists), score [B] its log-probability.  Lengths outside their range: no
+ * alignment, as above. */
 int ctc_amd_binary_best_path(const float *x, int64_t stride_t, int64_t stride_b, const float *y,
                              const int64_t *in_len, const int64_t *tgt_len,
                              int T, int B, int C, int S,
@@ -277,7 +315,9 @@ int ctc_amd_binary_best_path(const float *x, int64_t stride_t, int64_t stride_b,
  * and ((3T + 8) SP + 2T + 3SP + 8) * 4 + T * SP + 16 bytes <= 160 KB, SP = S rounded up to the states per lane (1, 2, 4
  * for S <= 64, 128, 256) -- 13 bytes per lattice cell, T = 150 at every S <= 64; CTC_AMD_ERR_UNSUPPORTED_SHAPE beyond.
  * Null pointers and T, B, C, S < 1 return CTC_AMD_ERR_BAD_ARGUMENT before anything is dereferenced or launched.
- * `workspace` is ignored and may be NULL.  No atomics, no waiting between workgroups: deterministic. */
+ * `workspace` is ignored and may be NULL.  No atomics, no waiting between workgroups: deterministic.
+ * Lengths outside [1, T] / [1, S]: a sample without an alignment (nll +inf, path -1, score -inf, frame_conf 0, spans -1 / -1,
+ * conf 0); labels outside [0, C) inside L_b: modulo C, read by their low 32 bits (Conventions). */
 int ctc_amd_noblank_token_spans(const float *x, int64_t stride_t, int64_t stride_b,
                                 const void *labels, int labels_i64,
                                 const int64_t *in_len, const int64_t *tgt_len,
@@ -309,7 +349,8 @@ int ctc_amd_binary_token_spans(const float *x, int64_t stride_t, int64_t stride_
  *         v(2L) > v(2L-1), else 2L-1; 0 when L = 0), -1 for t >= T_b and for samples with no alignment
  *   score [B]   out: v of the final state (-inf: no alignment -- too short for L plus its adjacent repeats, or every
  *         path crosses a -inf log-prob, e.g. a label's class masked on every frame; the path is -1 on every frame either
- *         way, exactly the samples for which ctc_amd_blank_loss_grad gives nll = +inf)
+ *         way, exactly the samples for which ctc_amd_blank_loss_grad gives nll = +inf).  A length outside [1, T] /
+ *         [0, S]: the same (path -1 on all T frames, score -inf); targets outside [0, C) are clamped (Conventions)
  * workspace: at least ctc_amd_workspace_bytes(CTC_AMD_BLANK, T, B, C, S) bytes; the 256-byte header is left alone
  * except for status bit 8.  S <= 255 (CTC_AMD_ERR_UNSUPPORTED_SHAPE beyond: 256..1023 label columns are
  * ctc_amd_blank_best_path_wide's), any T (back-pointers beyond LDS go to the workspace). */
@@ -348,7 +389,8 @@ int ctc_amd_blank_best_path_wide(const float *log_probs, int64_t stride_t, int64
  * l'_s != blank and l'_s != l'_{s-2}]) + lp[t,l'_s].  beta' leaves out the emission of its own step:
  * beta'_{T_b-1}(2L) = beta'_{T_b-1}(2L-1) = 0 (state 0 only when L = 0), others -inf, and the mirror recursion over the
  * successors s, s+1, [s+2 under the same skip rule], each carrying its emission lp[t+1, l'_.].
- *   nll   [B] out: -LSE(alpha_{T_b-1}(2L), alpha_{T_b-1}(2L-1)), as ctc_amd_blank_loss_grad writes it (+inf: no alignment)
+ *   nll   [B] out: -LSE(alpha_{T_b-1}(2L), alpha_{T_b-1}(2L-1)), as ctc_amd_blank_loss_grad writes it (+inf: no alignment,
+ *         a length outside [1, T] / [0, S] included: all T rows of gamma are 0 then; Conventions)
  *   gamma [B,T,2S+1] fp32 contiguous out: exp(alpha_t(s) + beta'_t(s) + nll) for t < T_b, s <= 2L_b, formed as
  *         alpha + beta' normalised per row; exactly 0 for t >= T_b, s > 2L_b, at states no path passes through and on
  *         every row of a sample with no alignment (L_b = 0: gamma[b,t,0] = 1 for t < T_b)
@@ -401,7 +443,7 @@ int ctc_amd_blank_posteriors_wide(const float *log_probs, int64_t stride_t, int6
  *              followed by one correctly rounded fp32 division by float(end - start); 0 where start is -1.  The order is
  *              part of the contract: a float32 loop in that order reproduces the bits.
  * The class of span j is targets[b,j].  Samples with no alignment or with lengths out of contract get in path, score,
- * nll and frame_conf what the two entries above leave there (path -1, score -inf, nll +inf or NaN, frame_conf 0).
+ * nll and frame_conf what the two entries above leave there (path -1, score -inf, nll +inf, frame_conf 0).
  * Null pointers, T, B, C, S < 1 and a blank outside [0, C) return CTC_AMD_ERR_BAD_ARGUMENT before anything is
  * dereferenced or launched, and before S is looked at; S > 1023, or a lattice that does not fit the workspace,
  * CTC_AMD_ERR_UNSUPPORTED_SHAPE.
@@ -437,7 +479,8 @@ int ctc_amd_dedup_multihot_targets(const int32_t *rows, int B, int S, int C, int
 /* Per-step posteriors of the no-blank lattice: gamma[b,t,l] = P(state l at step
  * t | x, targets) = exp(alpha_t(l) + beta_t(l) + nll), the quantity the loss gradient scatters
  * by class; rows sum to 1 for t < T_b and are 0 beyond T_b / L_b.  Same inputs as
- * ctc_amd_noblank_loss_grad; gamma is [B,T,S] fp32 contiguous; nll [B] is also produced. */
+ * ctc_amd_noblank_loss_grad; gamma is [B,T,S] fp32 contiguous; nll [B] is also produced.  A sample with a length
+ * outside [1, T] / [1, S]: nll >= 1e12, all T rows of gamma 0; labels outside [0, C): modulo C (Conventions). */
 int ctc_amd_noblank_posteriors(const float *x, int64_t stride_t, int64_t stride_b,
                                const void *labels, int labels_i64,
                                const int64_t *in_len, const int64_t *tgt_len,
@@ -448,7 +491,7 @@ int ctc_amd_noblank_posteriors(const float *x, int64_t stride_t, int64_t stride_
 /* The same for the binary lattice (NoBlankBinaryCTC): gamma[b,t,l] = P(target row l at step t | x, y) -- what the
  * binary loss gradient contracts with the target rows.  y [B,S,C] as ctc_amd_binary_loss_grad; gamma [B,T,S], nll [B].
  * Shapes of the pipelined binary kernel only (S <= 64, T <= 168, C <= 256, LDS images fit); others return
- * CTC_AMD_ERR_UNSUPPORTED_SHAPE. */
+ * CTC_AMD_ERR_UNSUPPORTED_SHAPE.  Lengths outside their range: as ctc_amd_noblank_posteriors. */
 int ctc_amd_binary_posteriors(const float *x, int64_t stride_t, int64_t stride_b, const float *y,
                               const int64_t *in_len, const int64_t *tgt_len,
                               int T, int B, int C, int S,

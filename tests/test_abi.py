@@ -40,6 +40,62 @@ def test_binding_covers_header(built):
     assert b"success" in lib.ctc_amd_error_string(0)
 
 
+def _c_kind(decl):
+    """one C parameter or return declaration -> 'ptr', 'int', 'int64', 'float', 'size_t', 'unsigned', 'void'"""
+    decl = " ".join(decl.replace("*", " * ").split())
+    if "*" in decl:
+        return "ptr"
+    words = [w for w in decl.split() if w != "const"]
+    kinds = {"int": "int", "int64_t": "int64", "float": "float", "size_t": "size_t", "unsigned": "unsigned", "void": "void"}
+    assert words and words[0] in kinds, decl
+    return kinds[words[0]]
+
+
+def _header_prototypes():
+    """name -> (return kind, [argument kinds]) of every prototype of include/ctc_amd.h, comments stripped"""
+    src = open(os.path.join(ROOT, "include", "ctc_amd.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = "\n".join(l for l in src.splitlines() if not l.lstrip().startswith("#"))
+    out = {}
+    for ret, name, args in re.findall(r"([A-Za-z_][A-Za-z_0-9 \t\n\*]*?)\b(ctc_amd_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", src):
+        ret = ret.replace('extern "C"', "").replace("{", " ").strip()
+        args = [a.strip() for a in args.split(",")]
+        out[name] = (_c_kind(ret), [] if args == ["void"] else [_c_kind(a) for a in args])
+    return out
+
+
+def _ctypes_kind(t):
+    if t is None:
+        return "void"
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or isinstance(t, type(ctypes.POINTER(ctypes.c_uint))):
+        return "ptr"
+    return {ctypes.c_int: "int", ctypes.c_int64: "int64", ctypes.c_float: "float", ctypes.c_size_t: "size_t",
+            ctypes.c_uint: "unsigned"}[t]
+
+
+def test_binding_types_are_the_headers():
+    """_lib.PROTOTYPES against the header position by position: pointer -> a pointer type, int, int64_t, float, size_t.
+    An `int` where the header says `int64_t` would pass every call until a stride exceeds 2^31."""
+    from ctc_amd import _lib
+    assert ctypes.sizeof(ctypes.c_int64) == 8 and ctypes.c_int64 is not ctypes.c_int      # the kinds below tell them apart
+    assert ctypes.c_size_t is not ctypes.c_int and ctypes.c_size_t is not ctypes.c_uint
+    header = _header_prototypes()
+    assert sorted(header) == _declared() == sorted(_lib.PROTOTYPES) and len(header) >= 59
+    wrong = []
+    for name, (ret, args) in header.items():
+        res, argtypes = _lib.PROTOTYPES[name]
+        got = (_ctypes_kind(res), [_ctypes_kind(t) for t in argtypes])
+        if got != (ret, args):
+            wrong.append((name, "header", (ret, args), "binding", got))
+    assert not wrong, wrong
+    # the parser tells the kinds apart: spot checks against prototypes read by eye
+    assert header["ctc_amd_workspace_bytes"] == ("size_t", ["int"] * 5)
+    assert header["ctc_amd_error_string"] == ("ptr", ["int"])
+    assert header["ctc_amd_scale_grad"] == ("int", ["ptr", "ptr", "size_t", "ptr"])
+    assert header["ctc_amd_noblank_loss_grad"][1][:5] == ["ptr", "int64", "int64", "ptr", "int"]
+    assert header["ctc_amd_noblank_loss_grad"][1][11:13] == ["float", "float"]
+
+
 def test_argument_errors_without_gpu(built):
     from ctc_amd import _lib
     lib = _lib.load()
