@@ -122,6 +122,11 @@ PROTOTYPES = {
     # exact scores of given label sequences: N candidates per sample (or one set shared by the batch) in one launch
     "ctc_amd_sequence_scores": (_int, [_vp, _i64, _i64, _vp, _int, _int, _int, _int, _vp, _int, _i64, _i64, _int,
                                        _vp, _i64, _vp, _int, _vp, _vp]),
+    # ... and the weighted sum of their gradients (N-best discriminative training): the same arguments, then w, grad,
+    # scores (or NULL) and the scratch
+    "ctc_amd_sequence_scores_grad_scratch_bytes": (_sz, [_int, _int, _int, _int, _int, _int]),
+    "ctc_amd_sequence_scores_grad": (_int, [_vp, _i64, _i64, _vp, _int, _int, _int, _int, _vp, _int, _i64, _i64, _int,
+                                            _vp, _i64, _vp, _int, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

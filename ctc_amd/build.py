@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 SO = os.path.join(LIBDIR, "libctc_amd.so")
 SOURCES = ["api.hip", "noblank.hip", "binary.hip", "blank.hip", "decode.hip", "blank_align.hip", "targets.hip", "producer.hip",
-           "evaluate.hip", "beam_search.hip", "sequence_scores.hip"]
+           "evaluate.hip", "beam_search.hip", "sequence_scores.hip", "sequence_scores_grad.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 

@@ -1131,7 +1131,8 @@ def noblank_beam_search(logits, input_lengths, beam_width=16, nbest=1, top_class
 SEQUENCE_SCORES_MAX_LABELS = 255   # ctc_amd_sequence_scores: 511 blank-lattice states, at most 8 per lane of one wave
 
 
-def _sequence_scores(x, name, input_lengths, sequences, sequence_lengths, counts, blank):
+def _sequence_scores_call(x, name, input_lengths, sequences, sequence_lengths, counts, blank):
+    """the checks and the placement of a call -> (x detached, unit class stride; everything else of the call)"""
     if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.dtype != torch.float32:
         raise ValueError("ctc_amd: %s must be a float32 tensor [T,B,C]" % name)
     T, B, C = x.shape
@@ -1179,17 +1180,110 @@ def _sequence_scores(x, name, input_lengths, sequences, sequence_lengths, counts
         sl = sl.contiguous()
     if counts is not None:
         counts = _placed(counts.detach(), dev)
-    scores = torch.empty((B, N), dtype=torch.float32, device=dev)
-    lib = _lib.load()
+    # everything of a call but x, as both entries take it
+    cands = (seq.data_ptr(), int(seq.dtype == torch.int64), 0 if shared else seq.stride(0), seq.stride(-2), L,
+             sl.data_ptr(), 0 if shared else sl.stride(0), None if counts is None else counts.data_ptr(), N)
+    return xs, _SequenceScoresCall(il, -1 if blank is None else int(blank), cands, (seq, sl, counts))
+
+
+def _sequence_scores(x, name, input_lengths, sequences, sequence_lengths, counts, blank):
+    xs, call = _sequence_scores_call(x, name, input_lengths, sequences, sequence_lengths, counts, blank)
+    C = x.shape[2]
+    if x.requires_grad and torch.is_grad_enabled():
+        if C > SEQUENCE_SCORES_GRAD_MAX_CLASSES:
+            raise _lib.CtcAmdError("ctc_amd: the gradient of the sequence scores takes at most %d classes, got C = %d "
+                                   "(detach %s, or call under torch.no_grad(), for the scores alone)"
+                                   % (SEQUENCE_SCORES_GRAD_MAX_CLASSES, C, name))
+        return _SequenceScoresFn.apply(x, call)
+    return _sequence_scores_forward(xs, call)
+
+
+SEQUENCE_SCORES_GRAD_MAX_CLASSES = 4096   # ctc_amd_sequence_scores_grad: the staged path of the forward kernel only
+
+
+class _SequenceScoresCall(NamedTuple):
+    input_lengths: torch.Tensor    # [B] int64 on the device
+    blank: int                     # -1: the no-blank lattice
+    cands: tuple                   # the arguments from `seq` to `N` of both C entries
+    keep: tuple                    # the tensors those pointers belong to
+
+
+def _sequence_scores_forward(xs, call):
+    T, B, C = xs.shape
+    dev = xs.device
+    scores = torch.empty((B, call.cands[-1]), dtype=torch.float32, device=dev)
     with _on_device(dev):
-        rc = lib.ctc_amd_sequence_scores(xs.data_ptr(), xs.stride(0), xs.stride(1), il.data_ptr(), T, B, C,
-                                         -1 if blank is None else int(blank), seq.data_ptr(),
-                                         int(seq.dtype == torch.int64), 0 if shared else seq.stride(0), seq.stride(-2), L,
-                                         sl.data_ptr(), 0 if shared else sl.stride(0),
-                                         None if counts is None else counts.data_ptr(), N, scores.data_ptr(),
-                                         _stream_handle(dev))
+        rc = _lib.load().ctc_amd_sequence_scores(xs.data_ptr(), xs.stride(0), xs.stride(1), call.input_lengths.data_ptr(),
+                                                 T, B, C, call.blank, *call.cands, scores.data_ptr(), _stream_handle(dev))
     _lib.check(rc, "ctc_amd_sequence_scores")
     return scores
+
+
+def _scratch(kind, need, device):
+    """`need` bytes of device memory for a launch that wants scratch (contents mean nothing before and after), from the
+    cache of `_workspace`: one growing buffer per (device, stream, kind), superseded by one at least 1.5x as large when
+    it is too small, never freed while a captured graph may hold its pointer -- `release_workspaces()` frees it."""
+    key = (device.index, _stream_handle(device), kind)
+    held = _workspaces.get(key)
+    if held is None:
+        held = _workspaces[key] = []
+    if not held or held[-1].numel() < need:
+        size = need if not held else max(need, held[-1].numel() + held[-1].numel() // 2)
+        held.append(torch.empty((size + 4095) & ~4095, dtype=torch.uint8, device=device))
+    return held[-1]
+
+
+def _sequence_scores_grad(xs, call, w, out=None, want_scores=False):
+    """One call of ctc_amd_sequence_scores_grad: xs [T,B,C] float32 (unit class stride), w [B,N] float32 -> the weighted
+    gradient [T,B,C] (written into `out`, any frame / batch strides, when given), with the scores when asked."""
+    T, B, C = xs.shape
+    dev = xs.device
+    N, L = call.cands[-1], call.cands[4]
+    if w.dtype != torch.float32 or tuple(w.shape) != (B, N):
+        raise ValueError("ctc_amd: the weights of the sequence scores must be float32 [%d,%d]" % (B, N))
+    if w.stride(1) != 1:
+        w = w.contiguous()
+    grad = torch.empty((T, B, C), dtype=torch.float32, device=dev) if out is None else out
+    scores = torch.empty((B, N), dtype=torch.float32, device=dev) if want_scores else None
+    lib = _lib.load()
+    need = lib.ctc_amd_sequence_scores_grad_scratch_bytes(T, B, C, N, L, call.blank)
+    if need == 0:
+        raise _lib.CtcAmdError("ctc_amd: the gradient of the sequence scores takes at most %d classes and %d labels, got "
+                               "C = %d, L = %d" % (SEQUENCE_SCORES_GRAD_MAX_CLASSES, SEQUENCE_SCORES_MAX_LABELS, C, L))
+    scratch = _scratch("sequence_scores_grad", need, dev)
+    with _on_device(dev):
+        rc = lib.ctc_amd_sequence_scores_grad(xs.data_ptr(), xs.stride(0), xs.stride(1), call.input_lengths.data_ptr(),
+                                              T, B, C, call.blank, *call.cands, w.data_ptr(), w.stride(0),
+                                              grad.data_ptr(), grad.stride(0), grad.stride(1),
+                                              None if scores is None else scores.data_ptr(),
+                                              scratch.data_ptr(), scratch.numel(), _stream_handle(dev))
+    _lib.check(rc, "ctc_amd_sequence_scores_grad")
+    return (grad, scores) if want_scores else grad
+
+
+class _SequenceScoresFn(torch.autograd.Function):
+    """scores = the forward launch, unchanged; backward = one call of ctc_amd_sequence_scores_grad with w = grad_output"""
+
+    @staticmethod
+    def forward(ctx, x, call):
+        xs = x.detach()
+        if xs.stride(2) != 1:
+            xs = xs.contiguous()
+        ctx.save_for_backward(x)
+        ctx.call = call
+        return _sequence_scores_forward(xs, call)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_scores):
+        (x,) = ctx.saved_tensors
+        xs = x.detach()
+        if xs.stride(2) != 1:
+            xs = xs.contiguous()
+        w = grad_scores
+        if w.dtype != torch.float32:
+            w = w.float()
+        return _sequence_scores_grad(xs, ctx.call, w), None
 
 
 def blank_sequence_scores(log_probs, input_lengths, sequences, sequence_lengths, counts=None, blank=0):
@@ -1197,7 +1291,7 @@ def blank_sequence_scores(log_probs, input_lengths, sequences, sequence_lengths,
     natural-log probability of candidate n for sample b, summed over ALL of its alignments of the first T_b frames --
     ``-nll`` of ``blank_ctc_loss`` on that sequence as the target, where that is finite.  All N candidates of all samples
     in one launch: N-best rescoring (``BeamHypotheses.scores`` is only a lower bound of this value), transcript retrieval,
-    scoring hypotheses made elsewhere.  There is NO gradient: the result does not require grad.
+    scoring hypotheses made elsewhere.  Differentiable in ``log_probs`` (below): N-best discriminative training.
 
     ``log_probs`` [T,B,C] float32 normalised log-probabilities on a HIP device (the contract of ``blank_ctc_loss``), any
     frame / batch strides (a view with another class stride is made contiguous); ``input_lengths`` [B], 0 <= T_b <= T.
@@ -1215,7 +1309,23 @@ def blank_sequence_scores(log_probs, input_lengths, sequences, sequence_lengths,
     the all-blank path.  NaN inputs give an unspecified value.
 
     One launch, no scratch, no host synchronisation, capture-safe, deterministic (two calls, or a graph replay, give the
-    same bits).  Within 1e-5 max(1, |score|) of float64 also at T = 2000.  DESIGN.md 3.15."""
+    same bits).  Within 1e-5 max(1, |score|) of float64 also at T = 2000.  DESIGN.md 3.15.
+
+    The gradient.  When ``log_probs`` requires grad and grad mode is on, the result requires grad; the
+    values are the same bits and the forward is the same launch (nothing is saved but the inputs).  ``backward`` is one
+    call of ``ctc_amd_sequence_scores_grad`` with the incoming gradient as weights: ``log_probs.grad[t, b, c] = sum over
+    n of grad_scores[b, n] * d scores[b, n] / d log_probs[t, b, c]``, a contiguous float32 [T,B,C] tensor, for all N
+    candidates at once, deterministic.  ``d scores[b, n] / d log_probs[t, b, c]`` is the occupancy of class c at frame t
+    in candidate n's own lattice (the sum of the state posteriors of the states that carry c), 0 for t >= T_b: the true
+    partial derivative with ``log_probs`` taken as free inputs -- NOT the ``exp(log_probs) - occupancy`` convention of
+    ``torch.nn.functional.ctc_loss`` and ``blank_ctc_loss``, which fold the ``log_softmax`` in front of the loss into the
+    gradient.  Behind a ``log_softmax`` the gradient that reaches the logits is the same.  A score that is ``-inf`` or
+    NaN takes no gradient, whatever arrives for it (NaN and inf included), and rows beyond ``counts`` take none either: the
+    candidate is skipped, not multiplied by 0, so ``torch.where(torch.isfinite(s), s, s.new_tensor(-1e30))`` followed by
+    a softmax over n is safe.  Where ``log_probs`` is ``-inf`` the gradient is 0.  C <= 4096 (``CtcAmdError`` beyond,
+    when a gradient is asked for).  The scratch of the backward (``ctc_amd_sequence_scores_grad_scratch_bytes``: about
+    16 (2L + 1) bytes per candidate and frame) comes from the module's growing workspace cache; ``release_workspaces()``
+    frees it.  Without a gradient -- the input does not require grad, or under ``torch.no_grad()`` -- nothing changes."""
     return _sequence_scores(log_probs, "log_probs", input_lengths, sequences, sequence_lengths, counts, int(blank))
 
 
@@ -1227,5 +1337,8 @@ def noblank_sequence_scores(logits, input_lengths, sequences, sequence_lengths, 
     the probability that the frames collapse to it; with equal neighbours it is what the loss's lattice gives for that
     target (the two labels are two states), not a collapse probability.  The empty sequence has an alignment only for
     T_b = 0 (score 0; -inf for T_b >= 1); fewer frames than labels: -inf.  A row that is ``-inf`` throughout gives an
-    unspecified value.  No gradient; everything else as there."""
+    unspecified value.  Everything else as there, the gradient included: here ``d scores[b, n] / d logits[t, b, c]`` is the
+    class occupancy minus ``softmax(logits[t, b])[c]`` (the log-sum-exp is taken inside, so this IS the gradient with
+    respect to the raw logits, the convention of ``noblank_ctc_loss``), and the softmax is taken once per row for all
+    candidates; a ``-inf`` or NaN score takes no gradient."""
     return _sequence_scores(logits, "logits", input_lengths, sequences, sequence_lengths, counts, None)

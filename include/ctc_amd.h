@@ -974,7 +974,7 @@ int ctc_amd_beam_search_lm(const float *x, int64_t stride_t, int64_t stride_b, c
  * summed over ALL of its alignments of the first T_b frames -- the exact value `scores` of ctc_amd_beam_search is a lower
  * bound of; N-best rescoring, transcript retrieval, scoring hypotheses made elsewhere.  One launch for all N candidates
  * of all samples: a sample's rows are brought on chip once per group of 8 candidates and every candidate's forward chain
- * is fed from them.  No gradient, no scratch, no atomics, no waiting between workgroups (deterministic: the same inputs
+ * is fed from them.  (The gradient: ctc_amd_sequence_scores_grad below.)  No scratch, no atomics, no waiting between workgroups (deterministic: the same inputs
  * give the same bits), no allocation and no host synchronisation.
  *   x          [T,B,C] fp32 at x[t * stride_t + b * stride_b + c] (strides in elements, unit class stride).  blank >= 0:
  *              normalised log-probabilities, the contract of ctc_amd_blank_loss_grad; the lattice is torch.nn.CTCLoss's
@@ -1017,6 +1017,55 @@ int ctc_amd_sequence_scores(const float *x, int64_t stride_t, int64_t stride_b, 
                             const void *seq, int seq_i64, int64_t seq_stride_b, int64_t seq_stride_n, int L,
                             const int64_t *seq_len, int64_t len_stride_b, const int32_t *count /* or NULL */,
                             int N, float *scores, void *stream);
+
+/* Gradient of those scores, for N-best discriminative training (minimum word error rate, MMI against
+ * competitors, contrastive training among transcripts): the weighted sum over a sample's candidates
+ *     grad[t, b, c] = sum over n "scored finite" of  w[b, n] * d scores[b, n] / d x[t, b, c],
+ * "scored finite": n < count[b] and scores[b, n] (as ctc_amd_sequence_scores gives it) finite.  All arguments up to N mean
+ * what they mean there; then
+ *   w          [B,N] fp32 at w[b * w_stride_b + n]: the weight of every score (d loss / d scores[b, n])
+ *   grad       [T,B,C] fp32 out at grad[t * grad_stride_t + b * grad_stride_b + c], strides of its own (in elements, unit
+ *              class stride); EVERY element is written
+ *   scores     [B,N] fp32 out or NULL: the scores, bit for bit those of ctc_amd_sequence_scores on the same inputs
+ *   scratch    ctc_amd_sequence_scores_grad_scratch_bytes(T, B, C, N, L, blank) bytes of device memory, 8-byte aligned; the
+ *              caller allocates, the contents before and after a call mean nothing
+ * The derivative, x taken as FREE inputs:
+ *   blank >= 0   d score / d x[t, c] = sum over the states s of the candidate's lattice that carry class c of gamma_t(s),
+ *                the class occupancy of the candidate's own lattice, t < T_b.  x holds log-probabilities and the kernel
+ *                does not know where they came from: this is the true partial derivative, NOT torch.nn.CTCLoss's
+ *                exp(x) - occupancy form, which has the log_softmax in front of the loss folded in.  Behind a log_softmax
+ *                the two agree (its backward subtracts softmax times the row sum, which is 1 per candidate).
+ *   blank < 0    x holds raw logits, the row's log-sum-exp is taken inside: d score / d x[t, c] = occupancy_t(c) -
+ *                softmax(x_t)[c], t < T_b; so grad = sum_n w_n occupancy_n - (sum over n scored finite of w_n) softmax(x_t),
+ *                the softmax taken once per row for all candidates.
+ *   Rows t >= T_b, and every row of a sample with T_b = 0, are exactly 0.  Where x is -inf the gradient is 0 (occupancy and
+ *   softmax are both 0 there), never NaN, for finite weights.
+ *   A candidate that is not scored finite -- n >= count[b], a NaN score (bad length, bad label), a -inf score (no
+ *   alignment) -- contributes exactly nothing whatever w[b, n] holds, NaN and inf included: it is skipped by its score, not
+ *   multiplied by 0.  The w of a candidate that IS scored finite must be finite.
+ * Scratch bytes: B N (8 T (S_L + 1) + 4 (L + 2)) rounded up to a multiple of 256, S_L = 2 L + 1 for blank >= 0 and L for
+ *   blank < 0 -- per candidate and frame the S_L forward states and their S_L emissions (fp32) and one offset (double);
+ *   per candidate L + 1 label ranks and the score.  0 when an argument is out of range (T, B, C, N or L < 1, L > 255,
+ *   C > 4096, blank >= C).  About 1.5 GB at T = 2000, B = 64, N = 4, L = 180 on the blank lattice.
+ * Deterministic: no atomics and no arrival order anywhere.  The candidates of a sample are added in the order n = 0, 1, ..;
+ *   inside a candidate the blank states are summed by one fixed tree and the k-th occurrences of the classes are added in
+ *   the order k = 0, 1, ..  So two calls, and the replay of a captured graph, give the same bits; candidates that follow with
+ *   w = 0 do not change them; a shared candidate set (seq_stride_b = 0) gives the bits of the expanded one.
+ * Three launches on `stream` (the forward kernel storing its rows, a backward chain per candidate, a fold over the
+ *   candidates per frame), no allocation, no host synchronisation: safe under stream capture.
+ * Arithmetic as for the scores; gamma within 2e-4 (T <= 300) / 5e-4 (T = 2000) of float64, so |grad - exact| <= that
+ *   times sum_n |w[b, n]|.
+ * A NULL x, in_len, seq, seq_len, w, grad or scratch, T, B, C, N or L < 1, blank >= C, a scratch not 8-byte aligned:
+ * CTC_AMD_ERR_BAD_ARGUMENT; then L > 255, C > 4096 (only the staged path of ctc_amd_sequence_scores is taken), more than
+ * 2^31 - 1 workgroups, scratch_bytes below the formula: CTC_AMD_ERR_UNSUPPORTED_SHAPE; all before any HIP call. */
+size_t ctc_amd_sequence_scores_grad_scratch_bytes(int T, int B, int C, int N, int L, int blank);
+int ctc_amd_sequence_scores_grad(const float *x, int64_t stride_t, int64_t stride_b, const int64_t *in_len,
+                                 int T, int B, int C, int blank /* < 0: the no-blank lattice, x raw logits */,
+                                 const void *seq, int seq_i64, int64_t seq_stride_b, int64_t seq_stride_n, int L,
+                                 const int64_t *seq_len, int64_t len_stride_b, const int32_t *count /* or NULL */, int N,
+                                 const float *w, int64_t w_stride_b,
+                                 float *grad, int64_t grad_stride_t, int64_t grad_stride_b, float *scores /* or NULL */,
+                                 void *scratch, size_t scratch_bytes, void *stream);
 
 #ifdef __cplusplus
 }
