@@ -35,6 +35,8 @@ struct BinaryParams {
     float *nll, *loss, *grad;
     float *gamma;                // optional [B][T][S] posteriors output (ctc_amd_binary_posteriors; pipelined kernel only)
     unsigned *counter;
+    const float *upstream;       // streamed kernel: a folded scale_grad call's grad_out -- every gradient value is multiplied
+                                 // by *upstream as it is stored (launch.hpp); null: 1.  The other kernels never read it.
 };
 
 constexpr int kBinThreads = 1024;
@@ -1142,6 +1144,7 @@ static int binary_params(BinaryParams &p, const void *x, int64_t stride_t, int64
     p.nll = nll; p.loss = gamma ? reinterpret_cast<float *>(static_cast<char *>(workspace) + 32) : loss;
     p.grad = gamma ? nullptr : grad; p.gamma = gamma;
     p.counter = static_cast<unsigned *>(workspace);
+    p.upstream = nullptr;
     return 0;
 }
 
@@ -1206,6 +1209,10 @@ static int binary_launch(const BinaryPlan &pl, int dtype, BinaryParams &p, hipSt
         using E = typename decltype(elem)::type;
         if (pl.family == kBinaryFlow)   // (a with_constant list ends in its fallthrough: binary_plan gives this kernel ch <= 3 only)
             return with_constant<1, 2, 3>(pl.ch, [&](auto ch) {
+                // (the loss launch of this kernel takes a folded scale_grad: remembered when captured, launch.hpp)
+                if constexpr (!GAMMA)
+                    return launch_loss<binary_flow_kernel<decltype(ch)::value, WT, GAMMA, E>>(
+                        grid, block, pl.lds, s, true, CTC_AMD_F32, (size_t)p.T * p.B * p.C, p, pl.pd);
                 return launch<binary_flow_kernel<decltype(ch)::value, WT, GAMMA, E>>(grid, block, pl.lds, s, p, pl.pd);
             });
         return with_constant<1, 2, 3, 4>(pl.ch, [&](auto ch) {

@@ -53,7 +53,7 @@ __host__ __device__ inline size_t flow_y_floats(int SP, int C, int PD)
 }
 
 struct BinaryFlowSmem {
-    float *em, *al, *be, *dummy, *q, *zrow, *ys, *dimg;
+    float *em, *al, *be, *dummy, *q, *zrow, *ys, *dimg, *up;
     unsigned short *y16;
     int *prog, *fail, *tile, *done, *ystage;
     __device__ BinaryFlowSmem(float *base, int T, int SP, int PD, int C)
@@ -68,6 +68,7 @@ struct BinaryFlowSmem {
         tile = f + 8;                                        // [kFlowMaxTiles] emission tile m is in LDS
         done = f + 20;                                       // [kFlowWorkers] rounds of logs worker u has published
         ystage = f + 32;                                     // [kFlowFirstWorker] that wave's share of the bf16 target images is in LDS (1: exact, 2: not)
+        up = dummy + 40;                                     // [kBinWaves] each wave's copy of the launch's upstream scalar (a folded scale_grad call)
         q = dummy + kFlowFlags;
         zrow = q + ((T + 7) & ~3);                            // (q[T]: where idle slots put their sum)
         ys = zrow + 64;
@@ -186,6 +187,10 @@ __global__ __launch_bounds__(kBinThreads) void binary_flow_kernel(BinaryParams p
     }
     __syncthreads();                                         // the flags exist (no wave has waited for memory yet)
     const ScalarLengths lens(p.in_len + b, p.tgt_len + b);
+    // ... and the upstream scalar of a folded scale_grad call (launch.hpp) comes the same way.  Every wave parks its copy in
+    // an LDS word of its own as soon as its lengths are there (below) and reads it back where it stores gradient rows: no
+    // register is held in between (this kernel has none to spare), and a wave's own LDS operations complete in order.
+    const ScalarUpstream upstream(GAMMA ? nullptr : p.upstream);
 
     // Targets -> LDS: the fp32 image [SP][PD] (the gradient's contraction reads it) and the bf16 image Y16[SP + 1][YP] of
     // their high halves (B operand of the emission tiles; row SP is zeros), zero beyond S labels / C classes (MFMA K and N
@@ -225,6 +230,7 @@ __global__ __launch_bounds__(kBinThreads) void binary_flow_kernel(BinaryParams p
     }
     int64_t Tb64, L64;
     lens.get(Tb64, L64);
+    if (!GAMMA) sm.up[w] = upstream.value();
     const bool ok = L64 >= 1 && L64 <= p.S && Tb64 >= L64 && Tb64 <= p.T;
     const int Tb = ok ? (int)Tb64 : 0, L = ok ? (int)L64 : 0;
     const float invC = 1.0f / (float)p.C;
@@ -375,6 +381,9 @@ __global__ __launch_bounds__(kBinThreads) void binary_flow_kernel(BinaryParams p
             return;
         }
         lds_order();
+        // (1.0f has one bit pattern; a NaN multiplies, as `s == 1.0f` of scale_grad_kernel has it.  Wave-uniform.)
+        const float go = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, sm.up[w])));
+        const bool scaled = __builtin_bit_cast(unsigned, go) != 0x3f800000u;
         f32x4 acc[CH];
 #pragma unroll
         for (int j = 0; j < CH; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -411,7 +420,9 @@ __global__ __launch_bounds__(kBinThreads) void binary_flow_kernel(BinaryParams p
             }
         }
         // the usual group -- four live rows, none with tails -- in one piece: one uniform branch instead of a dozen
-        if (!starved && slow4 == 0 && tl[0] >= 0 && tl[1] >= 0 && tl[2] >= 0 && tl[3] >= 0) {
+        // (a folded scale_grad call whose grad_out is not 1 takes the row-by-row path below, which multiplies the finished
+        // value once more, as the scale kernel would have)
+        if (!scaled && !starved && slow4 == 0 && tl[0] >= 0 && tl[1] >= 0 && tl[2] >= 0 && tl[3] >= 0) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 float *g = p.grad + ((int64_t)tl[i] * p.B + b) * p.C;
@@ -431,7 +442,8 @@ __global__ __launch_bounds__(kBinThreads) void binary_flow_kernel(BinaryParams p
             bin_row_base_settled(g);
             const int slot = 2 * (i & 1) + (i >> 1);         // (bit of slow4: slots (2jg, 0), (2jg, 1), (2jg+1, 0), (2jg+1, 1))
             if (tl[i] < 0 || starved) {                      // (uniform) dead row: zeros; starved: NaN
-                const float fill = starved ? __builtin_nanf("") : 0.f;
+                float fill = starved ? __builtin_nanf("") : 0.f;
+                if (scaled) fill *= go;
 #pragma unroll
                 for (int j = 0; j < CH; ++j)
                     if (j < CH - 1 || lane + 64 * j < p.C) bin_store_col<WT>(g, voff, j, fill);
@@ -440,14 +452,17 @@ __global__ __launch_bounds__(kBinThreads) void binary_flow_kernel(BinaryParams p
                 for (int j = 0; j < CH; ++j) {
                     const float pr = P(i & 1, i >> 1, j);
                     const float pq = pr * (1.0f - pr);
-                    const float gv = __builtin_fmaf(pr, gs, -acc[j][i]) * (pq * __builtin_amdgcn_rcpf(fmaxf(pq, 1e-12f)));
+                    float gv = __builtin_fmaf(pr, gs, -acc[j][i]) * (pq * __builtin_amdgcn_rcpf(fmaxf(pq, 1e-12f)));
+                    if (scaled) gv *= go;
                     if (j < CH - 1 || lane + 64 * j < p.C) bin_store_col<WT>(g, voff, j, gv);
                 }
             } else {
 #pragma unroll
                 for (int j = 0; j < CH; ++j) {
                     const float pr = P(i & 1, i >> 1, j);
-                    if (j < CH - 1 || lane + 64 * j < p.C) bin_store_col<WT>(g, voff, j, __builtin_fmaf(pr, gs, -acc[j][i]));
+                    float gv = __builtin_fmaf(pr, gs, -acc[j][i]);
+                    if (scaled) gv *= go;
+                    if (j < CH - 1 || lane + 64 * j < p.C) bin_store_col<WT>(g, voff, j, gv);
                 }
             }
         }

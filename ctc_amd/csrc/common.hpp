@@ -390,6 +390,20 @@ struct ScalarLengths {
     }
 };
 
+// The upstream gradient scalar of a scale_grad call folded into this launch (launch.hpp; `up` null: there is none, and
+// the value is 1), through the same scalar path and for the same reasons.  The load is unconditional -- without a pointer
+// it reads a 1.0f of the library's own.
+static __device__ const float kUnitUpstream = 1.0f;
+struct ScalarUpstream {
+    float v;
+    __device__ __forceinline__ explicit ScalarUpstream(const float *up)
+    {
+        typedef const __attribute__((address_space(4))) float const_f32;
+        v = *(const_f32 *)(uintptr_t)(up ? up : &kUnitUpstream);
+    }
+    __device__ __forceinline__ float value() const { return v; }
+};
+
 // Diagnostics only (CTC_AMD_DEBUG_STOP = -(wave+1)): that wave of workgroup 0 stamps
 // (s_memtime, s_memrealtime) pairs into workspace bytes [64,256) at phase boundaries
 // (tools/stamps.py reads them).  Never executes in a normal run (p.stop == 0).

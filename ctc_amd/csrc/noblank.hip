@@ -46,6 +46,8 @@ struct NoblankParams {
     int next_round;             // > 0: B exceeds one round of workgroups -- blocks prefetch for block + next_round
     float ls_a, ls_b;           // label-smoothed emission a lp[c_l] + b sum_n lp[n] (NoBlankCTC.py:100-107); 1, 0: plain
     int koff;                   // noblank_km_kernel: what the exponent recurrence starts with (log2 of the path count / 2)
+    const float *upstream;      // r16 kernel: a folded scale_grad call's grad_out -- every gradient value is multiplied by
+                                // *upstream as it is stored (launch.hpp); null: 1.  The other kernels never read it.
 };
 
 // Every field through an empty volatile asm: the copy holds the same values, but the compiler no longer knows that
@@ -58,7 +60,7 @@ __device__ __forceinline__ NoblankParams opaque_params(NoblankParams q)
     CTC_OPQ(x); CTC_OPQ(st); CTC_OPQ(sb); CTC_OPQ(lab); CTC_OPQ(lab64); CTC_OPQ(in_len); CTC_OPQ(tgt_len);
     CTC_OPQ(T); CTC_OPQ(B); CTC_OPQ(C); CTC_OPQ(S); CTC_OPQ(SP); CTC_OPQ(stop); CTC_OPQ(loss_scale); CTC_OPQ(grad_scale);
     CTC_OPQ(nll); CTC_OPQ(loss); CTC_OPQ(grad); CTC_OPQ(gamma); CTC_OPQ(lattice); CTC_OPQ(slab); CTC_OPQ(counter);
-    CTC_OPQ(next_round); CTC_OPQ(ls_a); CTC_OPQ(ls_b); CTC_OPQ(koff);
+    CTC_OPQ(next_round); CTC_OPQ(ls_a); CTC_OPQ(ls_b); CTC_OPQ(koff); CTC_OPQ(upstream);
 #undef CTC_OPQ
     return q;
 }
@@ -457,7 +459,13 @@ __global__ __launch_bounds__(256) void scale_grad_lowp_kernel(E *g, const float 
         }
         done = n4 * 4;
     }
-    for (size_t k = done + i; k < n; k += stride) g[k] = (E)((float)g[k] * s);
+    // (the tail through the same widen, multiply, narrow as the body: written as `(E)((float)g[k] * s)` the fp16 form
+    // compiles to a mixed-precision multiply-ADD of +0, which turns a -0 product into +0)
+    for (size_t k = done + i; k < n; k += stride) {
+        const unsigned short e = *reinterpret_cast<const unsigned short *>(g + k);
+        const f2_t v = r16_widen2<E>((unsigned)e) * f2_t{s, s};
+        *reinterpret_cast<unsigned short *>(g + k) = (unsigned short)r16_narrow2<E>(v);
+    }
 }
 
 // ---- host side of the entry points: parameters, then a plan, then a launch -------------------------
@@ -503,6 +511,7 @@ static int noblank_params(NoblankParams &p, const void *x, int64_t stride_t, int
     p.lattice = z.glb ? reinterpret_cast<float *>(ws + 256 + acc_list_bytes(B)) : nullptr;   // behind header and list
     p.slab = z.glb ? (int64_t)noblank_lattice_floats(T, z.SP) : 0;
     p.next_round = 0; p.koff = 0;
+    p.upstream = nullptr;
     const bool smooth = label_smoothing >= 0.f;
     p.ls_b = smooth ? (1.f - label_smoothing) / (float)C : 0.f;
     p.ls_a = smooth ? label_smoothing - p.ls_b : 1.f;
@@ -631,9 +640,12 @@ static int noblank_launch(const NoblankPlan &pl, int dtype, NoblankParams &p, hi
                                                      std::conditional_t<decltype(dt)::value == CTC_AMD_F16, _Float16, float>>;
                         constexpr int A = decltype(n4)::value, Bq = decltype(n2)::value;
                         constexpr bool NT = decltype(nt)::value != 0;
+                        // (the kernel that takes a folded scale_grad: remembered when captured, launch.hpp)
+                        const size_t n = (size_t)p.T * p.B * p.C;
                         if constexpr (4 * A + 2 * Bq <= 12)
-                            if (pl.ps) return launch<noblank_r16_kernel<A, Bq, NT, true, E>>(grid, block, pl.lds, s, p);
-                        return launch<noblank_r16_kernel<A, Bq, NT, false, E>>(grid, block, pl.lds, s, p);
+                            if (pl.ps)
+                                return launch_loss<noblank_r16_kernel<A, Bq, NT, true, E>>(grid, block, pl.lds, s, !p.gamma, dtype, n, p);
+                        return launch_loss<noblank_r16_kernel<A, Bq, NT, false, E>>(grid, block, pl.lds, s, !p.gamma, dtype, n, p);
                     });
                 });
             });
@@ -741,6 +753,7 @@ extern "C" int ctc_amd_scale_grad(float *grad, const float *grad_out, size_t n, 
 {
     if (!grad || !grad_out) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (n == 0) return 0;
+    if (fold_scale_grad(static_cast<hipStream_t>(stream), grad, CTC_AMD_F32, grad_out, n)) return 0;
     hipLaunchKernelGGL(scale_grad_kernel, scale_grad_grid(n), dim3(256), 0,
                        static_cast<hipStream_t>(stream), grad, grad_out, n);
     return (int)hipGetLastError();
@@ -765,6 +778,7 @@ extern "C" int ctc_amd_scale_grad_typed(void *grad, int dtype, const float *grad
     if (dtype == CTC_AMD_F32) return ctc_amd_scale_grad(static_cast<float *>(grad), grad_out, n, stream);
     if ((dtype != CTC_AMD_BF16 && dtype != CTC_AMD_F16) || !grad || !grad_out) return CTC_AMD_ERR_BAD_ARGUMENT;
     if (n == 0) return 0;
+    if (fold_scale_grad(static_cast<hipStream_t>(stream), grad, dtype, grad_out, n)) return 0;
     if (dtype == CTC_AMD_BF16)
         hipLaunchKernelGGL(scale_grad_lowp_kernel<__bf16>, scale_grad_grid(n), dim3(256), 0,
                            static_cast<hipStream_t>(stream), static_cast<__bf16 *>(grad), grad_out, n);
@@ -802,6 +816,16 @@ extern "C" int ctc_amd_noblank_posteriors_typed(const void *x, int x_dtype, int6
 }
 
 #ifdef CTC_AMD_DIAGNOSTICS
+// Diagnostic entry point (tests/test_scale_fold_gpu.py), not part of include/ctc_amd.h: how many scale_grad calls were
+// folded into a captured loss launch / met a remembered launch under capture and were refused, since the library was loaded.
+extern "C" int ctc_amd_debug_scale_folds(unsigned *taken, unsigned *refused)
+{
+    if (!taken || !refused) return CTC_AMD_ERR_BAD_ARGUMENT;
+    *taken = ctc::fold_table().taken.load(std::memory_order_relaxed);
+    *refused = ctc::fold_table().refused.load(std::memory_order_relaxed);
+    return 0;
+}
+
 // Diagnostic entry point (tools/chain_probe.py), not part of include/ctc_amd.h: the lattice chains of
 // noblank_r16.hpp alone, every emission row pre-published; out[0], out[1] = shader cycles of the
 // alpha / beta chain.

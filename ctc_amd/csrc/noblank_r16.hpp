@@ -85,7 +85,7 @@ __device__ __forceinline__ int r16_row(int T, int u, int g, int k)
 struct R16Smem {
     int TP;
     cell_t *em, *al, *be;                                    // (mantissa, exponent) cells, [state][time]
-    float *dummy, *stage, *cs;
+    float *dummy, *stage, *cs, *up;
     int *cnt, *lab, *occ, *done;
     __device__ R16Smem(float *base, int T, int SP, int RP)
     {
@@ -100,6 +100,7 @@ struct R16Smem {
         occ = lab + ((SP + 3) & ~3);                        // [SP] occurrence index, [SPpad] their maximum
         cs = reinterpret_cast<float *>(occ + ((SP + 3) & ~3) + 4);      // [workers][4 rows]: sum over the row slots of the per-row constants
         done = reinterpret_cast<int *>(cs + 4 * kPipeWorkers);          // workers whose constants are in `cs`
+        up = cs + 4 * kPipeWorkers + 4;                                 // the launch's upstream scalar (a folded scale_grad call), or 1
         stage = cs + 64;                                                 // [workers][4 rows][RP]
     }
 };
@@ -521,26 +522,46 @@ struct R16Row : R16RawRegs<sizeof(E) == 2, N4, N2> {
     }
     // grad row = x * rs + tile, the tile holding MINUS the class occupancy (nothing to negate here), written through;
     // `g` = start of the row in grad (`cb`: a constant added to every element -- the label-smoothing term, 0 otherwise)
-    template <bool NT, bool LS>
-    __device__ __forceinline__ void store_grad(E *g, const float *trow, int i16, float rs, bool col_ok, float cb) const
+    // SC: a folded scale_grad call (launch.hpp) -- the finished value times `go`, a second rounding exactly as
+    // scale_grad_kernel / scale_grad_lowp_kernel apply it to the stored value (2-byte: narrow, widen, multiply, narrow), so
+    // the launch gives the bits of the two launches; !SC is the code of a launch without the pointer
+    template <bool NT, bool LS, bool SC = false>
+    __device__ __forceinline__ void store_grad(E *g, const float *trow, int i16, float rs, bool col_ok, float cb, float go = 1.f) const
     {
         const f2_t r2 = {rs, rs}, cb2 = {cb, cb};
+        // (`go` is wave-uniform and stays in its scalar register: a packed multiply would want it twice in vector registers)
+        auto times_go = [&](float a) {
+            float r;
+            asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "s"(go), "v"(a));
+            return r;
+        };
+        auto scaled = [&](f2_t v) {
+            if constexpr (!SC) {
+                return v;
+            } else {
+                if constexpr (kLowp) v = r16_widen2<E>(r16_narrow2<E>(v));
+                return f2_t{times_go(v.x), times_go(v.y)};
+            }
+        };
         // every tile read first, then the arithmetic and the stores: a gradient store is inline asm with a memory clobber,
         // and a tile read placed behind one waits for its own LDS round trip with nothing else in flight -- three round
         // trips in a row per group
         f4_t o4[N4 > 0 ? N4 : 1];
         f2_t o2[N2 > 0 ? N2 : 1];
+        if constexpr (!SC) {
 #pragma unroll
-        for (int j = 0; j < N4; ++j) o4[j] = *reinterpret_cast<const f4_t *>(trow + off4(j, i16));
+            for (int j = 0; j < N4; ++j) o4[j] = *reinterpret_cast<const f4_t *>(trow + off4(j, i16));
 #pragma unroll
-        for (int k = 0; k < N2; ++k) o2[k] = *reinterpret_cast<const f2_t *>(trow + off2(k, i16));
+            for (int k = 0; k < N2; ++k) o2[k] = *reinterpret_cast<const f2_t *>(trow + off2(k, i16));
+        }
 #pragma unroll
         for (int j = 0; j < N4; ++j) {
+            if constexpr (SC) o4[j] = *reinterpret_cast<const f4_t *>(trow + off4(j, i16));
             const f4_t o = o4[j];
             f2_t olo = {o.x, o.y}, ohi = {o.z, o.w};
             if (LS) { olo += cb2; ohi += cb2; }
             const f2_t xlo = {a[j].x, a[j].y}, xhi = {a[j].z, a[j].w};
-            const f2_t vlo = __builtin_elementwise_fma(xlo, r2, olo), vhi = __builtin_elementwise_fma(xhi, r2, ohi);
+            const f2_t vlo = scaled(__builtin_elementwise_fma(xlo, r2, olo)), vhi = scaled(__builtin_elementwise_fma(xhi, r2, ohi));
             if (!(kLast4 && j == N4 - 1) || col_ok) {
                 if constexpr (kLowp) {
                     const wt_u2 n = {r16_narrow2<E>(vlo), r16_narrow2<E>(vhi)};
@@ -553,9 +574,10 @@ struct R16Row : R16RawRegs<sizeof(E) == 2, N4, N2> {
         }
 #pragma unroll
         for (int k = 0; k < N2; ++k) {
+            if constexpr (SC) o2[k] = *reinterpret_cast<const f2_t *>(trow + off2(k, i16));
             f2_t o = o2[k];
             if (LS) o += cb2;
-            const f2_t v = __builtin_elementwise_fma(c[k], r2, o);
+            const f2_t v = scaled(__builtin_elementwise_fma(c[k], r2, o));
             if (k < N2 - 1 || col_ok) {
                 if constexpr (kLowp) grad_store<NT, unsigned, 4>(reinterpret_cast<unsigned *>(g + off2(k, i16)), r16_narrow2<E>(v));
                 else grad_store<NT>(reinterpret_cast<f2_t *>(g + off2(k, i16)), v);
@@ -577,21 +599,23 @@ struct R16Row : R16RawRegs<sizeof(E) == 2, N4, N2> {
             for (int k = 0; k < N2; ++k) asm volatile("" ::"v"(c[k]));
         }
     }
+    // (`zv`: the zero as stored -- 0, or 0 * grad_out of a folded scale_grad call, which has grad_out's sign or is NaN)
     template <bool NT>
-    __device__ static __forceinline__ void store_zero(E *g, int i16, bool col_ok)
+    __device__ static __forceinline__ void store_zero(E *g, int i16, bool col_ok, float zv = 0.f)
     {
         if constexpr (kLowp) {
-            const wt_u2 z4 = {0u, 0u};
+            const unsigned z = r16_narrow2<E>(f2_t{zv, zv});
+            const wt_u2 z4 = {z, z};
 #pragma unroll
             for (int j = 0; j < N4; ++j)
                 if (!(kLast4 && j == N4 - 1) || col_ok) grad_store<NT, wt_u2, 4>(reinterpret_cast<wt_u2 *>(g + off4(j, i16)), z4);
 #pragma unroll
             for (int k = 0; k < N2; ++k)
-                if (k < N2 - 1 || col_ok) grad_store<NT, unsigned, 4>(reinterpret_cast<unsigned *>(g + off2(k, i16)), 0u);
+                if (k < N2 - 1 || col_ok) grad_store<NT, unsigned, 4>(reinterpret_cast<unsigned *>(g + off2(k, i16)), z);
             return;
         }
-        const f4_t z4 = {0.f, 0.f, 0.f, 0.f};
-        const f2_t z2 = {0.f, 0.f};
+        const f4_t z4 = {zv, zv, zv, zv};
+        const f2_t z2 = {zv, zv};
 #pragma unroll
         for (int j = 0; j < N4; ++j)
             if (!(kLast4 && j == N4 - 1) || col_ok) grad_store<NT>(reinterpret_cast<f4_t *>(g + off4(j, i16)), z4);
@@ -659,6 +683,10 @@ __global__ __launch_bounds__(kThreads, 4) void noblank_r16_kernel(NoblankParams 
     // followed by a readfirstlane, i.e. a full memory round trip BEFORE the first row load is issued,
     // and later waits on the row loads degrade to vmcnt(0).
     ScalarLengths len(p.in_len + b, p.tgt_len + b);
+    // ... and so does the upstream scalar of a folded scale_grad call (launch.hpp), once per launch and by one wave, which
+    // leaves it in LDS in front of the first sample's barrier (it waits for its lengths there anyway): the workers pick it
+    // up when their gradient pass begins, and neither the pointer nor the value occupies a register in between.
+    if (w == kChainB) *sm.up = ScalarUpstream(p.upstream).value();
     // this lane's row in each group (the same rows t for every sample: they depend on T alone)
     int tv0[G];
     Row v[G];
@@ -853,9 +881,11 @@ __global__ __launch_bounds__(kThreads, 4) void noblank_r16_kernel(NoblankParams 
     } while (0)
     if (!PS && Tb == 0) {                                    // no alignment exists: zero gradient
         if (p.grad) {
+            const float go = *sm.up;                         // (a folded scale_grad call: 0 * grad_out, as its kernel would leave it)
+            const float zv = go != 1.0f ? 0.f * go : 0.f;
 #pragma unroll
             for (int g = 0; g < G; ++g)
-                if (tv[g] >= 0) Row::template store_zero<NT>(reinterpret_cast<E *>(p.grad) + ((int64_t)tv[g] * p.B + b) * p.C, i16, col_ok);
+                if (tv[g] >= 0) Row::template store_zero<NT>(reinterpret_cast<E *>(p.grad) + ((int64_t)tv[g] * p.B + b) * p.C, i16, col_ok, zv);
         }
         if (p.gamma) {                                                      // posteriors of a sample without alignment: zeros
 #pragma unroll
@@ -1081,6 +1111,10 @@ __global__ __launch_bounds__(kThreads, 4) void noblank_r16_kernel(NoblankParams 
     }
     const bool first_occ[2] = {own[0] && occn[0] == 0, own[1] && occn[1] == 0};
     float *const sink = sm.dummy + 4;                        // (write-only)
+    // (the upstream scalar of a folded scale_grad call from LDS, once per sample and in the workers' idle window: the
+    // chains are still running, the first group's wait lies ahead.  1.0f has one bit pattern; a NaN multiplies, as
+    // `s == 1.0f` of scale_grad_kernel has it.)
+    const unsigned go_bits = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(unsigned, *sm.up));
 #pragma unroll
     for (int g = G - 1; g >= 0; --g) {
         if (!grp[g]) continue;
@@ -1158,7 +1192,13 @@ __global__ __launch_bounds__(kThreads, 4) void noblank_r16_kernel(NoblankParams 
             const bool mass = !live || tot > 0.f;
             // (smoothed: `live` is false on every row of a sample whose row constants leave it without an alignment, while
             // rs[] still holds the scale of its rows -- both terms hang on live && tot > 0)
-            if (smooth) x.template store_grad<NT, true>(gp, trow, i16, live && mass ? rs[g] * (1.f - p.ls_b) : 0.f, col_ok, live && mass ? -p.ls_b * gsc : 0.f);
+            // (a folded scale_grad call whose grad_out is not 1: the same rows through the multiplying form -- one scalar
+            // compare and branch per group in front of the instruction stream of a launch without the pointer)
+            if (go_bits != 0x3f800000u) {
+                const float go = __builtin_bit_cast(float, go_bits);
+                if (smooth) x.template store_grad<NT, true, true>(gp, trow, i16, live && mass ? rs[g] * (1.f - p.ls_b) : 0.f, col_ok, live && mass ? -p.ls_b * gsc : 0.f, go);
+                else x.template store_grad<NT, false, true>(gp, trow, i16, mass ? rs[g] : 0.f, col_ok, 0.f, go);
+            } else if (smooth) x.template store_grad<NT, true>(gp, trow, i16, live && mass ? rs[g] * (1.f - p.ls_b) : 0.f, col_ok, live && mass ? -p.ls_b * gsc : 0.f);
             else x.template store_grad<NT, false>(gp, trow, i16, mass ? rs[g] : 0.f, col_ok, 0.f);
         }
         lds_order();

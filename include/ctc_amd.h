@@ -260,7 +260,21 @@ int ctc_amd_collective_gate(void *workspace, int B, int timeout_us, void *stream
 /* backward of the autograd.Function: grad[i] *= *grad_out (a device scalar, the
  * upstream gradient of the 0-dim loss).  Every workgroup reads *grad_out and exits
  * at once when it is exactly 1.0f (the loss.backward() case, train.py:444), so the
- * common case moves no data and needs no host synchronisation. */
+ * common case moves no data and needs no host synchronisation.
+ *
+ * Under stream capture the call may add no node at all: it is FOLDED into the loss launch it
+ * scales when (1) `stream` is capturing, (2) the call is issued directly behind a *_loss_grad
+ * launch captured on that same stream -- nothing else has been captured or joined in behind that
+ * launch -- (3) grad, n (and dtype, for the typed form) are exactly that launch's gradient buffer,
+ * element count (T * B * C) and element type, (4) it is the first scale call behind that launch and
+ * (5) the launched kernel takes the pointer (the no-blank r16 kernel in every form and the streamed
+ * binary kernel: the kernels of the default plans for S <= 31 / S <= 64; not blank CTC).  The loss
+ * kernel's graph node then receives `grad_out` as a kernel argument and multiplies every gradient
+ * value by *grad_out as it stores it -- read on the device at every replay, never a captured value,
+ * and with the second rounding of the scale kernel, so the result has the bits of the two launches;
+ * nll and loss are not scaled.  `grad_out` must stay valid for as long as the graph is replayed, as
+ * it must for the scale kernel's node.  An eager call, and every captured call that does not meet the
+ * conditions, launches the scale kernel as before; the answer is the same either way. */
 int ctc_amd_scale_grad(float *grad, const float *grad_out, size_t n, void *stream);
 
 /* ctc_amd_scale_grad for a gradient of element type `dtype` (CTC_AMD_F32 / _BF16 / _F16, as
